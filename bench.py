@@ -26,10 +26,17 @@ The first step's k_prep is its own launch.
 Steps follow decoding order, so the W warmup steps decode the first W
 pictures and the K timed steps the next K.
 
-Bit-exactness: after the timed loop an untimed pass decodes the same W + K
-steps again and compares EVERY picture of every stream of every rank with the
-reference decoder's per-frame MD5s (tests/golden/golden.json, made by running
-the reference C on the same generated streams, seeds 100..163).
+A plain run is that headline run alone: set up, warm up, time the K steps,
+write the last step's pictures if `--dump-outputs DIR` is given (dump_outputs)
+and print the line.  `--full` adds everything else the line can hold: the
+bit-exactness checks, the P-only window, the RGBA leg, the CPU baseline, the
+other configs' legs and the end-to-end leg.
+
+Bit-exactness (`--full`): after the timed loop an untimed pass decodes the
+same W + K steps again and compares EVERY picture of every stream of every
+rank with the reference decoder's per-frame MD5s (tests/golden/golden.json,
+made by running the reference C on the same generated streams, seeds
+100..163).
 
 Multi-GPU: one process per GPU, streams partitioned across ranks with no
 data-path collective -> "scaling": "weak"; the only
@@ -76,12 +83,19 @@ def parse_args(argv=None):
     ap.add_argument("--streams", type=int, default=8, help="streams per GPU (configs[3]: 8)")
     ap.add_argument("--config", type=int, default=3, help="generator preset (3 = 1080p I+P)")
     ap.add_argument("--gen", default="", help="generator overrides k=v,... (experiments; default: preset)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (host parse + GPU + D2H) leg")
-    ap.add_argument("--no-rgba", action="store_true", help="skip the RGBA output leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, everything else as well: the bit-exactness checks against the "
+                         "reference MD5s, the P-only window, the RGBA leg, the CPU baseline, the config legs and "
+                         "the end-to-end leg (each with its own --no-... switch); default: the headline run only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the pictures the last timed step reconstructed to DIR/*.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-verify", action="store_true", help="--full without the bit-exactness checks")
+    ap.add_argument("--no-e2e", action="store_true",
+                    help="--full without the end-to-end (host parse + GPU + D2H) leg")
+    ap.add_argument("--no-rgba", action="store_true", help="--full without the RGBA output leg")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the SURVEY §8d config 2 (720p I-only) / config 5 (2160p) legs")
+                    help="--full without the SURVEY §8d config 2 (720p I-only) / config 5 (2160p) legs")
     ap.add_argument("--pipe", type=int, default=int(os.environ.get("BENCH_PIPE", "3")),
                     help="steps per launch (1..4; default 3, profiles/r91_ab_pipe3.txt): with P > 1, a launch "
                          "reconstructs P consecutive pictures of every stream and a later picture's rows start as "
@@ -1111,6 +1125,35 @@ def timed_run(run, dist, torch, sync, stride=1):
     return dt, us / max(nb, 1), sampled, per
 
 
+DUMP_BUDGET = 48 << 20     # --dump-outputs: bytes of float32 samples over all ranks (the dump stays below 64 MB)
+
+
+def dump_outputs(run, seeds, outdir, budget=DUMP_BUDGET):
+    """--dump-outputs: the picture of every stream that the last timed step
+    reconstructed, as a caller of the device-resident path reads it back
+    (Engine.read: packed I420 bytes), right after the timed launches:
+      outdir/stream<seed>.npy       float32, the picture's bytes -- all of
+          them when the rank's pictures fit `budget`, else those at a fixed
+          sorted sample of byte offsets (default_rng(0): the same for every
+          stream, run and build)
+      outdir/stream<seed>_sums.npy  float64, the sum of each 64 consecutive
+          bytes of the whole picture, so that every byte enters the dump
+    Returns the (stream, picture) pairs written."""
+    os.makedirs(outdir, exist_ok=True)
+    last = run.launches[-1][-1]
+    keep = budget // (4 * len(last))
+    idx, out = None, []
+    for s, k in enumerate(last):
+        pic = run.eng.read(s, int(run.slot_of[k][s]))
+        if pic.size > keep and idx is None:
+            idx = np.sort(np.random.default_rng(0).choice(pic.size, size=keep, replace=False))
+        np.save(os.path.join(outdir, f"stream{seeds[s]}.npy"), (pic if idx is None else pic[idx]).astype(np.float32))
+        np.save(os.path.join(outdir, f"stream{seeds[s]}_sums.npy"),
+                np.add.reduceat(pic.astype(np.float64), np.arange(0, pic.size, 64)))
+        out.append((s, k))
+    return out
+
+
 def launch_split(run, sampled, per):
     """Sampled launches split by whether one of their pictures is an IDR
     (I picture): {"i": (n, avg us, avg us per step), "p": (...)}."""
@@ -1239,6 +1282,10 @@ def config_legs(L, torch):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     a = parse_args(argv)
+    if not a.full:
+        # a plain run is the headline run alone: set up, warm up, time the
+        # steps, dump the outputs if asked, print the line
+        a.no_cpu_baseline = a.no_verify = a.no_e2e = a.no_rgba = a.no_legs = True
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(a.gpus, argv))
     torch, dist, rank, local, world = dist_setup(a.gpus)
@@ -1279,6 +1326,8 @@ def main(argv=None):
     stride = int(os.environ.get("BENCH_TIMING_STRIDE", "1"))
 
     dt, step_us, sampled, per_launch = timed_run(run, dist, torch, sync, stride)
+    if a.dump_outputs:
+        dump_outputs(run, seeds, a.dump_outputs, DUMP_BUDGET // world)
     split = launch_split(run, sampled, per_launch) if per_launch else None
     launches_timed = len(run.launches) - run.n_warm
     errors = eng.errors()
@@ -1303,7 +1352,7 @@ def main(argv=None):
     # the same streams with aligned GOPs, timed window P pictures only (the
     # round-2 headline's mix), beside the configs[3] mix -- not instead
     p_only = None
-    if staggered:
+    if staggered and a.full:
         # pictures P+W .. P+W+kp-1: no IDR (P = steps per launch)
         kp = max(P, min(a.steps, run.N - P - a.warmup) // P * P)
         run.set_plan(a.warmup, kp, [P] * S)

@@ -4,6 +4,10 @@ r03 #8).  Every stream must see its pictures in cyclic decode order, the
 pre-roll must bring stream s to its phase, a two-step launch must pair
 pictures (k, k+1) of every stream with k even, and the descriptor table must
 hold exactly the plan's pictures."""
+import json
+
+import numpy as np
+
 import bench
 from broadway_amd import gen
 from broadway_amd.engine import Capture
@@ -145,6 +149,59 @@ def test_device_run_pipe3_idr_last():
                 slots = [run.slot_of[st[s]][s] for st in launch]
                 assert len(set(slots)) == len(slots)
         run.free()
+
+
+def _line(capsys, argv):
+    bench.main(argv)
+    return json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+
+
+def test_plain_run_is_the_headline_run_alone(capsys, tmp_path):
+    """bench.py without --full (dry engine): pre-roll, warmup and the timed
+    steps, nothing after them; --steps sets the timed steps whatever their
+    number; --full adds the P-only window (and, on a GPU, the other legs)."""
+    argv = ["--gpus", "1", "--dry-run", "--streams", "2", "--config", "2", "--gen", "w_mbs=6,h_mbs=4,crop_bottom=0"]
+    line = _line(capsys, argv + ["--warmup", "1", "--steps", "3"])
+    assert line["dry_run"]["launches"] == 30 + 1 + 1 and line["p_only"] is None
+    assert line["steps"] == 3 and line["kernels"]["k_wgpp"]["trace_steps"] == [3]
+    assert line["ms_per_step"] > 0 and line["unit"] == "frames/s" and line["higher_is_better"] is True
+    full = _line(capsys, argv + ["--warmup", "1", "--steps", "3", "--full"])
+    assert full["dry_run"]["launches"] == 30 + 1 + 1 + 3 + 1 + 1 and full["p_only"]["i_pictures_timed"] == 0
+    assert full.keys() == line.keys()
+    line = _line(capsys, argv + ["--warmup", "2", "--steps", "200", "--dump-outputs", str(tmp_path)])
+    assert sum(line["kernels"]["k_wgpp"]["trace_steps"]) == 200 and line["config"]["frames_per_stream_timed"] == 200
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["stream100.npy", "stream100_sums.npy",
+                                                          "stream101.npy", "stream101_sums.npy"]
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: the last timed step's picture of every stream, whole
+    when it fits the budget, else at one fixed sample of offsets; float32
+    values, float64 sums over every byte; the same files from run to run."""
+    caps = _caps()
+    S, N, W, K = len(caps), 12, 3, 9
+    ph = bench.gop_phases(S, N, 3, warmup=W)
+    run = bench.DeviceRun(None, caps, W, K, 3, dry=True, phases=ph)
+    size = 13 * 7 * 384 + 10                                 # not a multiple of 64: a short last sum
+    pic = lambda s, slot: np.random.default_rng(1000 * s + slot).integers(0, 256, size, dtype=np.uint8)  # noqa: E731
+    run.eng.read = pic
+    last = [(s, (W + K - 1 + ph[s]) % N) for s in range(S)]
+    a, b, c = tmp_path / "a", tmp_path / "b", tmp_path / "c"
+    assert bench.dump_outputs(run, [7, 8, 9], str(a), budget=S * 4 * 1000) == last
+    assert bench.dump_outputs(run, [7, 8, 9], str(b), budget=S * 4 * 1000) == last
+    bench.dump_outputs(run, [7, 8, 9], str(c), budget=S * 4 * size)
+    idx = np.sort(np.random.default_rng(0).choice(size, size=1000, replace=False))
+    for s, k in last:
+        want = pic(s, int(run.slot_of[k][s]))
+        got = np.load(a / f"stream{7 + s}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, want[idx])
+        assert np.array_equal(got, np.load(b / f"stream{7 + s}.npy"))
+        assert np.array_equal(np.load(c / f"stream{7 + s}.npy"), want)
+        sums = np.load(a / f"stream{7 + s}_sums.npy")
+        assert sums.dtype == np.float64 and len(sums) == (size + 63) // 64 and sums.sum() == want.sum(dtype=np.int64)
+        assert sums[-1] == want[-10:].sum()
+    assert sum(p.stat().st_size for p in a.iterdir()) < S * (4 * 1000 + 8 * ((size + 63) // 64) + 2 * 128) + 1
+    run.free()
 
 
 def test_latency_floors_from_committed_profiles():

@@ -72,7 +72,7 @@ def _bench_worker(rank, world, port, q, one_device=False):
     import bench
     out = io.StringIO()
     with contextlib.redirect_stdout(out):
-        bench.main(["--gpus", str(world), "--dry-run", "--streams", "2", "--warmup", "1", "--steps", "3",
+        bench.main(["--gpus", str(world), "--dry-run", "--full", "--streams", "2", "--warmup", "1", "--steps", "3",
                     "--config", "2", "--gen", "w_mbs=6,h_mbs=4,crop_bottom=0"])
     q.put((rank, out.getvalue()))
 

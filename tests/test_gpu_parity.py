@@ -361,6 +361,44 @@ def test_engine_pipelined_steps_vs_oracle(wh, pipe, mode, monkeypatch):
         run.free()
 
 
+@pytest.mark.parametrize("budget", [1 << 30, 3 * 4 * 5000])
+def test_bench_dump_outputs_vs_oracle(budget, tmp_path):
+    """bench.py --dump-outputs after the timed run (GOP phases, three steps
+    per launch): every stream's file holds the picture its last timed step
+    reconstructed -- whole (float32) when the budget allows, else at the fixed
+    sample of byte offsets -- and the 64-byte sums cover the whole picture;
+    both against the oracle's decode of the stream."""
+    import numpy as np
+    import torch
+    import bench
+    S, N, W, K = 3, 12, 3, 9
+    streams = [gen.generate(2, 90 + i, nframes=N, w_mbs=13, h_mbs=7, crop_bottom=0, slices=2, gop=N)
+               for i in range(S)]
+    caps = [Capture(s) for s in streams]
+    refs = [O.decode(s)[0] for s in streams]
+    phases = bench.gop_phases(S, N, 3, warmup=W)
+    run = bench.DeviceRun(_lib.mi(), caps, W, K, 3, phases=phases)
+    try:
+        assert run.P == 3
+        bench.timed_run(run, None, torch, torch.cuda.synchronize)
+        seeds = [90, 91, 92]
+        wrote = bench.dump_outputs(run, seeds, str(tmp_path), budget)
+        assert wrote == [(s, (W + K - 1 + phases[s]) % N) for s in range(S)]
+        size = 13 * 7 * 384
+        idx = None if budget > 4 * S * size else \
+            np.sort(np.random.default_rng(0).choice(size, size=5000, replace=False))
+        for s, k in wrote:
+            want = np.frombuffer(refs[s][k], dtype=np.uint8)
+            got = np.load(tmp_path / f"stream{seeds[s]}.npy")
+            assert got.dtype == np.float32 and np.array_equal(got, want if idx is None else want[idx])
+            sums = np.load(tmp_path / f"stream{seeds[s]}_sums.npy")
+            assert sums.dtype == np.float64
+            assert np.array_equal(sums, want.reshape(-1, 64).sum(axis=1, dtype=np.float64))
+        assert run.eng.errors() == 0
+    finally:
+        run.free()
+
+
 @pytest.mark.parametrize("share", [0, 4])
 def test_swdec_concurrent_instances_vs_reference(share, monkeypatch):
     """One H264SwDec instance per thread, decoding concurrently (the

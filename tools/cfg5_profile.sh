@@ -7,8 +7,8 @@ TAG=${1:-cfg5}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-B4="bench.py --config 4 --streams 1 --steps 20 --warmup 4 --no-cpu-baseline --no-e2e --no-rgba --no-legs"
-B2="bench.py --config 1 --streams 4 --steps 20 --warmup 4 --no-cpu-baseline --no-e2e --no-rgba --no-legs"
+B4="bench.py --full --config 4 --streams 1 --steps 20 --warmup 4 --no-cpu-baseline --no-e2e --no-rgba --no-legs"
+B2="bench.py --full --config 1 --streams 4 --steps 20 --warmup 4 --no-cpu-baseline --no-e2e --no-rgba --no-legs"
 timeout -k 10 300 python3 $B4 > $OUT/bench_cfg5.json 2> $OUT/b5.err || { tail -20 $OUT/b5.err; exit 1; }
 timeout -k 10 300 python3 $B2 > $OUT/bench_cfg2.json 2> $OUT/b2.err || { tail -20 $OUT/b2.err; exit 1; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof5 -o bench -- python3 $B4 > /dev/null 2> $OUT/prof5.err || { tail -20 $OUT/prof5.err; exit 1; }

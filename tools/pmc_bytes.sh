@@ -24,6 +24,6 @@ for p in rd src wr; do
 done
 for p in rd src wr; do
   case $p in rd) C=$P_RD;; src) C=$P_SRC;; wr) C=$P_WR;; esac
-  timeout -s KILL 400 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/bytes_bench_$p -o bench -- python3 bench.py --no-cpu-baseline --no-verify --no-e2e --no-legs --no-rgba > /dev/null 2> $OUT/bytes_bench_$p.err || { tail -20 $OUT/bytes_bench_$p.err; exit 1; }
+  timeout -s KILL 400 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/bytes_bench_$p -o bench -- python3 bench.py --full --no-cpu-baseline --no-verify --no-e2e --no-legs --no-rgba > /dev/null 2> $OUT/bytes_bench_$p.err || { tail -20 $OUT/bytes_bench_$p.err; exit 1; }
   echo "bench pass $p done"
 done
