@@ -7,9 +7,13 @@
 //   d.onPictureDecoded = function (buffer, width, height, infos) { ... };
 //   d.decode(nalU8Array, parInfo);          // synchronous, one NAL per call
 //
-// buffer: MB-aligned planar I420 (width*height*3/2 bytes, no cropping), or
+// buffer: MB-aligned planar I420 (width*height*3/2 bytes, not cropped), or
 //         with {rgb: true} RGBA (width*height*4 bytes) converted on the GPU
 //         with the per-pixel arithmetic of DecoderPost.js's yuv2rgbcalc.
+//         With {crop: true} (combinable with rgb) the picture is cropped to
+//         the SPS crop window on the GPU, and width / height are
+//         cropOutWidth / cropOutHeight (what Player/YUVCanvas.js does with
+//         croppingParams, here before the picture leaves the device).
 // infos:  parInfo objects passed since the last picture, stamped with
 //         startDecoding / finishDecoding (DecoderPost.js:77-103, :277-281).
 // Not supported (outside the reconstruction path): sliceMode.
@@ -30,7 +34,7 @@ function Decoder(parOptions) {
   }
   this.infoAr = [];
   this.onPictureDecoded = function (buffer, width, height, infos) {};
-  this._h = native.create(0, this.options.rgb ? 1 : 0);
+  this._h = native.create(0, this.options.rgb ? 1 : 0, this.options.crop ? 1 : 0);
   var self = this;
   this._onPic = function (buffer, width, height) {
     var infos;

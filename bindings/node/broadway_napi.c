@@ -5,9 +5,12 @@
  *
  * Native surface (one H264SwDec instance per JS Decoder, unlike the single
  * global instance of the wasm module, Decoder.c:21-25):
- *   create(noOutputReordering, rgb)       -> handle (external); rgb != 0:
+ *   create(noOutputReordering, rgb, crop) -> handle (external); rgb != 0:
  *       pictures arrive as RGBA (width*height*4 bytes), converted on the GPU
- *       (H264SwDecNextPictureRGBA; DecoderPost.js rgb option :82-97)
+ *       (H264SwDecNextPictureRGBA; DecoderPost.js rgb option :82-97);
+ *       crop != 0: pictures arrive cropped to the SPS crop window on the GPU
+ *       (H264SwDecNextPictureCropped), I420 or with rgb RGBA, and onPicture
+ *       receives cropOutWidth, cropOutHeight
  *   decode(handle, Uint8Array, onPicture) -> undefined
  *       runs the broadwayDecode loop of Decoder.c:44-162 over the bytes:
  *       HDRS_RDY -> GetInfo; PIC_RDY -> drain NextPicture and call
@@ -28,8 +31,8 @@ typedef struct {
     H264SwDecInst inst;
     H264SwDecInfo info;
     u32 pic_decode;
-    u32 rgb;
-    /* rgb mode: the RGBA Buffer the last drain iteration allocated but found
+    u32 rgb, crop;
+    /* rgb / crop mode: the RGBA Buffer the last drain iteration allocated but found
      * no picture for, kept for the next picture instead of thrown away */
     napi_ref spare;
     size_t spare_len;
@@ -53,12 +56,13 @@ static void finalize_dec(napi_env env, void *data, void *hint)
 
 static napi_value js_create(napi_env env, napi_callback_info cbi)
 {
-    size_t argc = 2;
-    napi_value argv[2], out;
+    size_t argc = 3;
+    napi_value argv[3], out;
     CHECK(env, napi_get_cb_info(env, cbi, &argc, argv, NULL, NULL));
-    uint32_t no_reorder = 0, rgb = 0;
+    uint32_t no_reorder = 0, rgb = 0, crop = 0;
     if (argc >= 1) napi_get_value_uint32(env, argv[0], &no_reorder);
     if (argc >= 2) napi_get_value_uint32(env, argv[1], &rgb);
+    if (argc >= 3) napi_get_value_uint32(env, argv[2], &crop);
     JsDec *d = (JsDec *)calloc(1, sizeof(JsDec));
     if (!d) { napi_throw_error(env, NULL, "out of memory"); return NULL; }
     if (H264SwDecInit(&d->inst, no_reorder) != H264SWDEC_OK) {
@@ -68,6 +72,7 @@ static napi_value js_create(napi_env env, napi_callback_info cbi)
     }
     d->pic_decode = 1;
     d->rgb = rgb != 0;
+    d->crop = crop != 0;
     CHECK(env, napi_create_external(env, d, finalize_dec, NULL, &out));
     return out;
 }
@@ -123,27 +128,39 @@ static napi_value js_decode(napi_env env, napi_callback_info cbi)
             in.dataLen = 0;                      /* Decoder.c:130 */
             d->pic_decode++;
             for (;;) {
-                const size_t px = (size_t)d->info.picWidth * d->info.picHeight;
+                u32 ow = d->info.picWidth, oh = d->info.picHeight;
+                if (d->crop && d->info.croppingFlag) {
+                    ow = d->info.cropParams.cropOutWidth;
+                    oh = d->info.cropParams.cropOutHeight;
+                }
+                const size_t px = (size_t)ow * oh, nb = d->rgb ? px * 4 : px * 3 / 2;
                 napi_value view, args[3], res;
-                if (d->rgb) {
-                    /* RGBA straight into a new JS Buffer (DecoderPost.js hands
+                if (d->rgb || d->crop) {
+                    /* RGBA / the cropped picture straight into a new JS Buffer (DecoderPost.js hands
                      * onPictureDecoded a fresh copy, :89-95) */
                     void *dst = NULL;
                     napi_status st = napi_generic_failure;
                     if (d->spare) {
-                        if (d->spare_len == px * 4 && napi_get_reference_value(env, d->spare, &view) == napi_ok && view)
+                        if (d->spare_len == nb && napi_get_reference_value(env, d->spare, &view) == napi_ok && view)
                             st = napi_get_buffer_info(env, view, &dst, NULL);
                         napi_delete_reference(env, d->spare);
                         d->spare = NULL;
                     }
-                    if (st != napi_ok && napi_create_buffer(env, px * 4, &dst, &view) != napi_ok) {
+                    if (st != napi_ok && napi_create_buffer(env, nb, &dst, &view) != napi_ok) {
                         free(buf);
                         napi_throw_error(env, NULL, "cannot allocate picture buffer");
                         return NULL;
                     }
-                    if (H264SwDecNextPictureRGBA(d->inst, &pic, 0, (u8 *)dst) != H264SWDEC_PIC_RDY) {
+                    const H264SwDecRet nr = d->crop ? H264SwDecNextPictureCropped(d->inst, &pic, 0, (u8 *)dst, d->rgb)
+                                                    : H264SwDecNextPictureRGBA(d->inst, &pic, 0, (u8 *)dst);
+                    if (d->crop && nr == H264SWDEC_PARAM_ERR) {
+                        free(buf);
+                        napi_throw_error(env, NULL, "crop: the backend cannot crop (there is no host fallback)");
+                        return NULL;
+                    }
+                    if (nr != H264SWDEC_PIC_RDY) {
                         /* no picture: keep the Buffer for the next one */
-                        if (napi_create_reference(env, view, 1, &d->spare) == napi_ok) d->spare_len = px * 4;
+                        if (napi_create_reference(env, view, 1, &d->spare) == napi_ok) d->spare_len = nb;
                         else d->spare = NULL;
                         break;
                     }
@@ -158,8 +175,8 @@ static napi_value js_decode(napi_env env, napi_callback_info cbi)
                     }
                 }
                 args[0] = view;
-                napi_create_uint32(env, d->info.picWidth, &args[1]);
-                napi_create_uint32(env, d->info.picHeight, &args[2]);
+                napi_create_uint32(env, ow, &args[1]);
+                napi_create_uint32(env, oh, &args[2]);
                 if (napi_call_function(env, undef, argv[2], 3, args, &res) != napi_ok) {
                     free(buf);
                     return NULL;                 /* JS exception propagates */

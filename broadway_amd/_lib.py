@@ -74,7 +74,7 @@ class GenParams(C.Structure):
         "poc_type", "coef_pct", "level_tail_pct", "mv_jitter", "offpic_pct",
         "log2_max_frame_num", "poc_swap",
         "err_range_pct", "drop_slice_pct", "trunc_slice_pct", "drop_pic_pct", "gaps_allowed",
-        "nonref_pct", "ref_mod_pct", "mmco_pct", "lt_idr_pct")] + [("seed", C.c_uint64)]
+        "nonref_pct", "ref_mod_pct", "mmco_pct", "lt_idr_pct", "crop_left", "crop_top")] + [("seed", C.c_uint64)]
 
 
 HEADERS_CB = C.CFUNCTYPE(None, C.c_void_p)
@@ -176,6 +176,13 @@ def mi() -> C.CDLL:
         L.h264mi_yuv2rgba_device_pitch.restype = i32
     L.H264SwDecNextPictureRGBA.argtypes = [vp, C.POINTER(H264SwDecPicture), u32, vp]
     L.H264SwDecNextPictureRGBA.restype = i32
+    if hasattr(L, "h264mi_crop_device_pitch"):          # (optional: a library without them still loads)
+        L.H264SwDecNextPictureCropped.argtypes = [vp, C.POINTER(H264SwDecPicture), u32, vp, u32]
+        L.H264SwDecNextPictureCropped.restype = i32
+        L.h264mi_crop_device_pitch.argtypes = [vp, vp] + [i32] * 9 + [sz, sz, vp]
+        L.h264mi_crop_device_pitch.restype = i32
+        L.h264mi_engine_read_crop.argtypes = [vp] + [i32] * 7 + [vp]
+        L.h264mi_engine_read_crop.restype = i32
     L.h264mi_engine_sync.argtypes = [vp]
     L.h264mi_engine_sync.restype = i32
     L.h264mi_engine_kernel.argtypes = [vp]

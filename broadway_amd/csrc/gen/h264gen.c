@@ -267,11 +267,11 @@ static void write_sps(Gen *g)
     bw_ue(&bw, (uint32_t)(p->h_mbs - 1));
     bw_put(&bw, 1, 1);             /* frame_mbs_only_flag */
     bw_put(&bw, 1, 1);             /* direct_8x8_inference_flag */
-    int crop = p->crop_right || p->crop_bottom;
+    int crop = p->crop_left || p->crop_right || p->crop_top || p->crop_bottom;
     bw_put(&bw, (uint32_t)crop, 1);
     if (crop) {
-        bw_ue(&bw, 0); bw_ue(&bw, (uint32_t)(p->crop_right / 2));
-        bw_ue(&bw, 0); bw_ue(&bw, (uint32_t)(p->crop_bottom / 2));
+        bw_ue(&bw, (uint32_t)(p->crop_left / 2)); bw_ue(&bw, (uint32_t)(p->crop_right / 2));
+        bw_ue(&bw, (uint32_t)(p->crop_top / 2)); bw_ue(&bw, (uint32_t)(p->crop_bottom / 2));
     }
     bw_put(&bw, 0, 1);             /* vui_parameters_present_flag */
     bw_trailing(&bw);

@@ -53,6 +53,9 @@ typedef struct GenParams {
     int ref_mod_pct;               /* per P slice: ref_pic_list_modification commands */
     int mmco_pct;                  /* per non-IDR reference picture: adaptive marking (MMCO 1-4, 6; 5 with POC type 2) */
     int lt_idr_pct;                /* per IDR: long_term_reference_flag */
+    /* SPS frame_crop_left_offset / frame_crop_top_offset, luma pixels (even);
+     * both 0 leaves the stream byte-identical */
+    int crop_left, crop_top;
     uint64_t seed;
 } GenParams;
 

@@ -27,13 +27,11 @@ __device__ __forceinline__ uint32_t rgba_px(int y, int cr, int cg, int cb)
     return 0xFF000000u | ((uint32_t)b << 16) | ((uint32_t)g << 8) | (uint32_t)r;
 }
 
-// one 4-column group (2 chroma samples) of two rows
-__device__ __forceinline__ void rgba_group(const uint8_t *Y, const uint8_t *U, const uint8_t *V, uint8_t *O,
-                                           int width, size_t yo, size_t co)
+// the pixels of one 4-column group of two rows: y0 / y1 = the rows' four luma
+// bytes, u2 / v2 = the group's two chroma samples (bytes 0 and 1)
+__device__ __forceinline__ void rgba_group_px(uint32_t y0, uint32_t y1, uint32_t u2, uint32_t v2, uint32_t (&o0)[4],
+                                              uint32_t (&o1)[4])
 {
-    const uint32_t y0 = *(const uint32_t *)(Y + yo), y1 = *(const uint32_t *)(Y + yo + width);
-    const uint32_t u2 = *(const uint16_t *)(U + co), v2 = *(const uint16_t *)(V + co);
-    uint32_t o0[4], o1[4];
 #pragma unroll
     for (int k = 0; k < 2; k++) {
         const int u = (int)((u2 >> (8 * k)) & 255) - 128, v = (int)((v2 >> (8 * k)) & 255) - 128;
@@ -43,6 +41,16 @@ __device__ __forceinline__ void rgba_group(const uint8_t *Y, const uint8_t *U, c
         o1[2 * k] = rgba_px((int)((y1 >> (16 * k)) & 255), cr, cg, cb);
         o1[2 * k + 1] = rgba_px((int)((y1 >> (16 * k + 8)) & 255), cr, cg, cb);
     }
+}
+
+// one 4-column group (2 chroma samples) of two rows
+__device__ __forceinline__ void rgba_group(const uint8_t *Y, const uint8_t *U, const uint8_t *V, uint8_t *O,
+                                           int width, size_t yo, size_t co)
+{
+    const uint32_t y0 = *(const uint32_t *)(Y + yo), y1 = *(const uint32_t *)(Y + yo + width);
+    const uint32_t u2 = *(const uint16_t *)(U + co), v2 = *(const uint16_t *)(V + co);
+    uint32_t o0[4], o1[4];
+    rgba_group_px(y0, y1, u2, v2, o0, o1);
     // streaming output (nothing here reads it back): non-temporal stores
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const u32x4 w0 = {o0[0], o0[1], o0[2], o0[3]}, w1 = {o1[0], o1[1], o1[2], o1[3]};

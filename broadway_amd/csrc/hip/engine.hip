@@ -4,6 +4,7 @@
 // one launch reconstructs one picture from each stream of the batch).
 #include "recon_kernels.hip"
 #include "color.hip"
+#include "crop.hip"
 #include "conceal.hip"
 #include <hip/hip_ext.h>
 
@@ -83,7 +84,7 @@ struct h264mi_engine {
     hipEvent_t *tev;
     int tev_cap, tev_n;
     int tev_stride, tev_seq;  // record every tev_stride-th launch (h264mi_engine_set_timing_stride)
-    uint8_t *d_rgba;          // h264mi_engine_read_rgba staging (w*h*4 B, allocated on first use)
+    uint8_t *d_rgba;          // h264mi_engine_read_rgba / _read_crop staging (w*h*4 B, allocated on first use)
     int steps;                // pictures per stream per launch (h264mi_engine_set_steps)
     unsigned long long *d_prog;   // per picture row of a launch, per row wave: {MBs stored, epoch} (frame-pipelined launches)
     unsigned *d_done;             // per picture row of a launch: epoch once the row is stored
@@ -973,6 +974,60 @@ extern "C" int h264mi_engine_read_rgba(h264mi_engine *e, int stream, int slot, u
     if (h264mi_yuv2rgba_device_pitch(e->d_frames + e->frame_bytes * ((size_t)stream * e->nslots + slot), e->d_rgba,
                                      e->w * 16, e->h * 16, e->cpitch, 1, 0, 0, e->st))
         return -1;
+    HIPCHECK(hipMemcpyAsync(dst, e->d_rgba, bytes, hipMemcpyDeviceToHost, e->st));
+    HIPCHECK(hipStreamSynchronize(e->st));
+    return 0;
+}
+
+// The crop window (x, y, cw, ch; all even, inside the picture) of `npics`
+// pictures of width x height pixels, chroma rows cpitch bytes apart, at
+// d_in + k * in_stride -> packed at d_out + k * out_stride: I420 in the layout
+// of the reference testbench's CropPicture, or RGBA (crop.hip); device
+// pointers, asynchronous on `stream`.  RGBA output is 8-byte aligned.
+// -1 (nothing launched) on a bad argument.
+extern "C" int h264mi_crop_device_pitch(const void *d_in, void *d_out, int width, int height, int cpitch, int x, int y,
+                                        int cw, int ch, int rgba, int npics, size_t in_stride, size_t out_stride,
+                                        void *stream)
+{
+    if (!d_in || !d_out || width <= 0 || height <= 0 || ((width | height) & 1) || npics < 1 || cpitch < width / 2 ||
+        x < 0 || y < 0 || cw <= 0 || ch <= 0 || ((x | y | cw | ch) & 1) || cw > width - x || ch > height - y)
+        return -1;
+    const uint8_t *in = (const uint8_t *)d_in;
+    uint8_t *out = (uint8_t *)d_out;
+    if (rgba) {
+        const size_t al = (size_t)(uintptr_t)out | (npics > 1 ? out_stride : 0);
+        if (al & 7) return -1;
+        const int nblk = ((ch >> 1) * ((cw + 3) >> 2) + 127) >> 7;
+        if (!(cw & 3) && !(al & 15))
+            hipLaunchKernelGGL(k_crop_rgba<true>, dim3(nblk, npics), dim3(64), 0, (hipStream_t)stream, in, out, width,
+                               height, cpitch, x, y, cw, ch, in_stride, out_stride);
+        else
+            hipLaunchKernelGGL(k_crop_rgba<false>, dim3(nblk, npics), dim3(64), 0, (hipStream_t)stream, in, out, width,
+                               height, cpitch, x, y, cw, ch, in_stride, out_stride);
+    } else {
+        // the most chunks the three planes can cover, whatever the output's alignment
+        const int ny = cw * ch, nc = (cw >> 1) * (ch >> 1);
+        const int chunks = ((ny + 30) >> 4) + 2 * ((nc + 30) >> 4);
+        hipLaunchKernelGGL(k_crop_i420, dim3((chunks + 127) >> 7, npics), dim3(64), 0, (hipStream_t)stream, in, out,
+                           width, height, cpitch, x, y, cw, ch, in_stride, out_stride);
+    }
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// D2H of the crop window of a slot, packed I420 or RGBA (h264mi_crop_device_pitch
+// into a staging buffer, one contiguous copy); syncs the engine first
+extern "C" int h264mi_engine_read_crop(h264mi_engine *e, int stream, int slot, int x, int y, int cw, int ch, int rgba,
+                                       uint8_t *dst)
+{
+    if (!e || !dst || stream < 0 || stream >= e->nstreams || slot < 0 || slot >= e->nslots) return -1;
+    const int width = e->w * 16, height = e->h * 16;
+    if (x < 0 || y < 0 || cw <= 0 || ch <= 0 || ((x | y | cw | ch) & 1) || cw > width - x || ch > height - y) return -1;
+    if (h264mi_engine_sync(e)) return -1;
+    const uint8_t *src = e->d_frames + e->frame_bytes * ((size_t)stream * e->nslots + slot);
+    const size_t bytes = rgba ? (size_t)cw * ch * 4 : (size_t)cw * ch * 3 / 2;
+    if (!e->d_rgba) HIPCHECK(hipMalloc(&e->d_rgba, (size_t)e->nmbs * 256 * 4));
+    if (h264mi_crop_device_pitch(src, e->d_rgba, width, height, e->cpitch, x, y, cw, ch, rgba, 1, 0, 0, e->st)) return -1;
     HIPCHECK(hipMemcpyAsync(dst, e->d_rgba, bytes, hipMemcpyDeviceToHost, e->st));
     HIPCHECK(hipStreamSynchronize(e->st));
     return 0;

@@ -229,6 +229,28 @@ H264SwDecRet H264SwDecNextPictureRGBA(H264SwDecInst decInst, H264SwDecPicture *p
     return H264SWDEC_PIC_RDY;
 }
 
+/* NextPicture with the picture cropped to the active SPS's crop window on
+ * the GPU (DecTestBench -C, CropPicture :588-666): dst receives cropOutWidth *
+ * cropOutHeight * 3 / 2 bytes of I420, or * 4 bytes of RGBA with rgba != 0
+ * (the whole picture when croppingFlag == 0), and pOutputPicture points to
+ * it.  A backend without read_crop: H264SWDEC_PARAM_ERR, no host fallback. */
+H264SwDecRet H264SwDecNextPictureCropped(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer, u8 *dst,
+                                         u32 rgba)
+{
+    if (decInst == NULL || pOutput == NULL || dst == NULL) return H264SWDEC_PARAM_ERR;
+    DecContainer *c = (DecContainer *)decInst;
+    if (!c->dec.be.read_crop) return H264SWDEC_PARAM_ERR;
+    if (flushBuffer) h264dec_flush(&c->dec);
+    uint32_t id, idr, em;
+    const uint8_t *pic = h264dec_next_output_crop(&c->dec, &id, &idr, &em, dst, rgba != 0);
+    if (!pic) return H264SWDEC_OK;
+    pOutput->pOutputPicture = (u32 *)(void *)pic;
+    pOutput->picId = id;
+    pOutput->isIdrPicture = idr;
+    pOutput->nbrOfErrMBs = em;
+    return H264SWDEC_PIC_RDY;
+}
+
 H264SwDecRet H264SwDecGetTiming(H264SwDecInst decInst, double *parse_s, double *submit_s, double *wait_s,
                                 double *copy_s, u32 *pictures)
 {

@@ -398,8 +398,10 @@ static int finish_picture(H264Dec *d, int concealed_mbs)
     const Sps *sps = &d->sps[d->active_sps];
     const double t0 = h264dec_now();
     int rc = d->be.decode(d->be.ctx, &d->pb, d->cur_slot);
-    /* the picture's output copy starts now, behind its reconstruction */
-    if (!rc && d->be.prefetch && d->out_frames)
+    /* the picture's output copy starts now, behind its reconstruction --
+     * unless the caller takes its pictures cropped (out_cropped): the
+     * MB-aligned copy would cross PCIe for nothing */
+    if (!rc && d->be.prefetch && d->out_frames && !d->out_cropped)
         rc = d->be.prefetch(d->be.ctx, d->cur_slot, d->out_frames + d->frame_bytes * (size_t)d->cur_slot);
     d->t_submit += h264dec_now() - t0;
     if (rc) return DEC_FAIL(DEC_ERROR);
@@ -603,13 +605,33 @@ const uint8_t *h264dec_next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_id
 
 /* rgba != NULL: the picture as RGBA (w*h*4 bytes) into rgba, converted by
  * the backend (returns rgba) */
+static const uint8_t *next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs, uint8_t *rgba,
+                                  uint8_t *crop, int crop_rgba);
+
 const uint8_t *h264dec_next_output_rgba(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
                                         uint8_t *rgba)
 {
+    return next_output(d, pic_id, is_idr, err_mbs, rgba, NULL, 0);
+}
+
+const uint8_t *h264dec_next_output_crop(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
+                                        uint8_t *dst, int rgba)
+{
+    if (!dst) return NULL;
+    return next_output(d, pic_id, is_idr, err_mbs, NULL, dst, rgba);
+}
+
+/* crop != NULL: the active SPS's crop window of the picture (the whole
+ * picture without one) into crop, as I420 or (crop_rgba) RGBA */
+static const uint8_t *next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs, uint8_t *rgba,
+                                  uint8_t *crop, int crop_rgba)
+{
     if (rgba && !d->be.read_rgba) return NULL;
+    const Sps *sps = crop ? h264dec_active_sps(d) : NULL;
+    if (crop && (!d->be.read_crop || !sps)) return NULL;
     const DpbOut *o = dpb_next_output(&d->dpb);
     if (!o) return NULL;
-    uint8_t *dst = rgba ? rgba : d->out_frames + d->frame_bytes * (size_t)o->slot;
+    uint8_t *dst = crop ? crop : rgba ? rgba : d->out_frames + d->frame_bytes * (size_t)o->slot;
     /* rather than wait for the GPU, parse the next picture's slices that
      * spec_launch_ahead queued (the buffer already holds them); the core
      * stays busy and warm, and the decode call that follows takes them */
@@ -621,10 +643,19 @@ const uint8_t *h264dec_next_output_rgba(H264Dec *d, uint32_t *pic_id, uint32_t *
     const double t0 = h264dec_now();
     if (d->be.sync && d->be.sync(d->be.ctx)) return NULL;
     const double t1 = h264dec_now();
-    const int rr = rgba ? d->be.read_rgba(d->be.ctx, o->slot, dst) : d->be.read(d->be.ctx, o->slot, dst);
+    int rr;
+    if (crop) {
+        const int cl = sps->crop ? 2 * sps->crop_l : 0, ct = sps->crop ? 2 * sps->crop_t : 0;
+        const int cr = sps->crop ? 2 * sps->crop_r : 0, cb = sps->crop ? 2 * sps->crop_b : 0;
+        rr = d->be.read_crop(d->be.ctx, o->slot, cl, ct, 16 * sps->w_mbs - cl - cr, 16 * sps->h_mbs - ct - cb,
+                             crop_rgba, dst);
+    } else {
+        rr = rgba ? d->be.read_rgba(d->be.ctx, o->slot, dst) : d->be.read(d->be.ctx, o->slot, dst);
+    }
     d->t_wait += t1 - t0;
     d->t_copy += h264dec_now() - t1;
     d->n_output++;
+    d->out_cropped = crop != NULL;
     if (rr < 0) return NULL;
     if (pic_id) *pic_id = (uint32_t)o->pic_id;
     if (is_idr) *is_idr = (uint32_t)o->is_idr;

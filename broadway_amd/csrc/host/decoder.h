@@ -42,6 +42,10 @@ typedef struct H264Backend {
     /* copy slot converted to RGBA (w*16 * h*16 * 4 bytes, DecoderPost.js
      * rgb output; same returns); NULL when the backend has no conversion */
     int  (*read_rgba)(void *ctx, int slot, uint8_t *dst);
+    /* copy the window (x, y, cw, ch; luma pixels, even) of slot, packed, as
+     * I420 (cw * ch * 3 / 2 bytes) or with rgba != 0 as RGBA (cw * ch * 4
+     * bytes); same returns; NULL when the backend cannot crop */
+    int  (*read_crop)(void *ctx, int slot, int x, int y, int cw, int ch, int rgba, uint8_t *dst);
     /* optional: host memory for the output frames (pinned by the HIP
      * backend, so each picture's D2H copy runs at DMA speed); NULL: malloc */
     void *(*host_alloc)(void *ctx, size_t bytes);
@@ -113,6 +117,11 @@ typedef struct H264Dec {
     uint8_t *out_frames;
     size_t   frame_bytes;
     int      nslots;
+    /* the last picture left through h264dec_next_output_crop: the next
+     * pictures' uncropped copies into out_frames are not started (nobody
+     * reads them); a plain next_output clears it and reads synchronously
+     * until the copies are back */
+    int      out_cropped;
     /* statistics */
     uint64_t pics_decoded, alg_ref_bytes, coded_blocks;
     /* speculative parallel slice parsing (specparse.c); NULL: off */
@@ -138,6 +147,10 @@ const uint8_t *h264dec_next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_id
                                    uint32_t *err_mbs);
 const uint8_t *h264dec_next_output_rgba(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
                                         uint8_t *rgba);
+/* the same, the picture cropped to the active SPS's crop window (the whole
+ * picture without one) into dst by the backend's read_crop (returns dst) */
+const uint8_t *h264dec_next_output_crop(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
+                                        uint8_t *dst, int rgba);
 int  h264dec_valid_param_sets(const H264Dec *d);
 /* conceal the current picture's missing MBs (conceal.c); returns their
  * number or -1 */

@@ -486,6 +486,42 @@ static int hb_read_rgba(void *vctx, int slot, uint8_t *dst)
     return slot_flagged(c, slot, false);
 }
 
+// The crop entry points are weak here: the CPU stand-in of the engine
+// (oracle/null_device.cpp) has none, and a backend built against it leaves read_crop NULL
+// (H264SwDecNextPictureCropped then fails; there is no host crop).
+extern "C" int h264mi_engine_read_crop(h264mi_engine *e, int stream, int slot, int x, int y, int cw, int ch, int rgba,
+                                       uint8_t *dst) __attribute__((weak));
+extern "C" int h264mi_crop_device_pitch(const void *d_in, void *d_out, int width, int height, int cpitch, int x, int y,
+                                        int cw, int ch, int rgba, int npics, size_t in_stride, size_t out_stride,
+                                        void *hip_stream) __attribute__((weak));
+
+static int hb_read_crop(void *vctx, int slot, int x, int y, int cw, int ch, int rgba, uint8_t *dst)
+{
+    HipBackendCtx *c = (HipBackendCtx *)vctx;
+    if (slot < 0 || slot >= c->nslots) return -1;
+    if (c->sh) {
+        h264mi_engine *e = c->e;
+        int w = 0, h = 0, ns = 0, nsl = 0, bl = 0;
+        engine_shape(e, &w, &h, &ns, &nsl, &bl);
+        if (x < 0 || y < 0 || cw <= 0 || ch <= 0 || ((x | y | cw | ch) & 1) || cw > w * 16 - x || ch > h * 16 - y)
+            return -1;
+        const size_t bytes = rgba ? (size_t)cw * ch * 4 : (size_t)cw * ch * 3 / 2;
+        // (the RGBA staging holds any crop of the picture in either form)
+        if (!c->d_rgba) HIPCHECK(hipMalloc(&c->d_rgba, (size_t)w * h * 256 * 4));
+        {
+            std::lock_guard<std::mutex> l(c->sh->mu);
+            if (h264mi_crop_device_pitch(h264mi_engine_frame_ptr(e, c->lane, slot), c->d_rgba, w * 16, h * 16,
+                                         h264mi_engine_chroma_pitch(e), x, y, cw, ch, rgba, 1, 0, 0, engine_stream(e)))
+                return -1;
+            HIPCHECK(hipMemcpyAsync(dst, c->d_rgba, bytes, hipMemcpyDeviceToHost, engine_stream(e)));
+            HIPCHECK(hipEventRecord(c->ev_last, engine_stream(e)));
+        }
+        return slot_flagged(c, slot);
+    }
+    if (h264mi_engine_read_crop(c->e, 0, slot, x, y, cw, ch, rgba, dst)) return -1;
+    return slot_flagged(c, slot, false);
+}
+
 // Pinned host blocks (decoder output frames) kept after free for the next
 // decoder instance: pinning tens of MB per instance is a large share of a
 // short stream's host time.  Exact-size reuse, at most H264MI_HOST_POOL_MB
@@ -615,6 +651,7 @@ extern "C" H264Backend h264mi_hip_backend_create(int device)
     be.decode = hb_decode;
     be.read = hb_read;
     be.read_rgba = hb_read_rgba;
+    be.read_crop = h264mi_engine_read_crop && h264mi_crop_device_pitch ? hb_read_crop : NULL;
     be.host_alloc = hb_host_alloc;
     be.host_free = hb_host_free;
     be.records_wait = hb_records_wait;

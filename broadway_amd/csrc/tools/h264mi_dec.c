@@ -4,7 +4,11 @@
  * D2H of every output picture.  Call protocol of the reference testbench
  * (Decoder/src/DecTestBench.c:230-410): decode, drain NextPicture after each
  * PIC_RDY, flush at end of stream.
- *   h264mi_dec [-R] [-Oout.yuv|-Onone] [-rN] [-T] [-SN] [-Acpus] in.h264 [in2.h264 ...]
+ *   h264mi_dec [-R] [-C] [-Oout.yuv|-Onone] [-rN] [-T] [-SN] [-Acpus] in.h264 [in2.h264 ...]
+ * -C (DecTestBench.c:137 "display cropped image"): pictures are cropped to the
+ * SPS crop window on the GPU (H264SwDecNextPictureCropped) and -O receives the
+ * cropped frames, CropPicture's layout (:588-666); a backend that cannot crop
+ * ends the run with a message and a non-zero status.
  * -rN decodes the stream N times (one instance each; HIP start-up is paid
  * once, before the timed loop); -T prints the wall time of the decode loops.
  * Several inputs: one thread per input, each with its own instances
@@ -102,7 +106,10 @@ static double other_threads_cpu(pid_t skip, int *n)
 static double g_t[4];   /* parse, submit, wait, copy (H264SwDecGetTiming), summed over instances */
 static pthread_mutex_t g_mu = PTHREAD_MUTEX_INITIALIZER;
 
-static int decode_once(const uint8_t *stream, uint32_t len, uint8_t *work, int no_reorder, FILE *fo, int *errs)
+/* -1: no decoder instance; -2: -C on a backend that cannot crop; -3: out of
+ * memory.  first: the input's first pass (prints its crop window) */
+static int decode_once(const uint8_t *stream, uint32_t len, uint8_t *work, int no_reorder, int crop, int first,
+                       FILE *fo, int *errs)
 {
     H264SwDecInst inst;
     if (H264SwDecInit(&inst, (u32)no_reorder) != H264SWDEC_OK) return -1;
@@ -115,7 +122,8 @@ static int decode_once(const uint8_t *stream, uint32_t len, uint8_t *work, int n
     in.pStream = work;
     in.dataLen = len;
     size_t size = 0;
-    int pics = 0;
+    uint8_t *cbuf = NULL;       /* -C: the cropped picture */
+    int pics = 0, nocrop = 0, nomem = 0;
     u32 pic_id = 0;
     while (in.dataLen > 0) {
         in.picId = pic_id;
@@ -123,13 +131,29 @@ static int decode_once(const uint8_t *stream, uint32_t len, uint8_t *work, int n
         if (r == H264SWDEC_HDRS_RDY_BUFF_NOT_EMPTY) {
             if (H264SwDecGetInfo(inst, &info) != H264SWDEC_OK) break;
             size = (size_t)info.picWidth * info.picHeight * 3 / 2;
+            if (crop) {
+                if (info.croppingFlag) {
+                    if (first)
+                        printf("Cropping params: (%u, %u) %ux%u\n", info.cropParams.cropLeftOffset,
+                               info.cropParams.cropTopOffset, info.cropParams.cropOutWidth,
+                               info.cropParams.cropOutHeight);
+                    size = (size_t)info.cropParams.cropOutWidth * info.cropParams.cropOutHeight * 3 / 2;
+                }
+                free(cbuf);
+                cbuf = (uint8_t *)malloc(size ? size : 1);
+                if (!cbuf) { nomem = 1; break; }
+            }
         } else if (r == H264SWDEC_PIC_RDY || r == H264SWDEC_PIC_RDY_BUFF_NOT_EMPTY) {
             pic_id++;
-            while (H264SwDecNextPicture(inst, &pic, 0) == H264SWDEC_PIC_RDY) {
+            if (crop && !cbuf) { nomem = 1; break; }
+            H264SwDecRet n;
+            while ((n = crop ? H264SwDecNextPictureCropped(inst, &pic, 0, cbuf, 0)
+                             : H264SwDecNextPicture(inst, &pic, 0)) == H264SWDEC_PIC_RDY) {
                 pics++;
                 *errs += (int)pic.nbrOfErrMBs;
                 if (fo) fwrite(pic.pOutputPicture, 1, size, fo);
             }
+            if (crop && n == H264SWDEC_PARAM_ERR) { nocrop = 1; break; }
         } else if (r < 0) {
             (*errs)++;
         }
@@ -138,7 +162,8 @@ static int decode_once(const uint8_t *stream, uint32_t len, uint8_t *work, int n
         in.dataLen -= used;
         in.pStream = out.pStrmCurrPos;
     }
-    while (H264SwDecNextPicture(inst, &pic, 1) == H264SWDEC_PIC_RDY) {
+    while (!nocrop && !nomem && (crop ? H264SwDecNextPictureCropped(inst, &pic, 1, cbuf, 0)
+                            : H264SwDecNextPicture(inst, &pic, 1)) == H264SWDEC_PIC_RDY) {
         pics++;
         *errs += (int)pic.nbrOfErrMBs;
         if (fo) fwrite(pic.pOutputPicture, 1, size, fo);
@@ -150,13 +175,14 @@ static int decode_once(const uint8_t *stream, uint32_t len, uint8_t *work, int n
         pthread_mutex_unlock(&g_mu);
     }
     H264SwDecRelease(inst);
-    return pics;
+    free(cbuf);
+    return nocrop ? -2 : nomem ? -3 : pics;
 }
 
 typedef struct Job {
     uint8_t *buf, *work;
     uint32_t len;
-    int reps, no_reorder, pics, errs, fail;
+    int reps, no_reorder, crop, pics, errs, fail;
     FILE *fo;
 } Job;
 
@@ -168,8 +194,9 @@ static void *run_job(void *arg)
     struct timespec c0, c1;
     clock_gettime(CLOCK_THREAD_CPUTIME_ID, &c0);
     for (int k = 0; k < j->reps; k++) {
-        const int n = decode_once(j->buf, j->len, j->work, j->no_reorder, k == 0 ? j->fo : NULL, &j->errs);
-        if (n < 0) { j->fail = 1; break; }
+        const int n = decode_once(j->buf, j->len, j->work, j->no_reorder, j->crop, k == 0, k == 0 ? j->fo : NULL,
+                                  &j->errs);
+        if (n < 0) { j->fail = -n; break; }
         j->pics += n;
     }
     clock_gettime(CLOCK_THREAD_CPUTIME_ID, &c1);
@@ -198,12 +225,13 @@ int main(int argc, char **argv)
 {
     const char *out = NULL;
     const char *ins[256];
-    int nin = 0, no_reorder = 0, timing = 0, reps = 1, share = 0, gate = 0;
+    int nin = 0, no_reorder = 0, timing = 0, reps = 1, share = 0, gate = 0, crop = 0;
     const char *cpus = NULL;
     for (int i = 1; i < argc; i++) {
         if (!strncmp(argv[i], "-O", 2)) out = argv[i] + 2;
         else if (!strcmp(argv[i], "-R")) no_reorder = 1;
         else if (!strcmp(argv[i], "-T")) timing = 1;
+        else if (!strcmp(argv[i], "-C")) crop = 1;
         else if (!strncmp(argv[i], "-r", 2)) reps = atoi(argv[i] + 2);
         else if (!strncmp(argv[i], "-S", 2)) share = atoi(argv[i] + 2);
         else if (!strncmp(argv[i], "-A", 2)) cpus = argv[i] + 2;
@@ -211,7 +239,7 @@ int main(int argc, char **argv)
         else if (nin < 256) ins[nin++] = argv[i];
     }
     if (!nin || reps < 1) {
-        fprintf(stderr, "usage: h264mi_dec [-R] [-Oout] [-rN] [-T] [-SN] [-Acpus] [-G] in.h264 [in2.h264 ...]\n");
+        fprintf(stderr, "usage: h264mi_dec [-R] [-C] [-Oout] [-rN] [-T] [-SN] [-Acpus] [-G] in.h264 [in2.h264 ...]\n");
         return 2;
     }
     if (cpus) {
@@ -227,6 +255,7 @@ int main(int argc, char **argv)
         if (load(ins[i], &jobs[i])) return 2;
         jobs[i].reps = reps;
         jobs[i].no_reorder = no_reorder;
+        jobs[i].crop = crop;
     }
     FILE *fo = (out && strcmp(out, "none")) ? fopen(out, "wb") : NULL;
     jobs[0].fo = fo;
@@ -269,6 +298,8 @@ int main(int argc, char **argv)
     h264mi_host_thread_stats(&w1, NULL);
     if (fo) fclose(fo);
     for (int i = 0; i < nin; i++) {
+        if (jobs[i].fail == 3) { fprintf(stderr, "out of memory\n"); return 1; }
+        if (jobs[i].fail == 2) { fprintf(stderr, "cropping (-C) is not supported by this backend\n"); return 1; }
         if (jobs[i].fail) { fprintf(stderr, "DECODER INITIALIZATION FAILED\n"); return 1; }
         pics += jobs[i].pics;
         errs += jobs[i].errs;

@@ -7,9 +7,9 @@ of the wasm glue of Decoder/src/Decoder.c:44-162:
 * ``decode`` copies the input into the decoder's stream buffer (a 1 MiB heap
   buffer in the reference, DecoderPost.js:152/:283) and runs synchronously;
 * ``onPictureDecoded`` receives the MB-aligned planar I420 picture
-  (``width*height*3/2`` bytes, width/height multiples of 16, no cropping --
-  H264SwDecApi.c:233-234) plus the ``infos`` collected since the last picture
-  with ``startDecoding``/``finishDecoding`` stamps (DecoderPost.js:77-103);
+  (``width*height*3/2`` bytes, width/height multiples of 16, not cropped --
+  H264SwDecApi.c:233-234; see ``crop`` below) plus the ``infos`` collected
+  since the last picture with ``startDecoding``/``finishDecoding`` stamps (DecoderPost.js:77-103);
 * after a picture completes, the rest of the buffer is dropped
   (Decoder.c:122-134) and the DPB is never flushed (Decoder.c:140), so
   pictures held for display reordering are not emitted.
@@ -18,6 +18,14 @@ of the wasm glue of Decoder/src/Decoder.c:44-162:
   RGBA array (``width*height*4`` bytes) converted on the GPU with the
   reference converter's per-pixel arithmetic (yuv2rgbcalc, :514-560) --
   ``H264SwDecNextPictureRGBA`` instead of ``H264SwDecNextPicture``.
+
+* ``crop: true`` (an extension; the reference leaves cropping to its callers:
+  DecTestBench -C, Player/YUVCanvas.js croppingParams): every picture is
+  cropped to the SPS crop window on the GPU (``H264SwDecNextPictureCropped``)
+  and ``onPictureDecoded(buffer, cropOutWidth, cropOutHeight, infos)`` receives
+  a new packed array of ``cropOutWidth*cropOutHeight*3/2`` bytes -- or, with
+  ``rgb: true`` as well, ``*4`` bytes of RGBA.  A stream without a crop window
+  delivers the whole picture.
 
 Unlike the reference module (a single global instance) every ``Decoder`` has
 its own H264SwDec instance, so several streams can be decoded side by side.
@@ -47,6 +55,7 @@ class Decoder:
         if self.options.get("sliceMode"):
             raise NotImplementedError("sliceMode (per-slice workers) is not part of the MI355X path")
         self._rgb = bool(self.options.get("rgb"))
+        self._crop = bool(self.options.get("crop"))
         self._L = _lib.mi()
         inst = C.c_void_p()
         ret = self._L.H264SwDecInit(C.byref(inst), 0)
@@ -99,7 +108,18 @@ class Decoder:
             inp.dataLen = 0
             self.pic_decode_number += 1
             while True:
-                if self._rgb:
+                if self._crop:
+                    w, h = self._out_size()
+                    out = np.empty(w * h * 4 if self._rgb else w * h * 3 // 2, dtype=np.uint8)
+                    ret = L.H264SwDecNextPictureCropped(self._inst, C.byref(self._pic), 0, out.ctypes.data,
+                                                        int(self._rgb))
+                    if ret == _lib.H264SWDEC_PARAM_ERR:
+                        raise RuntimeError("crop: the backend cannot crop (there is no host fallback)")
+                    if ret != _lib.H264SWDEC_PIC_RDY:
+                        break
+                    self.pic_display_number += 1
+                    self._emit(self._pic, out)
+                elif self._rgb:
                     w, h = self._info.picWidth, self._info.picHeight
                     rgba = np.empty(w * h * 4, dtype=np.uint8)
                     if L.H264SwDecNextPictureRGBA(self._inst, C.byref(self._pic), 0,
@@ -116,8 +136,15 @@ class Decoder:
             inp.dataLen = 0
         return ret
 
+    def _out_size(self):
+        """(width, height) of the pictures handed to onPictureDecoded."""
+        i = self._info
+        if self._crop and i.croppingFlag:
+            return i.cropParams.cropOutWidth, i.cropParams.cropOutHeight
+        return i.picWidth, i.picHeight
+
     def _emit(self, pic, rgba=None) -> None:
-        w, h = self._info.picWidth, self._info.picHeight
+        w, h = self._out_size()
         if rgba is not None:
             buf = rgba
         else:

@@ -179,6 +179,16 @@ class Engine:
             raise RuntimeError("h264mi_engine_read_rgba failed")
         return out
 
+    def read_crop(self, stream: int, slot: int, x: int, y: int, cw: int, ch: int, rgba: bool = False) -> np.ndarray:
+        """The window (x, y, cw, ch; luma pixels, all even) of the slot,
+        cropped on the GPU: packed I420 (cw*ch*3/2 bytes, the layout of the
+        reference testbench's CropPicture) or RGBA (cw*ch*4 bytes)."""
+        out = np.empty(cw * ch * 4 if rgba else cw * ch * 3 // 2, dtype=np.uint8)
+        if self._L.h264mi_engine_read_crop(self._h, stream, slot, x, y, cw, ch, int(bool(rgba)),
+                                           out.ctypes.data) != 0:
+            raise RuntimeError("h264mi_engine_read_crop failed")
+        return out
+
     @property
     def device(self) -> int:
         return int(self._L.h264mi_engine_device(self._h))

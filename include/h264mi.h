@@ -119,6 +119,16 @@ void  H264SwDecMemset(void *ptr, i32 value, u32 count);                         
  * picHeight * 4 bytes; pOutput->pOutputPicture = rgba.  No reference C
  * counterpart: the reference converts in JavaScript. */
 H264SwDecRet H264SwDecNextPictureRGBA(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer, u8 *rgba);
+/* NextPicture, the picture cropped to the active SPS's crop window on the GPU:
+ * what DecTestBench -C writes (CropPicture, DecTestBench.c:588-666) and what
+ * the player displays (YUVCanvas croppingParams).  dst receives cropOutWidth *
+ * cropOutHeight * 3 / 2 bytes of I420, or with rgba != 0 cropOutWidth *
+ * cropOutHeight * 4 bytes of RGBA (H264SwDecGetInfo's cropParams; with
+ * croppingFlag == 0 the whole picture, as NextPicture / NextPictureRGBA
+ * deliver it); pOutput->pOutputPicture = dst.  H264SWDEC_PARAM_ERR when the
+ * backend cannot crop: there is no host fallback. */
+H264SwDecRet H264SwDecNextPictureCropped(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer, u8 *dst,
+                                         u32 rgba);
 /* Extension (no reference counterpart): where an instance's time went, in
  * seconds since H264SwDecInit -- host parse (NAL extraction, headers, CAVLC /
  * MB layer, DPB, concealment), record upload + kernel launch, waiting for the
@@ -274,6 +284,22 @@ int  h264mi_yuv2rgba_device(const void *d_i420, void *d_rgba, int width, int hei
  * h264mi_engine_chroma_pitch; the packed form above is cpitch = width / 2) */
 int  h264mi_yuv2rgba_device_pitch(const void *d_i420, void *d_rgba, int width, int height, int cpitch, int npics,
                                   size_t in_stride, size_t out_stride, void *hip_stream);
+/* display cropping on the device (crop.hip): the window (x, y, cw, ch -- luma
+ * pixels, all even, x + cw <= width, y + ch <= height) of npics pictures of
+ * width x height pixels (even) at d_in + k * in_stride, chroma rows cpitch
+ * bytes apart (an engine slot, or packed I420 with cpitch = width / 2), packed
+ * at d_out + k * out_stride: rgba == 0 I420 in the layout of the reference
+ * testbench's CropPicture (cw * ch * 3 / 2 bytes, DecTestBench.c:588-666),
+ * else RGBA (cw * ch * 4 bytes, the crop of h264mi_yuv2rgba_device's output;
+ * d_out and, for npics > 1, out_stride multiples of 8).  Device pointers,
+ * asynchronous on `hip_stream`.  -1 on a bad argument, nothing launched. */
+int  h264mi_crop_device_pitch(const void *d_in, void *d_out, int width, int height, int cpitch, int x, int y,
+                              int cw, int ch, int rgba, int npics, size_t in_stride, size_t out_stride,
+                              void *hip_stream);
+/* D2H of the crop window of a slot, I420 or RGBA as above: waits for the
+ * engine's launches, crops into a staging buffer, one contiguous copy */
+int  h264mi_engine_read_crop(h264mi_engine *e, int stream, int slot, int x, int y, int cw, int ch, int rgba,
+                             uint8_t *dst);
 int  h264mi_engine_sync(h264mi_engine *e);
 /* number of (launch, picture) slots flagged since the last call: residual
  * range errors (reference transform.c:181) or a bounded wait that expired;
