@@ -77,6 +77,15 @@ class GenParams(C.Structure):
         "nonref_pct", "ref_mod_pct", "mmco_pct", "lt_idr_pct", "crop_left", "crop_top")] + [("seed", C.c_uint64)]
 
 
+class TensorDesc(C.Structure):
+    """h264mi_tensor_desc (include/h264mi.h)."""
+    _fields_ = [(n, C.c_int) for n in ("x", "y", "cw", "ch", "mode", "dtype")] + \
+               [("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
+TENSOR_RGB, TENSOR_GRAY = 0, 1
+TENSOR_U8, TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 0, 1, 2, 3
+
 HEADERS_CB = C.CFUNCTYPE(None, C.c_void_p)
 PICTURE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32)
 
@@ -183,6 +192,14 @@ def mi() -> C.CDLL:
         L.h264mi_crop_device_pitch.restype = i32
         L.h264mi_engine_read_crop.argtypes = [vp] + [i32] * 7 + [vp]
         L.h264mi_engine_read_crop.restype = i32
+    if hasattr(L, "h264mi_tensor_device_pitch"):        # (optional, as above)
+        td = C.POINTER(TensorDesc)
+        L.h264mi_tensor_device_pitch.argtypes = [vp, C.POINTER(sz), i32, i32, i32, i32, td, vp, sz, vp]
+        L.h264mi_tensor_device_pitch.restype = i32
+        L.h264mi_engine_export_tensor.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), td, vp, sz, vp]
+        L.h264mi_engine_export_tensor.restype = i32
+        L.H264SwDecNextPictureTensor.argtypes = [vp, C.POINTER(H264SwDecPicture), u32, td, vp, vp]
+        L.H264SwDecNextPictureTensor.restype = i32
     L.h264mi_engine_sync.argtypes = [vp]
     L.h264mi_engine_sync.restype = i32
     L.h264mi_engine_kernel.argtypes = [vp]

@@ -5,6 +5,7 @@
 #include "recon_kernels.hip"
 #include "color.hip"
 #include "crop.hip"
+#include "tensor.hip"
 #include "conceal.hip"
 #include <hip/hip_ext.h>
 
@@ -85,6 +86,7 @@ struct h264mi_engine {
     int tev_cap, tev_n;
     int tev_stride, tev_seq;  // record every tev_stride-th launch (h264mi_engine_set_timing_stride)
     uint8_t *d_rgba;          // h264mi_engine_read_rgba / _read_crop staging (w*h*4 B, allocated on first use)
+    hipEvent_t ev_exp_in, ev_exp_out;   // h264mi_engine_export_tensor: the caller's stream -> ours -> the caller's (created on first use)
     int steps;                // pictures per stream per launch (h264mi_engine_set_steps)
     unsigned long long *d_prog;   // per picture row of a launch, per row wave: {MBs stored, epoch} (frame-pipelined launches)
     unsigned *d_done;             // per picture row of a launch: epoch once the row is stored
@@ -298,6 +300,8 @@ extern "C" void h264mi_engine_destroy(h264mi_engine *e)
     if (e->h_conceal) (void)hipHostFree(e->h_conceal);
     if (e->d_conceal) (void)hipFree(e->d_conceal);
     if (e->ev_conceal) (void)hipEventDestroy(e->ev_conceal);
+    if (e->ev_exp_in) (void)hipEventDestroy(e->ev_exp_in);
+    if (e->ev_exp_out) (void)hipEventDestroy(e->ev_exp_out);
     h264mi_engine_set_timing(e, 0);
     if (e->st) (void)hipStreamDestroy(e->st);
     free(e);
@@ -1031,6 +1035,86 @@ extern "C" int h264mi_engine_read_crop(h264mi_engine *e, int stream, int slot, i
     HIPCHECK(hipMemcpyAsync(dst, e->d_rgba, bytes, hipMemcpyDeviceToHost, e->st));
     HIPCHECK(hipStreamSynchronize(e->st));
     return 0;
+}
+
+// a window / mode / dtype a tensor export accepts (the window rules are
+// h264mi_crop_device_pitch's)
+static bool tensor_desc_ok(const h264mi_tensor_desc *t, int width, int height)
+{
+    return t && t->x >= 0 && t->y >= 0 && t->cw > 0 && t->ch > 0 && !((t->x | t->y | t->cw | t->ch) & 1) &&
+           t->cw <= width - t->x && t->ch <= height - t->y &&
+           (t->mode == H264MI_TENSOR_RGB || t->mode == H264MI_TENSOR_GRAY) && t->dtype >= H264MI_TENSOR_U8 &&
+           t->dtype <= H264MI_TENSOR_F32;
+}
+
+// Pictures as planar tensors (tensor.hip): the window desc->(x, y, cw, ch) of
+// the npics pictures of width x height pixels that start in_offsets[k] bytes
+// after d_in (chroma rows cpitch bytes apart), as contiguous (planes, ch, cw)
+// elements of desc->dtype at d_out + k * out_stride; device pointers,
+// asynchronous on `stream`; TENSOR_MAX_PICS pictures per launch.  -1 (nothing
+// launched) on a bad argument.
+extern "C" int h264mi_tensor_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width, int height,
+                                          int cpitch, const h264mi_tensor_desc *desc, void *d_out, size_t out_stride,
+                                          void *stream)
+{
+    static_assert(H264MI_TENSOR_RGB == TENSOR_RGB && H264MI_TENSOR_GRAY == TENSOR_GRAY &&
+                      H264MI_TENSOR_U8 == TENSOR_U8 && H264MI_TENSOR_F16 == TENSOR_F16 &&
+                      H264MI_TENSOR_BF16 == TENSOR_BF16 && H264MI_TENSOR_F32 == TENSOR_F32,
+                  "include/h264mi.h and tensor.hip name the same modes and element types");
+    if (!d_in || !in_offsets || !d_out || width <= 0 || height <= 0 || ((width | height) & 1) || npics < 1 ||
+        cpitch < width / 2 || !tensor_desc_ok(desc, width, height))
+        return -1;
+    const size_t es = (size_t)tensor_elem_size(desc->dtype);
+    if (((size_t)(uintptr_t)d_out | out_stride) & (es - 1)) return -1;
+    const bool v16 = !(((size_t)(uintptr_t)d_out | out_stride | (size_t)desc->cw * es) & 15);
+    tensor_args a;
+    a.in = (const uint8_t *)d_in;
+    a.width = width; a.height = height; a.cpitch = cpitch;
+    a.x = desc->x; a.y = desc->y; a.cw = desc->cw; a.ch = desc->ch;
+    a.out_stride = out_stride;
+    for (int p = 0; p < 3; p++) { a.scale[p] = desc->scale[p]; a.bias[p] = desc->bias[p]; }
+    for (int k0 = 0; k0 < npics; k0 += TENSOR_MAX_PICS) {
+        const int n = npics - k0 < TENSOR_MAX_PICS ? npics - k0 : TENSOR_MAX_PICS;
+        for (int k = 0; k < TENSOR_MAX_PICS; k++) a.in_off[k] = k < n ? in_offsets[k0 + k] : 0;
+        a.out = (uint8_t *)d_out + (size_t)k0 * out_stride;
+        tensor_launch(desc->mode, desc->dtype, v16, n, (hipStream_t)stream, a);
+        HIPCHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+// The slots (streams[k], slots[k]), k < n, as tensors in the caller's device
+// memory, with no host synchronisation: the engine's stream waits for what
+// `stream` (NULL: the null stream; ours is non-blocking, so that too goes
+// through events) holds already -- d_out may have been recycled on it --, the
+// kernel runs on the engine's stream, behind every launch queued so far and
+// ahead of every later one, and `stream` waits for the kernel.
+extern "C" int h264mi_engine_export_tensor(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                           const h264mi_tensor_desc *desc, void *d_out, size_t out_stride, void *stream)
+{
+    if (!e || n < 1 || !streams || !slots || !d_out || !tensor_desc_ok(desc, e->w * 16, e->h * 16)) return -1;
+    for (int k = 0; k < n; k++)
+        if (streams[k] < 0 || streams[k] >= e->nstreams || slots[k] < 0 || slots[k] >= e->nslots) return -1;
+    const size_t es = (size_t)tensor_elem_size(desc->dtype);
+    if (((size_t)(uintptr_t)d_out | out_stride) & (es - 1)) return -1;
+    if (h264mi_pointer_device(d_out) != e->dev) return -1;
+    HIPCHECK(hipSetDevice(e->dev));
+    if (!e->ev_exp_in) HIPCHECK(hipEventCreateWithFlags(&e->ev_exp_in, hipEventDisableTiming));
+    if (!e->ev_exp_out) HIPCHECK(hipEventCreateWithFlags(&e->ev_exp_out, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(e->ev_exp_in, (hipStream_t)stream));
+    HIPCHECK(hipStreamWaitEvent(e->st, e->ev_exp_in, 0));
+    int rc = 0;
+    for (int k0 = 0; k0 < n && !rc; k0 += TENSOR_MAX_PICS) {
+        size_t off[TENSOR_MAX_PICS];
+        const int m = n - k0 < TENSOR_MAX_PICS ? n - k0 : TENSOR_MAX_PICS;
+        for (int k = 0; k < m; k++) off[k] = e->frame_bytes * ((size_t)streams[k0 + k] * e->nslots + slots[k0 + k]);
+        rc = h264mi_tensor_device_pitch(e->d_frames, off, m, e->w * 16, e->h * 16, e->cpitch, desc,
+                                        (uint8_t *)d_out + (size_t)k0 * out_stride, out_stride, e->st);
+    }
+    // (also after a failed launch: whatever reached our stream stays ordered)
+    HIPCHECK(hipEventRecord(e->ev_exp_out, e->st));
+    HIPCHECK(hipStreamWaitEvent((hipStream_t)stream, e->ev_exp_out, 0));
+    return rc;
 }
 
 extern "C" void *h264mi_engine_frame_ptr(h264mi_engine *e, int stream, int slot)

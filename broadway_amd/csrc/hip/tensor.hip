@@ -1,0 +1,212 @@
+// Decoded pictures as device tensors: the window (x, y, cw, ch -- all even) of
+// each of a list of pictures as contiguous planes, (3, ch, cw) R G B with the
+// pixel values of color.hip (rgba_group_px; x and y are even, so the RGB of the
+// crop is the crop of the RGB) or (1, ch, cw) luma, as uint8, fp16, bf16 or
+// fp32.  The float types hold fma((float)c, scale[p], bias[p]) of plane p: one
+// fp32 fused multiply-add, then (16-bit types) one round-to-nearest-even
+// conversion (v_cvt_f16_f32 / v_cvt_pk_bf16_f32).  Input as in crop.hip: luma
+// rows `width` apart, chroma rows `cpitch` apart (an engine slot, or packed
+// I420 with cpitch = width / 2); picture k starts in_off[k] bytes after `in`
+// and goes to out + k * out_stride.
+//
+// HBM-bound elementwise kernels, 64 threads per block, work items in raster
+// order (no lane idles at row ends), non-temporal stores.  A work item is two
+// rows of 4 * NG columns, NG the 4-column groups of color.hip it holds:
+//   V16   row starts are 16-byte aligned (out, out_stride and cw * element
+//         size are multiples of 16): NG = 4 / element size, so a lane stores
+//         16 bytes per plane row, 6 stores (RGB) or 2 (GRAY) per item;
+//   else  NG = 1 and every element is stored on its own (a row can start on
+//         any element, and a row pair's last group is 2 columns wide when
+//         cw = 2 mod 4).
+// Luma and chroma bytes come from aligned dwords through v_alignbyte, as in
+// crop.hip (x can be 2 mod 4, x / 2 odd, a picture can start on any byte).
+
+#define TENSOR_MAX_PICS 32          // pictures per launch (their offsets travel in the kernel arguments)
+
+enum { TENSOR_RGB = 0, TENSOR_GRAY = 1 };
+enum { TENSOR_U8 = 0, TENSOR_F16 = 1, TENSOR_BF16 = 2, TENSOR_F32 = 3 };
+
+struct tensor_args {
+    const uint8_t *in;
+    uint8_t *out;
+    int width, height, cpitch, x, y, cw, ch;
+    size_t out_stride;
+    float scale[3], bias[3];
+    unsigned long long in_off[TENSOR_MAX_PICS];
+};
+
+typedef float tensor_f32x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 tensor_f16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 tensor_bf16x2 __attribute__((ext_vector_type(2)));
+
+__host__ __device__ constexpr int tensor_elem_size(int dt) { return dt == TENSOR_U8 ? 1 : dt == TENSOR_F32 ? 4 : 2; }
+
+// the 4 * NW source bytes at s (any alignment, all inside the picture): the
+// aligned dwords holding them, realigned.  The last dword is read only when
+// s is not aligned (it then holds the last byte).
+template <int NW>
+__device__ __forceinline__ void tensor_load(const uint8_t *s, uint32_t (&d)[NW])
+{
+    const uint32_t sh = (uint32_t)(uintptr_t)s & 3u;
+    const uint32_t *q = (const uint32_t *)(s - sh);
+    uint32_t e[NW + 1];
+#pragma unroll
+    for (int j = 0; j < NW; j++) e[j] = q[j];
+    e[NW] = q[sh ? NW : NW - 1];
+#pragma unroll
+    for (int j = 0; j < NW; j++) d[j] = __builtin_amdgcn_alignbyte(e[j + 1], e[j], sh);
+}
+
+// element i of a plane row: the sample c as the element type's bits
+template <int DT>
+__device__ __forceinline__ uint32_t tensor_elem(uint32_t c, float s, float b)
+{
+    if constexpr (DT == TENSOR_U8) return c;
+    const float f = __builtin_fmaf((float)c, s, b);
+    if constexpr (DT == TENSOR_F16) return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f);
+    if constexpr (DT == TENSOR_BF16) return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)f);
+    return __builtin_bit_cast(uint32_t, f);
+}
+
+// one plane row of an item: the samples c[0 .. n) as elements at d.  V16:
+// n = N = 16 / element size and d is 16-byte aligned.
+template <int DT, int N, bool V16>
+__device__ __forceinline__ void tensor_store(const uint32_t (&c)[N], int n, float s, float b, uint8_t *d)
+{
+    constexpr int ES = tensor_elem_size(DT);
+    if constexpr (V16) {
+        static_assert(N * ES == 16, "a lane stores 16 bytes");
+        constexpr int PER = 4 / ES;                 // elements per dword
+        uint32_t w[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if constexpr (ES == 2) {
+                // both halves of a dword in one packed conversion
+                const tensor_f32x2 f = {__builtin_fmaf((float)c[2 * j], s, b), __builtin_fmaf((float)c[2 * j + 1], s, b)};
+                if constexpr (DT == TENSOR_F16) w[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(f, tensor_f16x2));
+                else w[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(f, tensor_bf16x2));
+            } else {
+                w[j] = 0;
+#pragma unroll
+                for (int i = 0; i < PER; i++) {
+                    uint32_t v = tensor_elem<DT>(c[PER * j + i], s, b);
+                    // the sample as an opaque value: from clamp(x >> 10, 0, 255) | clamp(..) << 8 the
+                    // compiler forms v_ashr_pk_u8_i32 and ORs bytes 2 and 3 into its result as if the
+                    // upper half were zero, but on gfx950 the instruction leaves the destination's
+                    // upper 16 bits as they were (here: those of x, its first source)
+                    if constexpr (DT == TENSOR_U8) asm("" : "+v"(v));
+                    w[j] |= v << (8 * ES * i);
+                }
+            }
+        }
+        const crop_u32x4 o = {w[0], w[1], w[2], w[3]};
+        __builtin_nontemporal_store(o, (crop_u32x4 *)d);
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; i++) {
+            if (i >= n) break;
+            const uint32_t v = tensor_elem<DT>(c[i], s, b);
+            if (ES == 1) __builtin_nontemporal_store((uint8_t)v, d + i);
+            else if (ES == 2) __builtin_nontemporal_store((uint16_t)v, (uint16_t *)d + i);
+            else __builtin_nontemporal_store(v, (uint32_t *)d + i);
+        }
+    }
+}
+
+// grid: (ceil(items / 128) blocks of 64 threads, pictures of this launch),
+// items = the window's (row pair, 4 * NG-column group) pairs in raster order
+template <int MODE, int DT, bool V16>
+__global__ __launch_bounds__(64) void k_tensor(const tensor_args a)
+{
+    constexpr int ES = tensor_elem_size(DT);
+    constexpr int NG = V16 ? 4 / ES : 1;            // 4-column groups per item
+    constexpr int NC = 4 * NG;                      // columns per item
+    constexpr int NP = MODE == TENSOR_RGB ? 3 : 1;
+    const int width = a.width, cpitch = a.cpitch, cw = a.cw;
+    const int ni = (cw + NC - 1) / NC;              // items per row pair
+    const int nf = ni * (a.ch >> 1);
+    const uint8_t *Y = a.in + a.in_off[blockIdx.y];
+    const uint8_t *U = Y + (size_t)width * a.height + (size_t)(a.y >> 1) * cpitch + (a.x >> 1);
+    const uint8_t *V = U + (size_t)cpitch * (a.height >> 1);
+    Y += (size_t)a.y * width + a.x;
+    uint8_t *O = a.out + blockIdx.y * a.out_stride;
+    const size_t plane = (size_t)cw * a.ch * ES;
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const int f = blockIdx.x * 128 + h * 64 + (int)threadIdx.x;
+        if (f >= nf) continue;
+        const int y2 = f / ni, g = f - y2 * ni;
+        const uint8_t *sy = Y + (size_t)(2 * y2) * width + NC * g;
+        const size_t co = (size_t)y2 * cpitch + (NC / 2) * g;
+        // V16: cw is a multiple of NC; else the row pair's last group can be 2 columns wide
+        const bool full = V16 || NC * g + NC <= cw;
+        uint32_t y0[NG], y1[NG], u[(NG + 1) / 2], v[(NG + 1) / 2];
+        if (full) {
+            tensor_load<NG>(sy, y0);
+            tensor_load<NG>(sy + width, y1);
+        } else {
+            y0[0] = crop_load2(sy);
+            y1[0] = crop_load2(sy + width);
+        }
+        if (MODE == TENSOR_RGB) {
+            if (NG >= 2) {
+                tensor_load<(NG + 1) / 2>(U + co, u);
+                tensor_load<(NG + 1) / 2>(V + co, v);
+            } else if (full) {
+                u[0] = crop_load2(U + co);
+                v[0] = crop_load2(V + co);
+            } else {
+                u[0] = U[co];
+                v[0] = V[co];
+            }
+        }
+        // c[row][plane][column]: the samples of the item
+        uint32_t c[2][NP][NC];
+#pragma unroll
+        for (int k = 0; k < NG; k++) {
+            if (MODE == TENSOR_RGB) {
+                uint32_t o0[4], o1[4];
+                rgba_group_px(y0[k], y1[k], (u[k >> 1] >> (16 * (k & 1))) & 0xFFFFu, (v[k >> 1] >> (16 * (k & 1))) & 0xFFFFu,
+                              o0, o1);
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+#pragma unroll
+                    for (int p = 0; p < NP; p++) {
+                        c[0][p][4 * k + i] = (o0[i] >> (8 * p)) & 255u;
+                        c[1][p][4 * k + i] = (o1[i] >> (8 * p)) & 255u;
+                    }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    c[0][0][4 * k + i] = (y0[k] >> (8 * i)) & 255u;
+                    c[1][0][4 * k + i] = (y1[k] >> (8 * i)) & 255u;
+                }
+            }
+        }
+        const int n = full ? NC : 2;
+        uint8_t *d = O + ((size_t)(2 * y2) * cw + NC * g) * ES;
+#pragma unroll
+        for (int p = 0; p < NP; p++) {
+            tensor_store<DT, NC, V16>(c[0][p], n, a.scale[p], a.bias[p], d + p * plane);
+            tensor_store<DT, NC, V16>(c[1][p], n, a.scale[p], a.bias[p], d + p * plane + (size_t)cw * ES);
+        }
+    }
+}
+
+// launch for (mode, dtype, v16); items per row pair as in the kernel
+static void tensor_launch(int mode, int dt, bool v16, int npics, hipStream_t st, const tensor_args &a)
+{
+    const int nc = v16 ? 16 / tensor_elem_size(dt) : 4;
+    const int nf = ((a.cw + nc - 1) / nc) * (a.ch >> 1);
+    const dim3 grid((nf + 127) >> 7, npics), block(64);
+#define TENSOR_CASE(M, D)                                                                 \
+    if (mode == M && dt == D) {                                                           \
+        if (v16) hipLaunchKernelGGL((k_tensor<M, D, true>), grid, block, 0, st, a);       \
+        else hipLaunchKernelGGL((k_tensor<M, D, false>), grid, block, 0, st, a);          \
+    }
+    TENSOR_CASE(TENSOR_RGB, TENSOR_U8) TENSOR_CASE(TENSOR_RGB, TENSOR_F16)
+    TENSOR_CASE(TENSOR_RGB, TENSOR_BF16) TENSOR_CASE(TENSOR_RGB, TENSOR_F32)
+    TENSOR_CASE(TENSOR_GRAY, TENSOR_U8) TENSOR_CASE(TENSOR_GRAY, TENSOR_F16)
+    TENSOR_CASE(TENSOR_GRAY, TENSOR_BF16) TENSOR_CASE(TENSOR_GRAY, TENSOR_F32)
+#undef TENSOR_CASE
+}

@@ -251,6 +251,54 @@ H264SwDecRet H264SwDecNextPictureCropped(H264SwDecInst decInst, H264SwDecPicture
     return H264SWDEC_PIC_RDY;
 }
 
+/* NextPicture with the picture exported to device memory as a planar tensor
+ * (include/h264mi.h); desc == NULL: RGB fp16, scale 1/255, over the active
+ * SPS's crop window, which a desc with cw == 0 takes as well.  A backend
+ * without export_tensor: H264SWDEC_PARAM_ERR, no host fallback. */
+H264SwDecRet H264SwDecNextPictureTensor(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
+                                        const h264mi_tensor_desc *desc, void *d_dst, void *hip_stream)
+{
+    if (decInst == NULL || pOutput == NULL || d_dst == NULL) return H264SWDEC_PARAM_ERR;
+    DecContainer *c = (DecContainer *)decInst;
+    if (!c->dec.be.export_tensor) return H264SWDEC_PARAM_ERR;
+    h264mi_tensor_desc t;
+    if (desc) {
+        t = *desc;
+    } else {
+        memset(&t, 0, sizeof(t));
+        t.mode = H264MI_TENSOR_RGB;
+        t.dtype = H264MI_TENSOR_F16;
+        for (int p = 0; p < 3; p++) t.scale[p] = 1.0f / 255.0f;
+    }
+    if ((t.mode != H264MI_TENSOR_RGB && t.mode != H264MI_TENSOR_GRAY) || t.dtype < H264MI_TENSOR_U8 ||
+        t.dtype > H264MI_TENSOR_F32)
+        return H264SWDEC_PARAM_ERR;
+    const size_t es = t.dtype == H264MI_TENSOR_U8 ? 1 : t.dtype == H264MI_TENSOR_F32 ? 4 : 2;
+    if ((size_t)(uintptr_t)d_dst & (es - 1)) return H264SWDEC_PARAM_ERR;
+    if (flushBuffer) h264dec_flush(&c->dec);
+    const Sps *s = h264dec_active_sps(&c->dec);
+    if (!s) return H264SWDEC_OK;                    /* no headers yet: no picture either */
+    const int width = 16 * (int)s->w_mbs, height = 16 * (int)s->h_mbs;
+    if (t.cw == 0) {
+        const int cl = s->crop ? 2 * (int)s->crop_l : 0, ct = s->crop ? 2 * (int)s->crop_t : 0;
+        const int cr = s->crop ? 2 * (int)s->crop_r : 0, cb = s->crop ? 2 * (int)s->crop_b : 0;
+        t.x = cl; t.y = ct; t.cw = width - cl - cr; t.ch = height - ct - cb;
+    }
+    if (t.x < 0 || t.y < 0 || t.cw <= 0 || t.ch <= 0 || ((t.x | t.y | t.cw | t.ch) & 1) || t.cw > width - t.x ||
+        t.ch > height - t.y)
+        return H264SWDEC_PARAM_ERR;
+    uint32_t id, idr, em;
+    int failed = 0;
+    const uint8_t *pic = h264dec_next_output_tensor(&c->dec, &id, &idr, &em, &t, d_dst, hip_stream, &failed);
+    if (failed) return H264SWDEC_PARAM_ERR;         /* (d_dst not on the decoder's GPU) */
+    if (!pic) return H264SWDEC_OK;
+    pOutput->pOutputPicture = (u32 *)(void *)pic;
+    pOutput->picId = id;
+    pOutput->isIdrPicture = idr;
+    pOutput->nbrOfErrMBs = em;
+    return H264SWDEC_PIC_RDY;
+}
+
 H264SwDecRet H264SwDecGetTiming(H264SwDecInst decInst, double *parse_s, double *submit_s, double *wait_s,
                                 double *copy_s, u32 *pictures)
 {

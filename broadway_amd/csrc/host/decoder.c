@@ -399,8 +399,8 @@ static int finish_picture(H264Dec *d, int concealed_mbs)
     const double t0 = h264dec_now();
     int rc = d->be.decode(d->be.ctx, &d->pb, d->cur_slot);
     /* the picture's output copy starts now, behind its reconstruction --
-     * unless the caller takes its pictures cropped (out_cropped): the
-     * MB-aligned copy would cross PCIe for nothing */
+     * unless the caller takes its pictures cropped or as device tensors
+     * (out_cropped): the MB-aligned copy would cross PCIe for nothing */
     if (!rc && d->be.prefetch && d->out_frames && !d->out_cropped)
         rc = d->be.prefetch(d->be.ctx, d->cur_slot, d->out_frames + d->frame_bytes * (size_t)d->cur_slot);
     d->t_submit += h264dec_now() - t0;
@@ -603,35 +603,54 @@ const uint8_t *h264dec_next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_id
     return h264dec_next_output_rgba(d, pic_id, is_idr, err_mbs, NULL);
 }
 
+/* a tensor export (h264dec_next_output_tensor); failed: the backend refused it */
+typedef struct TensorOut {
+    const void *desc;
+    void *d_dst, *hip_stream;
+    int failed;
+} TensorOut;
+
 /* rgba != NULL: the picture as RGBA (w*h*4 bytes) into rgba, converted by
  * the backend (returns rgba) */
 static const uint8_t *next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs, uint8_t *rgba,
-                                  uint8_t *crop, int crop_rgba);
+                                  uint8_t *crop, int crop_rgba, TensorOut *tensor);
 
 const uint8_t *h264dec_next_output_rgba(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
                                         uint8_t *rgba)
 {
-    return next_output(d, pic_id, is_idr, err_mbs, rgba, NULL, 0);
+    return next_output(d, pic_id, is_idr, err_mbs, rgba, NULL, 0, NULL);
 }
 
 const uint8_t *h264dec_next_output_crop(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
                                         uint8_t *dst, int rgba)
 {
     if (!dst) return NULL;
-    return next_output(d, pic_id, is_idr, err_mbs, NULL, dst, rgba);
+    return next_output(d, pic_id, is_idr, err_mbs, NULL, dst, rgba, NULL);
+}
+
+const uint8_t *h264dec_next_output_tensor(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
+                                          const void *desc, void *d_dst, void *hip_stream, int *failed)
+{
+    TensorOut t = {desc, d_dst, hip_stream, 0};
+    const uint8_t *r = desc && d_dst ? next_output(d, pic_id, is_idr, err_mbs, NULL, NULL, 0, &t) : NULL;
+    if (failed) *failed = t.failed;
+    return r;
 }
 
 /* crop != NULL: the active SPS's crop window of the picture (the whole
- * picture without one) into crop, as I420 or (crop_rgba) RGBA */
+ * picture without one) into crop, as I420 or (crop_rgba) RGBA; tensor !=
+ * NULL: the picture as a tensor in device memory (nothing is copied out) */
 static const uint8_t *next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs, uint8_t *rgba,
-                                  uint8_t *crop, int crop_rgba)
+                                  uint8_t *crop, int crop_rgba, TensorOut *tensor)
 {
     if (rgba && !d->be.read_rgba) return NULL;
+    if (tensor && !d->be.export_tensor) return NULL;
     const Sps *sps = crop ? h264dec_active_sps(d) : NULL;
     if (crop && (!d->be.read_crop || !sps)) return NULL;
     const DpbOut *o = dpb_next_output(&d->dpb);
     if (!o) return NULL;
-    uint8_t *dst = crop ? crop : rgba ? rgba : d->out_frames + d->frame_bytes * (size_t)o->slot;
+    uint8_t *dst = tensor ? (uint8_t *)tensor->d_dst : crop ? crop : rgba ? rgba
+                                                     : d->out_frames + d->frame_bytes * (size_t)o->slot;
     /* rather than wait for the GPU, parse the next picture's slices that
      * spec_launch_ahead queued (the buffer already holds them); the core
      * stays busy and warm, and the decode call that follows takes them */
@@ -644,7 +663,10 @@ static const uint8_t *next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr
     if (d->be.sync && d->be.sync(d->be.ctx)) return NULL;
     const double t1 = h264dec_now();
     int rr;
-    if (crop) {
+    if (tensor) {
+        rr = d->be.export_tensor(d->be.ctx, o->slot, tensor->desc, tensor->d_dst, tensor->hip_stream);
+        tensor->failed = rr < 0;
+    } else if (crop) {
         const int cl = sps->crop ? 2 * sps->crop_l : 0, ct = sps->crop ? 2 * sps->crop_t : 0;
         const int cr = sps->crop ? 2 * sps->crop_r : 0, cb = sps->crop ? 2 * sps->crop_b : 0;
         rr = d->be.read_crop(d->be.ctx, o->slot, cl, ct, 16 * sps->w_mbs - cl - cr, 16 * sps->h_mbs - ct - cb,
@@ -655,7 +677,7 @@ static const uint8_t *next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr
     d->t_wait += t1 - t0;
     d->t_copy += h264dec_now() - t1;
     d->n_output++;
-    d->out_cropped = crop != NULL;
+    d->out_cropped = crop != NULL || tensor != NULL;
     if (rr < 0) return NULL;
     if (pic_id) *pic_id = (uint32_t)o->pic_id;
     if (is_idr) *is_idr = (uint32_t)o->is_idr;

@@ -46,6 +46,11 @@ typedef struct H264Backend {
      * I420 (cw * ch * 3 / 2 bytes) or with rgba != 0 as RGBA (cw * ch * 4
      * bytes); same returns; NULL when the backend cannot crop */
     int  (*read_crop)(void *ctx, int slot, int x, int y, int cw, int ch, int rgba, uint8_t *dst);
+    /* export slot as a planar tensor into device memory d_dst, ordered on the
+     * caller's HIP stream hip_stream (desc: a checked h264mi_tensor_desc,
+     * include/h264mi.h); nothing reaches the host; same returns; NULL when
+     * the backend cannot export */
+    int  (*export_tensor)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
     /* optional: host memory for the output frames (pinned by the HIP
      * backend, so each picture's D2H copy runs at DMA speed); NULL: malloc */
     void *(*host_alloc)(void *ctx, size_t bytes);
@@ -117,10 +122,10 @@ typedef struct H264Dec {
     uint8_t *out_frames;
     size_t   frame_bytes;
     int      nslots;
-    /* the last picture left through h264dec_next_output_crop: the next
-     * pictures' uncropped copies into out_frames are not started (nobody
-     * reads them); a plain next_output clears it and reads synchronously
-     * until the copies are back */
+    /* the last picture left through h264dec_next_output_crop or
+     * h264dec_next_output_tensor: the next pictures' uncropped copies into
+     * out_frames are not started (nobody reads them); a plain next_output
+     * clears it and reads synchronously until the copies are back */
     int      out_cropped;
     /* statistics */
     uint64_t pics_decoded, alg_ref_bytes, coded_blocks;
@@ -151,6 +156,11 @@ const uint8_t *h264dec_next_output_rgba(H264Dec *d, uint32_t *pic_id, uint32_t *
  * picture without one) into dst by the backend's read_crop (returns dst) */
 const uint8_t *h264dec_next_output_crop(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
                                         uint8_t *dst, int rgba);
+/* the same, the picture exported by the backend's export_tensor (returns
+ * d_dst, a device pointer); *failed = 1 when the export of the picture taken
+ * from the DPB failed */
+const uint8_t *h264dec_next_output_tensor(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
+                                          const void *desc, void *d_dst, void *hip_stream, int *failed);
 int  h264dec_valid_param_sets(const H264Dec *d);
 /* conceal the current picture's missing MBs (conceal.c); returns their
  * number or -1 */

@@ -522,6 +522,28 @@ static int hb_read_crop(void *vctx, int slot, int x, int y, int cw, int ch, int 
     return slot_flagged(c, slot, false);
 }
 
+// Weak like the crop entry points: a backend built against the CPU stand-in of
+// the engine leaves export_tensor NULL (H264SwDecNextPictureTensor then fails).
+extern "C" int h264mi_engine_export_tensor(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                           const h264mi_tensor_desc *desc, void *d_out, size_t out_stride,
+                                           void *hip_stream) __attribute__((weak));
+
+// nothing waits here: the decoder synced before (the slot's flags are on the
+// host), and the export orders itself on the engine's and the caller's stream
+static int hb_export_tensor(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
+{
+    HipBackendCtx *c = (HipBackendCtx *)vctx;
+    if (slot < 0 || slot >= c->nslots) return -1;
+    const int lane = c->lane;
+    std::unique_lock<std::mutex> l;
+    if (c->sh) l = std::unique_lock<std::mutex>(c->sh->mu);
+    if (h264mi_engine_export_tensor(c->e, 1, &lane, &slot, (const h264mi_tensor_desc *)desc, d_dst, 0, hip_stream))
+        return -1;
+    if (c->sh) HIPCHECK(hipEventRecord(c->ev_last, engine_stream(c->e)));
+    c->enq++;
+    return slot_flagged(c, slot, false);
+}
+
 // Pinned host blocks (decoder output frames) kept after free for the next
 // decoder instance: pinning tens of MB per instance is a large share of a
 // short stream's host time.  Exact-size reuse, at most H264MI_HOST_POOL_MB
@@ -652,6 +674,7 @@ extern "C" H264Backend h264mi_hip_backend_create(int device)
     be.read = hb_read;
     be.read_rgba = hb_read_rgba;
     be.read_crop = h264mi_engine_read_crop && h264mi_crop_device_pitch ? hb_read_crop : NULL;
+    be.export_tensor = h264mi_engine_export_tensor ? hb_export_tensor : NULL;
     be.host_alloc = hb_host_alloc;
     be.host_free = hb_host_free;
     be.records_wait = hb_records_wait;

@@ -27,6 +27,15 @@ of the wasm glue of Decoder/src/Decoder.c:44-162:
   ``rgb: true`` as well, ``*4`` bytes of RGBA.  A stream without a crop window
   delivers the whole picture.
 
+* ``tensor: true`` or ``tensor: {"dtype": ..., "mode": ..., "mean": ...,
+  "std": ..., "scale": ..., "bias": ...}`` (an extension for device consumers;
+  needs torch, imported only on this path): nothing is copied to the host.
+  ``onPictureDecoded(tensor, width, height, infos)`` receives a new
+  ``(planes, height, width)`` torch tensor on the decoder's GPU, cropped to the
+  SPS crop window, built by ``H264SwDecNextPictureTensor`` on torch's current
+  stream -- the arguments of ``Engine.to_tensor`` (default: RGB, float16,
+  scale 1/255).  It combines with neither ``rgb`` nor ``crop`` (ValueError).
+
 Unlike the reference module (a single global instance) every ``Decoder`` has
 its own H264SwDec instance, so several streams can be decoded side by side.
 Reconstruction always runs on the GPU through libh264mi.so; ``sliceMode``
@@ -35,6 +44,7 @@ Reconstruction always runs on the GPU through libh264mi.so; ``sliceMode``
 from __future__ import annotations
 
 import ctypes as C
+import os
 import time
 from typing import Callable, List, Optional
 
@@ -56,6 +66,17 @@ class Decoder:
             raise NotImplementedError("sliceMode (per-slice workers) is not part of the MI355X path")
         self._rgb = bool(self.options.get("rgb"))
         self._crop = bool(self.options.get("crop"))
+        self._tensor = self.options.get("tensor") or None
+        if self._tensor is not None:
+            if self._rgb or self._crop:
+                raise ValueError("tensor: not combinable with rgb or crop (mode='rgb' and the SPS window are part of it)")
+            opts = {} if self._tensor is True else dict(self._tensor)
+            unknown = set(opts) - {"dtype", "mode", "mean", "std", "scale", "bias"}
+            if unknown:
+                raise ValueError(f"tensor: unknown keys {sorted(unknown)}")
+            from .engine import tensor_desc          # (imports torch)
+            self._tensor = tensor_desc(None, **opts)
+            self._device = int(os.environ.get("H264MI_DEVICE") or 0)     # the GPU H264SwDecInit takes (api.c)
         self._L = _lib.mi()
         inst = C.c_void_p()
         ret = self._L.H264SwDecInit(C.byref(inst), 0)
@@ -108,7 +129,23 @@ class Decoder:
             inp.dataLen = 0
             self.pic_decode_number += 1
             while True:
-                if self._crop:
+                if self._tensor is not None:
+                    import torch
+                    desc, planes, dtype = self._tensor
+                    w, h = self._out_size()
+                    dev = torch.device("cuda", self._device)
+                    with torch.cuda.device(dev):
+                        out = torch.empty((planes, h, w), dtype=dtype, device=dev)
+                    ret = L.H264SwDecNextPictureTensor(self._inst, C.byref(self._pic), 0, C.byref(desc),
+                                                       out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+                    if ret == _lib.H264SWDEC_PARAM_ERR:
+                        raise RuntimeError("tensor: the backend cannot export device tensors "
+                                           "(there is no host fallback)")
+                    if ret != _lib.H264SWDEC_PIC_RDY:
+                        break
+                    self.pic_display_number += 1
+                    self._emit(self._pic, out)
+                elif self._crop:
                     w, h = self._out_size()
                     out = np.empty(w * h * 4 if self._rgb else w * h * 3 // 2, dtype=np.uint8)
                     ret = L.H264SwDecNextPictureCropped(self._inst, C.byref(self._pic), 0, out.ctypes.data,
@@ -139,7 +176,7 @@ class Decoder:
     def _out_size(self):
         """(width, height) of the pictures handed to onPictureDecoded."""
         i = self._info
-        if self._crop and i.croppingFlag:
+        if (self._crop or self._tensor is not None) and i.croppingFlag:
             return i.cropParams.cropOutWidth, i.cropParams.cropOutHeight
         return i.picWidth, i.picHeight
 

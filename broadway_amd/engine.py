@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import List, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -18,6 +18,56 @@ from . import _lib
 
 MBREC_BYTES = 96
 PICDESC_BYTES = 32
+
+
+def tensor_affine(mean: Sequence[float], std: Sequence[float]) -> Tuple[Tuple[float, ...], Tuple[float, ...]]:
+    """(scale, bias) of ``(c / 255 - mean) / std`` for 8-bit samples c: mean
+    and std are per-plane triples in 0..1 units; scale = 1 / (255 * std) and
+    bias = -mean / std, computed in float64 and rounded once to fp32 (the
+    values the kernel's fused multiply-add takes)."""
+    mean, std = [float(m) for m in mean], [float(s) for s in std]
+    if len(mean) != 3 or len(std) != 3:
+        raise ValueError("mean and std are triples")
+    scale = tuple(float(np.float32(1.0 / (255.0 * s))) for s in std)
+    bias = tuple(float(np.float32(-m / s)) for m, s in zip(mean, std))
+    return scale, bias
+
+
+def tensor_desc(window, mode="rgb", dtype=None, scale=None, bias=None, mean=None, std=None):
+    """(``_lib.TensorDesc``, planes, torch dtype) of a tensor export
+    (Engine.to_tensor, Decoder's ``tensor`` option); window = (x, y, cw, ch),
+    or None for the decoder's SPS crop window (cw = 0 in the descriptor)."""
+    import torch
+    dtype = torch.float16 if dtype is None else dtype
+    dts = {torch.uint8: _lib.TENSOR_U8, torch.float16: _lib.TENSOR_F16, torch.bfloat16: _lib.TENSOR_BF16,
+           torch.float32: _lib.TENSOR_F32}
+    modes = {"rgb": (_lib.TENSOR_RGB, 3), "gray": (_lib.TENSOR_GRAY, 1)}
+    if dtype not in dts:
+        raise ValueError(f"dtype {dtype}: one of torch.uint8, float16, bfloat16, float32")
+    if mode not in modes:
+        raise ValueError(f"mode {mode!r}: 'rgb' or 'gray'")
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std go together")
+    if mean is not None:
+        if scale is not None or bias is not None:
+            raise ValueError("mean / std or scale / bias, not both")
+        scale, bias = tensor_affine(mean, std)
+
+    def triple(v, default):
+        if v is None:
+            return (default,) * 3
+        v = tuple(float(f) for f in v) if hasattr(v, "__len__") else (float(v),) * 3
+        if len(v) != 3:
+            raise ValueError("scale and bias are scalars or triples")
+        return v
+
+    d = _lib.TensorDesc()
+    d.x, d.y, d.cw, d.ch = (int(v) for v in window) if window is not None else (0, 0, 0, 0)
+    d.mode, planes = modes[mode]
+    d.dtype = dts[dtype]
+    d.scale[:] = triple(scale, 1.0 / 255.0)
+    d.bias[:] = triple(bias, 0.0)
+    return d, planes, dtype
 
 
 @dataclass
@@ -187,6 +237,54 @@ class Engine:
         if self._L.h264mi_engine_read_crop(self._h, stream, slot, x, y, cw, ch, int(bool(rgba)),
                                            out.ctypes.data) != 0:
             raise RuntimeError("h264mi_engine_read_crop failed")
+        return out
+
+    def to_tensor(self, streams: Sequence[int], slots: Sequence[int], window=None, mode: str = "rgb", dtype=None,
+                  scale=None, bias=None, mean=None, std=None, out=None, stream=None):
+        """The slots (streams[k], slots[k]) as one ``(n, planes, ch, cw)``
+        torch tensor on ``cuda:{self.device}``, built on the GPU and never
+        copied to the host: planes R, G, B (``mode="rgb"``, the values of
+        read_rgba) or luma (``"gray"``) of ``window`` = (x, y, cw, ch), all
+        even (None: the whole picture), as ``dtype`` (torch.uint8, float16 --
+        the default --, bfloat16 or float32).  Float elements are
+        ``fma(c, scale[p], bias[p])`` in fp32, rounded once more to the 16-bit
+        types; scale and bias are scalars or per-plane triples (default
+        1 / 255 and 0), or come from ``mean`` / ``std`` (``tensor_affine``);
+        uint8 ignores them.
+
+        The export is ordered on ``stream`` (a torch.cuda.Stream; default:
+        torch's current stream of the device): it starts after the work queued
+        there and after every launch queued on the engine, later work on
+        ``stream`` sees the tensor, and a later launch that overwrites a slot
+        waits for it.  The host is never synchronised.  ``out``: a contiguous
+        tensor of the result's shape, dtype and device to fill instead of a
+        new ``torch.empty``.  The result is an ordinary torch tensor, so DLPack
+        consumers (``torch.utils.dlpack`` / ``__dlpack__``) need nothing further."""
+        import torch
+        n = len(streams)
+        if n < 1 or len(slots) != n:
+            raise ValueError("streams and slots name the same, non-zero number of pictures")
+        if window is None:
+            window = (0, 0, self.w_mbs * 16, self.h_mbs * 16)
+        desc, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std)
+        shape = (n, planes, desc.ch, desc.cw)
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            if min(shape) < 1:
+                raise ValueError(f"window {tuple(window)}")
+            with torch.cuda.device(self.device):
+                out = torch.empty(shape, dtype=dtype, device=dev)
+        elif tuple(out.shape) != shape or out.dtype != dtype or out.device != dev or not out.is_contiguous():
+            raise ValueError(f"out: a contiguous {dtype} tensor of shape {shape} on {dev} "
+                             f"(got {out.dtype} {tuple(out.shape)} on {out.device})")
+        cur = torch.cuda.current_stream(dev)
+        st = stream if stream is not None else cur
+        if st != cur:
+            out.record_stream(st)       # (the caching allocator: the block is in use on `stream` too)
+        if self._L.h264mi_engine_export_tensor(self._h, n, (C.c_int * n)(*streams), (C.c_int * n)(*slots),
+                                               C.byref(desc), out.data_ptr(),
+                                               planes * desc.ch * desc.cw * out.element_size(), st.cuda_stream) != 0:
+            raise RuntimeError("h264mi_engine_export_tensor failed (stream, slot or window out of range?)")
         return out
 
     @property

@@ -129,6 +129,25 @@ H264SwDecRet H264SwDecNextPictureRGBA(H264SwDecInst decInst, H264SwDecPicture *p
  * backend cannot crop: there is no host fallback. */
 H264SwDecRet H264SwDecNextPictureCropped(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer, u8 *dst,
                                          u32 rgba);
+/* A picture as a planar tensor in device memory (tensor.hip): the window (x, y,
+ * cw, ch -- luma pixels, all even) as (3, ch, cw) R G B planes (the values of
+ * NextPictureRGBA) or one (1, ch, cw) luma plane, contiguous, of uint8 (the
+ * sample) or fp16 / bf16 / fp32: fma((float)sample, scale[p], bias[p]) of plane
+ * p as one fp32 fused multiply-add, then rounded to nearest-even to the 16-bit
+ * types.  GRAY uses scale[0] and bias[0]; uint8 ignores both. */
+enum { H264MI_TENSOR_RGB = 0, H264MI_TENSOR_GRAY = 1 };
+enum { H264MI_TENSOR_U8 = 0, H264MI_TENSOR_F16 = 1, H264MI_TENSOR_BF16 = 2, H264MI_TENSOR_F32 = 3 };
+typedef struct { int x, y, cw, ch, mode, dtype; float scale[3], bias[3]; } h264mi_tensor_desc;
+/* NextPicture, the picture exported to device memory instead of copied to the
+ * host: d_dst (on the decoder's GPU, a multiple of the element size) receives
+ * the tensor of `desc`, ordered on `hip_stream` as h264mi_engine_export_tensor
+ * orders it (NULL: the null stream); pOutput->pOutputPicture = d_dst.  desc ==
+ * NULL: RGB, fp16, scale 1/255, bias 0 over the active SPS's crop window (the
+ * whole picture when croppingFlag == 0); a desc with cw == 0 takes that window
+ * too.  H264SWDEC_PARAM_ERR on a bad desc or d_dst and when the backend cannot
+ * export: there is no host fallback. */
+H264SwDecRet H264SwDecNextPictureTensor(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
+                                        const h264mi_tensor_desc *desc, void *d_dst, void *hip_stream);
 /* Extension (no reference counterpart): where an instance's time went, in
  * seconds since H264SwDecInit -- host parse (NAL extraction, headers, CAVLC /
  * MB layer, DPB, concealment), record upload + kernel launch, waiting for the
@@ -300,6 +319,28 @@ int  h264mi_crop_device_pitch(const void *d_in, void *d_out, int width, int heig
  * engine's launches, crops into a staging buffer, one contiguous copy */
 int  h264mi_engine_read_crop(h264mi_engine *e, int stream, int slot, int x, int y, int cw, int ch, int rgba,
                              uint8_t *dst);
+/* pictures as planar tensors on the device (tensor.hip, h264mi_tensor_desc
+ * above): the npics pictures of width x height pixels (even) that start
+ * in_offsets[k] bytes (a host array; any order, repeats allowed) after d_in,
+ * chroma rows cpitch bytes apart as for h264mi_crop_device_pitch, whose window
+ * rules apply; picture k's (planes, ch, cw) elements at d_out + k * out_stride.
+ * d_out and out_stride are multiples of the element size; where they and the
+ * row bytes are multiples of 16 a lane stores 16 bytes at a time.  Nothing
+ * outside the planes * ch * cw elements of each picture is written.  Device
+ * pointers, asynchronous on `hip_stream`.  -1 on a bad argument, nothing
+ * launched. */
+int  h264mi_tensor_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width, int height,
+                                int cpitch, const h264mi_tensor_desc *desc, void *d_out, size_t out_stride,
+                                void *hip_stream);
+/* the slots (streams[k], slots[k]), k < n, of an engine as tensors in the
+ * caller's memory on the engine's GPU, without any host synchronisation: the
+ * export sees every launch queued on the engine before the call, starts only
+ * after the work already queued on `hip_stream` (NULL: the null stream), and
+ * work queued on `hip_stream` after the call sees the finished tensors; a
+ * later launch that overwrites one of the slots waits for the export.  -1 on
+ * a bad stream, slot or desc, or when d_out is not on the engine's device. */
+int  h264mi_engine_export_tensor(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                 const h264mi_tensor_desc *desc, void *d_out, size_t out_stride, void *hip_stream);
 int  h264mi_engine_sync(h264mi_engine *e);
 /* number of (launch, picture) slots flagged since the last call: residual
  * range errors (reference transform.c:181) or a bounded wait that expired;
