@@ -83,7 +83,14 @@ class TensorDesc(C.Structure):
                [("scale", C.c_float * 3), ("bias", C.c_float * 3)]
 
 
+class TensorResizeDesc(C.Structure):
+    """h264mi_tensor_resize_desc (include/h264mi.h)."""
+    _fields_ = [("t", TensorDesc), ("ow", C.c_int), ("oh", C.c_int), ("filter", C.c_int)]
+
+
 TENSOR_RGB, TENSOR_GRAY = 0, 1
+RESIZE_TRIANGLE = 0
+RESIZE_MAX_DIM = 16384
 TENSOR_U8, TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 0, 1, 2, 3
 
 HEADERS_CB = C.CFUNCTYPE(None, C.c_void_p)
@@ -200,6 +207,14 @@ def mi() -> C.CDLL:
         L.h264mi_engine_export_tensor.restype = i32
         L.H264SwDecNextPictureTensor.argtypes = [vp, C.POINTER(H264SwDecPicture), u32, td, vp, vp]
         L.H264SwDecNextPictureTensor.restype = i32
+    if hasattr(L, "h264mi_tensor_resize_device_pitch"):     # (optional, as above)
+        rd = C.POINTER(TensorResizeDesc)
+        L.h264mi_tensor_resize_device_pitch.argtypes = [vp, C.POINTER(sz), i32, i32, i32, i32, rd, vp, sz, vp]
+        L.h264mi_tensor_resize_device_pitch.restype = i32
+        L.h264mi_engine_export_tensor_resized.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), rd, vp, sz, vp]
+        L.h264mi_engine_export_tensor_resized.restype = i32
+        L.H264SwDecNextPictureTensorResized.argtypes = [vp, C.POINTER(H264SwDecPicture), u32, rd, vp, vp]
+        L.H264SwDecNextPictureTensorResized.restype = i32
     L.h264mi_engine_sync.argtypes = [vp]
     L.h264mi_engine_sync.restype = i32
     L.h264mi_engine_kernel.argtypes = [vp]

@@ -6,6 +6,7 @@
 #include "color.hip"
 #include "crop.hip"
 #include "tensor.hip"
+#include "resize.hip"
 #include "conceal.hip"
 #include <hip/hip_ext.h>
 
@@ -1047,6 +1048,14 @@ static bool tensor_desc_ok(const h264mi_tensor_desc *t, int width, int height)
            t->dtype <= H264MI_TENSOR_F32;
 }
 
+// a resize descriptor h264mi_tensor_resize_device_pitch accepts
+static bool resize_desc_ok(const h264mi_tensor_resize_desc *d, int width, int height)
+{
+    return d && tensor_desc_ok(&d->t, width, height) && d->filter == H264MI_RESIZE_TRIANGLE && d->ow >= 1 &&
+           d->oh >= 1 && d->ow <= RESIZE_MAX_DIM && d->oh <= RESIZE_MAX_DIM && d->t.cw <= RESIZE_MAX_DIM &&
+           d->t.ch <= RESIZE_MAX_DIM && d->t.cw <= 32 * d->ow && d->t.ch <= 32 * d->oh;
+}
+
 // Pictures as planar tensors (tensor.hip): the window desc->(x, y, cw, ch) of
 // the npics pictures of width x height pixels that start in_offsets[k] bytes
 // after d_in (chroma rows cpitch bytes apart), as contiguous (planes, ch, cw)
@@ -1083,16 +1092,51 @@ extern "C" int h264mi_tensor_device_pitch(const void *d_in, const size_t *in_off
     return 0;
 }
 
+// The same pictures resized (resize.hip): the window filtered to desc->oh x
+// desc->ow samples per plane, picture k's (planes, oh, ow) elements at d_out +
+// k * out_stride.  1 <= ow, oh <= 16384 and, per axis, at most 32 source
+// samples per output (64 taps); filter = H264MI_RESIZE_TRIANGLE.  Stateless:
+// the tap tables are made in the kernel.  -1 (nothing launched) on a bad
+// argument.
+extern "C" int h264mi_tensor_resize_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width,
+                                                 int height, int cpitch, const h264mi_tensor_resize_desc *desc,
+                                                 void *d_out, size_t out_stride, void *stream)
+{
+    if (!d_in || !in_offsets || !d_out || width <= 0 || height <= 0 || ((width | height) & 1) || npics < 1 ||
+        cpitch < width / 2 || !resize_desc_ok(desc, width, height))
+        return -1;
+    const h264mi_tensor_desc *t = &desc->t;
+    const size_t es = (size_t)tensor_elem_size(t->dtype);
+    if (((size_t)(uintptr_t)d_out | out_stride) & (es - 1)) return -1;
+    resize_args a;
+    a.t.in = (const uint8_t *)d_in;
+    a.t.width = width; a.t.height = height; a.t.cpitch = cpitch;
+    a.t.x = t->x; a.t.y = t->y; a.t.cw = t->cw; a.t.ch = t->ch;
+    a.t.out_stride = out_stride;
+    a.ow = desc->ow; a.oh = desc->oh;
+    for (int p = 0; p < 3; p++) { a.t.scale[p] = t->scale[p]; a.t.bias[p] = t->bias[p]; }
+    for (int k0 = 0; k0 < npics; k0 += TENSOR_MAX_PICS) {
+        const int n = npics - k0 < TENSOR_MAX_PICS ? npics - k0 : TENSOR_MAX_PICS;
+        for (int k = 0; k < TENSOR_MAX_PICS; k++) a.t.in_off[k] = k < n ? in_offsets[k0 + k] : 0;
+        a.t.out = (uint8_t *)d_out + (size_t)k0 * out_stride;
+        resize_launch(t->mode, t->dtype, n, (hipStream_t)stream, a);
+        HIPCHECK(hipGetLastError());
+    }
+    return 0;
+}
+
 // The slots (streams[k], slots[k]), k < n, as tensors in the caller's device
 // memory, with no host synchronisation: the engine's stream waits for what
 // `stream` (NULL: the null stream; ours is non-blocking, so that too goes
 // through events) holds already -- d_out may have been recycled on it --, the
 // kernel runs on the engine's stream, behind every launch queued so far and
 // ahead of every later one, and `stream` waits for the kernel.
-extern "C" int h264mi_engine_export_tensor(h264mi_engine *e, int n, const int *streams, const int *slots,
-                                           const h264mi_tensor_desc *desc, void *d_out, size_t out_stride, void *stream)
+// (rdesc != NULL: resized, desc = &rdesc->t)
+static int engine_export(h264mi_engine *e, int n, const int *streams, const int *slots, const h264mi_tensor_desc *desc,
+                         const h264mi_tensor_resize_desc *rdesc, void *d_out, size_t out_stride, void *stream)
 {
-    if (!e || n < 1 || !streams || !slots || !d_out || !tensor_desc_ok(desc, e->w * 16, e->h * 16)) return -1;
+    if (!e || n < 1 || !streams || !slots || !d_out) return -1;
+    if (rdesc ? !resize_desc_ok(rdesc, e->w * 16, e->h * 16) : !tensor_desc_ok(desc, e->w * 16, e->h * 16)) return -1;
     for (int k = 0; k < n; k++)
         if (streams[k] < 0 || streams[k] >= e->nstreams || slots[k] < 0 || slots[k] >= e->nslots) return -1;
     const size_t es = (size_t)tensor_elem_size(desc->dtype);
@@ -1108,13 +1152,30 @@ extern "C" int h264mi_engine_export_tensor(h264mi_engine *e, int n, const int *s
         size_t off[TENSOR_MAX_PICS];
         const int m = n - k0 < TENSOR_MAX_PICS ? n - k0 : TENSOR_MAX_PICS;
         for (int k = 0; k < m; k++) off[k] = e->frame_bytes * ((size_t)streams[k0 + k] * e->nslots + slots[k0 + k]);
-        rc = h264mi_tensor_device_pitch(e->d_frames, off, m, e->w * 16, e->h * 16, e->cpitch, desc,
-                                        (uint8_t *)d_out + (size_t)k0 * out_stride, out_stride, e->st);
+        uint8_t *o = (uint8_t *)d_out + (size_t)k0 * out_stride;
+        rc = rdesc ? h264mi_tensor_resize_device_pitch(e->d_frames, off, m, e->w * 16, e->h * 16, e->cpitch, rdesc, o,
+                                                       out_stride, e->st)
+                   : h264mi_tensor_device_pitch(e->d_frames, off, m, e->w * 16, e->h * 16, e->cpitch, desc, o,
+                                                out_stride, e->st);
     }
     // (also after a failed launch: whatever reached our stream stays ordered)
     HIPCHECK(hipEventRecord(e->ev_exp_out, e->st));
     HIPCHECK(hipStreamWaitEvent((hipStream_t)stream, e->ev_exp_out, 0));
     return rc;
+}
+
+extern "C" int h264mi_engine_export_tensor(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                           const h264mi_tensor_desc *desc, void *d_out, size_t out_stride, void *stream)
+{
+    return engine_export(e, n, streams, slots, desc, NULL, d_out, out_stride, stream);
+}
+
+// the same, resized (h264mi_tensor_resize_device_pitch); the same pair of events
+extern "C" int h264mi_engine_export_tensor_resized(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                                   const h264mi_tensor_resize_desc *desc, void *d_out,
+                                                   size_t out_stride, void *stream)
+{
+    return engine_export(e, n, streams, slots, desc ? &desc->t : NULL, desc, d_out, out_stride, stream);
 }
 
 extern "C" void *h264mi_engine_frame_ptr(h264mi_engine *e, int stream, int slot)

@@ -1,0 +1,265 @@
+// Resized tensor export: the window of tensor.hip, filtered to
+// (oh, ow) samples per plane by an antialiased triangle filter (bilinear with
+// the support stretched by the downscale ratio) in integer arithmetic, then
+// tensor.hip's elements: resized tensor == convert(resize(samples(window))).
+//
+// One axis, n source samples -> m outputs: R = 2 max(m, n); output j has
+// C = (2 j + 1) n - m (its centre (j + 0.5) n / m - 0.5 in units of 1 / (2 m));
+// source sample k, 0 <= k < n, weighs w_k = R - |2 m k - C| where that is
+// positive (taps outside the window are dropped, the rest are contiguous, at
+// most 64 with n <= 32 m); q_k = (w_k * 16384 + W / 2) / W with W = sum w_k, and
+// 16384 - sum q_k goes to the first tap of largest weight.  Two passes:
+//   t   = (sum_k qx_k * s[row][k] + 128) >> 8          (6 fractional bits, 16 bits)
+//   out = (sum_l qy_l * t[l] + (1 << 19)) >> 20        (<= 255, no clamp)
+//
+// A workgroup of 256 threads makes one RESIZE_TW x RESIZE_TH tile of one
+// picture's output:
+//   taps      lanes 0..47 of wave 0 derive first tap, count and the q of one
+//             tile column or row each (32-bit unsigned divisions) into LDS,
+//             k-major, so that lanes over columns / rows read without conflicts;
+//   per chunk of 2..16 source rows (as many as the tile's source columns leave
+//   room for in the staging buffer):
+//   stage     the chunk's columns, converted once per source pixel (tensor.hip's
+//             loads, color.hip's rgba_group_px), one dword per pixel, rows an
+//             odd number of dwords apart; at most 3 items per thread, their
+//             loads issued together;
+//   horizontal  one lane per (source row, output column), rows fastest: lanes
+//             of a half-wave read different rows (odd pitch: different banks)
+//             of the same few columns; all planes of a pixel from one dword,
+//             four taps per iteration (the tables are zero-padded to that);
+//             t as uint16, [plane][column][row], columns 9 dwords apart;
+//   vertical  one lane per (plane, output row, output column), 6 (RGB) or 2
+//             (GRAY) per thread, adds the chunk's rows of its taps to a 32-bit
+//             accumulator in a register;
+//   at the end: round, tensor_elem<DT>, one non-temporal store per element
+//   (rows are short and start on any element).
+
+#define RESIZE_TW 32                // output columns of a tile
+#define RESIZE_TH 16                // output rows of a tile
+#define RESIZE_THREADS 256
+#define RESIZE_MAX_TAPS 64          // n <= 32 m
+#define RESIZE_ROWS 16              // source rows per chunk, at most
+#define RESIZE_STAGE_DW 6144        // staging buffer; 2 rows of the widest tile (32 : 1) are 2130 dwords
+#define RESIZE_TPITCH (RESIZE_ROWS + 2)     // uint16 per column of t: 9 dwords
+#define RESIZE_MAX_DIM 16384        // ow, oh (and cw, ch): w * 16384 <= 2^29
+
+struct resize_args {
+    tensor_args t;
+    int ow, oh;
+};
+
+// the taps of output j of an axis n -> m: q[k * qpitch], k < count, for source
+// samples first + k, and zeros up to the next multiple of 4 taps.  Every
+// intermediate fits 32 bits for m, n <= 16384.
+__device__ __forceinline__ void resize_taps(uint32_t n, uint32_t m, uint32_t j, uint16_t *q, int qpitch, int &first,
+                                            int &count)
+{
+    const uint32_t R = 2u * (m > n ? m : n), m2 = 2u * m;
+    const int32_t C = (int32_t)((2u * j + 1u) * n) - (int32_t)m;
+    // w_k > 0: C - R < 2 m k < C + R
+    const int32_t lo = C - (int32_t)R;
+    const uint32_t k0 = lo < 0 ? 0u : (uint32_t)lo / m2 + 1u;
+    uint32_t k1 = ((uint32_t)(C + (int32_t)R) - 1u) / m2;
+    k1 = k1 < n - 1u ? k1 : n - 1u;
+    uint32_t W = 0, wmax = 0, kmax = 0;
+    for (uint32_t k = k0; k <= k1; k++) {
+        const int32_t d = (int32_t)(m2 * k) - C;
+        const uint32_t w = R - (uint32_t)(d < 0 ? -d : d);
+        W += w;
+        if (w > wmax) { wmax = w; kmax = k - k0; }
+    }
+    int32_t rest = 16384;
+    for (uint32_t k = k0; k <= k1; k++) {
+        const int32_t d = (int32_t)(m2 * k) - C;
+        const uint32_t w = R - (uint32_t)(d < 0 ? -d : d);
+        const uint32_t qk = (w * 16384u + (W >> 1)) / W;
+        q[(k - k0) * qpitch] = (uint16_t)qk;
+        rest -= (int32_t)qk;
+    }
+    first = (int)k0;
+    count = (int)k1 - (int)k0 + 1;
+    if (count > 0) q[kmax * qpitch] = (uint16_t)((int32_t)q[kmax * qpitch] + rest);
+    // (the horizontal pass takes its taps four at a time)
+    for (int k = count > 0 ? count : 0; k < ((count + 3) & ~3); k++) q[k * qpitch] = 0;
+}
+
+// Stage items tid + 256 u, u < NIT, of a chunk: the loads of all NIT items are
+// issued before the first conversion (one straight-line block: a thread past
+// the last item repeats it and stores nothing).  The window's last group can
+// be 2 columns wide: its luma dword is still read whole (the bytes behind a
+// luma row are the next row's or the chroma planes'), its one chroma sample is
+// the upper byte of the pair that ends with it (the byte in front of a chroma
+// plane is the plane's in front of it); columns 2 and 3 of that group hold
+// garbage no tap reads.
+template <int MODE, int NIT>
+__device__ __forceinline__ void resize_stage(const tensor_args &a, const uint8_t *Y, const uint8_t *U, const uint8_t *V,
+                                             uint32_t *stage, int pitch, int ng, int nit, int xs0, int r0, int tid)
+{
+    uint32_t y0[NIT][1], y1[NIT][1], u[NIT], v[NIT];
+    int so[NIT];
+#pragma unroll
+    for (int i = 0; i < NIT; i++) {
+        const int it = tid + RESIZE_THREADS * i < nit ? tid + RESIZE_THREADS * i : nit - 1;
+        const int pr = it / ng, g = it - pr * ng;
+        const int c = xs0 + 4 * g, ry = r0 + 2 * pr;
+        const uint8_t *sy = Y + (size_t)ry * a.width + c;
+        tensor_load<1>(sy, y0[i]);
+        tensor_load<1>(sy + a.width, y1[i]);
+        if (MODE == TENSOR_RGB) {
+            const int part = c + 4 <= a.cw ? 0 : 1;
+            const size_t co = (size_t)(ry >> 1) * a.cpitch + (c >> 1) - part;
+            u[i] = crop_load2(U + co) >> (8 * part);
+            v[i] = crop_load2(V + co) >> (8 * part);
+        }
+        so[i] = (2 * pr) * pitch + 4 * g;
+    }
+#pragma unroll
+    for (int i = 0; i < NIT; i++) {
+        uint32_t o0[4], o1[4];
+        if (MODE == TENSOR_RGB) {
+            rgba_group_px(y0[i][0], y1[i][0], u[i], v[i], o0, o1);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                o0[k] = (y0[i][0] >> (8 * k)) & 255u;
+                o1[k] = (y1[i][0] >> (8 * k)) & 255u;
+            }
+        }
+        if (tid + RESIZE_THREADS * i < nit) {
+            uint32_t *s0 = stage + so[i], *s1 = s0 + pitch;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                s0[k] = o0[k];
+                s1[k] = o1[k];
+            }
+        }
+    }
+}
+
+// grid: (tiles of RESIZE_TW x RESIZE_TH outputs in raster order, pictures of
+// this launch), 256 threads
+template <int MODE, int DT>
+__global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const resize_args ra)
+{
+    constexpr int ES = tensor_elem_size(DT);
+    constexpr int NP = MODE == TENSOR_RGB ? 3 : 1;
+    constexpr int NE = NP * RESIZE_TW * RESIZE_TH / RESIZE_THREADS;     // outputs per thread
+    static_assert(RESIZE_TW == 32 && RESIZE_TH * RESIZE_TW == 2 * RESIZE_THREADS, "item -> (plane, row, column) below");
+    __shared__ uint32_t stage[RESIZE_STAGE_DW + 4];         // (+ 4: the zero-weight taps behind the last row's last)
+    __shared__ uint16_t qx[RESIZE_MAX_TAPS * RESIZE_TW], qy[RESIZE_MAX_TAPS * RESIZE_TH];
+    __shared__ uint16_t tb[NP * RESIZE_TW * RESIZE_TPITCH];
+    __shared__ int fx[RESIZE_TW], cx[RESIZE_TW], fy[RESIZE_TH], cy[RESIZE_TH];
+    const tensor_args &a = ra.t;
+    const int tid = (int)threadIdx.x;
+    const int width = a.width, cpitch = a.cpitch, cw = a.cw, ch = a.ch, ow = ra.ow, oh = ra.oh;
+    const int ntx = (ow + RESIZE_TW - 1) / RESIZE_TW;
+    const int ty = (int)blockIdx.x / ntx, tx = (int)blockIdx.x - ty * ntx;
+    const int ox0 = tx * RESIZE_TW, oy0 = ty * RESIZE_TH;
+    const int nx = ow - ox0 < RESIZE_TW ? ow - ox0 : RESIZE_TW, ny = oh - oy0 < RESIZE_TH ? oh - oy0 : RESIZE_TH;
+
+    if (tid < RESIZE_TW + RESIZE_TH) {
+        const bool isx = tid < RESIZE_TW;
+        const int l = isx ? tid : tid - RESIZE_TW;
+        int f = 0, c = 0;
+        if (l < (isx ? nx : ny))
+            resize_taps((uint32_t)(isx ? cw : ch), (uint32_t)(isx ? ow : oh), (uint32_t)((isx ? ox0 : oy0) + l),
+                        (isx ? qx : qy) + l, isx ? RESIZE_TW : RESIZE_TH, f, c);
+        (isx ? fx : fy)[l] = f;
+        (isx ? cx : cy)[l] = c;
+    }
+    __syncthreads();
+
+    // the tile's source columns [xs0, xs0 + segw) (4-column groups of the
+    // window) and rows [ys0, ye) (row pairs): first taps and tap ends grow with
+    // the output index
+    const int xs0 = fx[0] & ~3, segw = (fx[nx - 1] + cx[nx - 1] - xs0 + 3) & ~3, pitch = segw | 1, ng = segw >> 2;
+    const int ys0 = fy[0] & ~1, ye = fy[ny - 1] + cy[ny - 1];
+    int lrc = 4;                                    // log2 of the chunk's rows
+    while (lrc > 1 && (pitch << lrc) > RESIZE_STAGE_DW) lrc--;
+    if ((pitch << lrc) > RESIZE_STAGE_DW) return;   // (not with n <= 32 m)
+    const int rc = 1 << lrc;
+
+    const uint8_t *Y = a.in + a.in_off[blockIdx.y];
+    const uint8_t *U = Y + (size_t)width * a.height + (size_t)(a.y >> 1) * cpitch + (a.x >> 1);
+    const uint8_t *V = U + (size_t)cpitch * (a.height >> 1);
+    Y += (size_t)a.y * width + a.x;
+
+    uint32_t acc[NE];
+#pragma unroll
+    for (int e = 0; e < NE; e++) acc[e] = 0;
+
+    for (int r0 = ys0; r0 < ye; r0 += rc) {
+        const int nr = ye - r0 < rc ? ye - r0 : rc;         // source rows of this chunk
+        // stage: (row pair, 4-column group) items, groups fastest, at most 3 per thread
+        const int nit = ((nr + 1) >> 1) * ng;
+        if (nit <= RESIZE_THREADS) resize_stage<MODE, 1>(a, Y, U, V, stage, pitch, ng, nit, xs0, r0, tid);
+        else if (nit <= 2 * RESIZE_THREADS) resize_stage<MODE, 2>(a, Y, U, V, stage, pitch, ng, nit, xs0, r0, tid);
+        else resize_stage<MODE, 3>(a, Y, U, V, stage, pitch, ng, nit, xs0, r0, tid);
+        __syncthreads();
+        // horizontal: (source row, output column) items, rows fastest
+        for (int it = tid; it < (RESIZE_TW << lrc); it += RESIZE_THREADS) {
+            const int r = it & (rc - 1), j = it >> lrc;
+            if (r >= nr || j >= nx) continue;
+            const uint32_t *s = stage + r * pitch + (fx[j] - xs0);
+            const int n = cx[j];
+            uint32_t h[NP];
+#pragma unroll
+            for (int p = 0; p < NP; p++) h[p] = 0;
+            // four taps at a time, their LDS reads in flight together; behind
+            // the last tap: weight 0 times whatever the buffer holds
+            for (int k = 0; k < n; k += 4) {
+                uint32_t px[4], q[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    px[u] = s[k + u];
+                    q[u] = qx[(k + u) * RESIZE_TW + j];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++)
+#pragma unroll
+                    for (int p = 0; p < NP; p++) h[p] += q[u] * ((px[u] >> (8 * p)) & 255u);
+            }
+#pragma unroll
+            for (int p = 0; p < NP; p++) tb[(p * RESIZE_TW + j) * RESIZE_TPITCH + r] = (uint16_t)((h[p] + 128u) >> 8);
+        }
+        __syncthreads();
+        // vertical: item tid + 256 e = (plane e >> 1, row (tid >> 5) + 8 (e & 1), column tid & 31):
+        // the chunk's rows among the item's taps, each tap once over the chunks
+#pragma unroll
+        for (int e = 0; e < NE; e++) {
+            const int p = e >> 1, i = (tid >> 5) + 8 * (e & 1), j = tid & 31;
+            if (i >= ny || j >= nx) continue;
+            const int f = fy[i];
+            const int lo = f > r0 ? f : r0, hi = f + cy[i] < r0 + nr ? f + cy[i] : r0 + nr;
+            const uint16_t *t = tb + (p * RESIZE_TW + j) * RESIZE_TPITCH;
+            for (int row = lo; row < hi; row++) acc[e] += (uint32_t)qy[(row - f) * RESIZE_TH + i] * t[row - r0];
+        }
+        // (the next chunk's stage writes only `stage`; its barrier orders this
+        // chunk's reads of tb before the next horizontal pass)
+    }
+
+    uint8_t *O = a.out + blockIdx.y * a.out_stride;
+#pragma unroll
+    for (int e = 0; e < NE; e++) {
+        const int p = e >> 1, i = (tid >> 5) + 8 * (e & 1), j = tid & 31;
+        if (i >= ny || j >= nx) continue;
+        const uint32_t v = tensor_elem<DT>((acc[e] + (1u << 19)) >> 20, a.scale[p], a.bias[p]);
+        const size_t o = ((size_t)p * oh + (size_t)(oy0 + i)) * ow + (size_t)(ox0 + j);
+        if (ES == 1) __builtin_nontemporal_store((uint8_t)v, O + o);
+        else if (ES == 2) __builtin_nontemporal_store((uint16_t)v, (uint16_t *)O + o);
+        else __builtin_nontemporal_store(v, (uint32_t *)O + o);
+    }
+}
+
+static void resize_launch(int mode, int dt, int npics, hipStream_t st, const resize_args &a)
+{
+    const unsigned ntx = (unsigned)(a.ow + RESIZE_TW - 1) / RESIZE_TW, nty = (unsigned)(a.oh + RESIZE_TH - 1) / RESIZE_TH;
+    const dim3 grid(ntx * nty, npics), block(RESIZE_THREADS);
+#define RESIZE_CASE(M, D) \
+    if (mode == M && dt == D) hipLaunchKernelGGL((k_tensor_resize<M, D>), grid, block, 0, st, a);
+    RESIZE_CASE(TENSOR_RGB, TENSOR_U8) RESIZE_CASE(TENSOR_RGB, TENSOR_F16)
+    RESIZE_CASE(TENSOR_RGB, TENSOR_BF16) RESIZE_CASE(TENSOR_RGB, TENSOR_F32)
+    RESIZE_CASE(TENSOR_GRAY, TENSOR_U8) RESIZE_CASE(TENSOR_GRAY, TENSOR_F16)
+    RESIZE_CASE(TENSOR_GRAY, TENSOR_BF16) RESIZE_CASE(TENSOR_GRAY, TENSOR_F32)
+#undef RESIZE_CASE
+}

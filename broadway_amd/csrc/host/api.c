@@ -299,6 +299,47 @@ H264SwDecRet H264SwDecNextPictureTensor(H264SwDecInst decInst, H264SwDecPicture 
     return H264SWDEC_PIC_RDY;
 }
 
+/* NextPictureTensor with the tensor resized on the GPU (include/h264mi.h);
+ * desc->t.cw == 0: the active SPS's crop window.  Everything the export can
+ * refuse is checked before a picture is taken from the DPB. */
+H264SwDecRet H264SwDecNextPictureTensorResized(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
+                                               const h264mi_tensor_resize_desc *desc, void *d_dst, void *hip_stream)
+{
+    if (decInst == NULL || pOutput == NULL || d_dst == NULL || desc == NULL) return H264SWDEC_PARAM_ERR;
+    DecContainer *c = (DecContainer *)decInst;
+    if (!c->dec.be.export_tensor_resized) return H264SWDEC_PARAM_ERR;
+    h264mi_tensor_resize_desc r = *desc;
+    h264mi_tensor_desc *t = &r.t;
+    if ((t->mode != H264MI_TENSOR_RGB && t->mode != H264MI_TENSOR_GRAY) || t->dtype < H264MI_TENSOR_U8 ||
+        t->dtype > H264MI_TENSOR_F32 || r.filter != H264MI_RESIZE_TRIANGLE || r.ow < 1 || r.oh < 1 || r.ow > 16384 ||
+        r.oh > 16384)
+        return H264SWDEC_PARAM_ERR;
+    const size_t es = t->dtype == H264MI_TENSOR_U8 ? 1 : t->dtype == H264MI_TENSOR_F32 ? 4 : 2;
+    if ((size_t)(uintptr_t)d_dst & (es - 1)) return H264SWDEC_PARAM_ERR;
+    if (flushBuffer) h264dec_flush(&c->dec);
+    const Sps *s = h264dec_active_sps(&c->dec);
+    if (!s) return H264SWDEC_OK;                    /* no headers yet: no picture either */
+    const int width = 16 * (int)s->w_mbs, height = 16 * (int)s->h_mbs;
+    if (t->cw == 0) {
+        const int cl = s->crop ? 2 * (int)s->crop_l : 0, ct = s->crop ? 2 * (int)s->crop_t : 0;
+        const int cr = s->crop ? 2 * (int)s->crop_r : 0, cb = s->crop ? 2 * (int)s->crop_b : 0;
+        t->x = cl; t->y = ct; t->cw = width - cl - cr; t->ch = height - ct - cb;
+    }
+    if (t->x < 0 || t->y < 0 || t->cw <= 0 || t->ch <= 0 || ((t->x | t->y | t->cw | t->ch) & 1) ||
+        t->cw > width - t->x || t->ch > height - t->y || t->cw > 32 * r.ow || t->ch > 32 * r.oh)
+        return H264SWDEC_PARAM_ERR;
+    uint32_t id, idr, em;
+    int failed = 0;
+    const uint8_t *pic = h264dec_next_output_tensor_resized(&c->dec, &id, &idr, &em, &r, d_dst, hip_stream, &failed);
+    if (failed) return H264SWDEC_PARAM_ERR;         /* (d_dst not on the decoder's GPU) */
+    if (!pic) return H264SWDEC_OK;
+    pOutput->pOutputPicture = (u32 *)(void *)pic;
+    pOutput->picId = id;
+    pOutput->isIdrPicture = idr;
+    pOutput->nbrOfErrMBs = em;
+    return H264SWDEC_PIC_RDY;
+}
+
 H264SwDecRet H264SwDecGetTiming(H264SwDecInst decInst, double *parse_s, double *submit_s, double *wait_s,
                                 double *copy_s, u32 *pictures)
 {

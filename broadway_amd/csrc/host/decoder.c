@@ -603,11 +603,12 @@ const uint8_t *h264dec_next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_id
     return h264dec_next_output_rgba(d, pic_id, is_idr, err_mbs, NULL);
 }
 
-/* a tensor export (h264dec_next_output_tensor); failed: the backend refused it */
+/* a tensor export (h264dec_next_output_tensor, resized: _tensor_resized);
+ * failed: the backend refused it */
 typedef struct TensorOut {
     const void *desc;
     void *d_dst, *hip_stream;
-    int failed;
+    int failed, resized;
 } TensorOut;
 
 /* rgba != NULL: the picture as RGBA (w*h*4 bytes) into rgba, converted by
@@ -631,7 +632,16 @@ const uint8_t *h264dec_next_output_crop(H264Dec *d, uint32_t *pic_id, uint32_t *
 const uint8_t *h264dec_next_output_tensor(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
                                           const void *desc, void *d_dst, void *hip_stream, int *failed)
 {
-    TensorOut t = {desc, d_dst, hip_stream, 0};
+    TensorOut t = {desc, d_dst, hip_stream, 0, 0};
+    const uint8_t *r = desc && d_dst ? next_output(d, pic_id, is_idr, err_mbs, NULL, NULL, 0, &t) : NULL;
+    if (failed) *failed = t.failed;
+    return r;
+}
+
+const uint8_t *h264dec_next_output_tensor_resized(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
+                                                  const void *desc, void *d_dst, void *hip_stream, int *failed)
+{
+    TensorOut t = {desc, d_dst, hip_stream, 0, 1};
     const uint8_t *r = desc && d_dst ? next_output(d, pic_id, is_idr, err_mbs, NULL, NULL, 0, &t) : NULL;
     if (failed) *failed = t.failed;
     return r;
@@ -644,7 +654,7 @@ static const uint8_t *next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr
                                   uint8_t *crop, int crop_rgba, TensorOut *tensor)
 {
     if (rgba && !d->be.read_rgba) return NULL;
-    if (tensor && !d->be.export_tensor) return NULL;
+    if (tensor && !(tensor->resized ? d->be.export_tensor_resized : d->be.export_tensor)) return NULL;
     const Sps *sps = crop ? h264dec_active_sps(d) : NULL;
     if (crop && (!d->be.read_crop || !sps)) return NULL;
     const DpbOut *o = dpb_next_output(&d->dpb);
@@ -664,7 +674,8 @@ static const uint8_t *next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr
     const double t1 = h264dec_now();
     int rr;
     if (tensor) {
-        rr = d->be.export_tensor(d->be.ctx, o->slot, tensor->desc, tensor->d_dst, tensor->hip_stream);
+        rr = (tensor->resized ? d->be.export_tensor_resized : d->be.export_tensor)(d->be.ctx, o->slot, tensor->desc,
+                                                                                    tensor->d_dst, tensor->hip_stream);
         tensor->failed = rr < 0;
     } else if (crop) {
         const int cl = sps->crop ? 2 * sps->crop_l : 0, ct = sps->crop ? 2 * sps->crop_t : 0;

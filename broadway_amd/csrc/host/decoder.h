@@ -51,6 +51,8 @@ typedef struct H264Backend {
      * include/h264mi.h); nothing reaches the host; same returns; NULL when
      * the backend cannot export */
     int  (*export_tensor)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
+    /* the same, resized on the GPU (desc: a checked h264mi_tensor_resize_desc) */
+    int  (*export_tensor_resized)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
     /* optional: host memory for the output frames (pinned by the HIP
      * backend, so each picture's D2H copy runs at DMA speed); NULL: malloc */
     void *(*host_alloc)(void *ctx, size_t bytes);
@@ -161,6 +163,10 @@ const uint8_t *h264dec_next_output_crop(H264Dec *d, uint32_t *pic_id, uint32_t *
  * from the DPB failed */
 const uint8_t *h264dec_next_output_tensor(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
                                           const void *desc, void *d_dst, void *hip_stream, int *failed);
+/* the same through the backend's export_tensor_resized (desc: an
+ * h264mi_tensor_resize_desc) */
+const uint8_t *h264dec_next_output_tensor_resized(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
+                                                  const void *desc, void *d_dst, void *hip_stream, int *failed);
 int  h264dec_valid_param_sets(const H264Dec *d);
 /* conceal the current picture's missing MBs (conceal.c); returns their
  * number or -1 */

@@ -528,20 +528,38 @@ extern "C" int h264mi_engine_export_tensor(h264mi_engine *e, int n, const int *s
                                            const h264mi_tensor_desc *desc, void *d_out, size_t out_stride,
                                            void *hip_stream) __attribute__((weak));
 
+extern "C" int h264mi_engine_export_tensor_resized(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                                   const h264mi_tensor_resize_desc *desc, void *d_out,
+                                                   size_t out_stride, void *hip_stream) __attribute__((weak));
+
 // nothing waits here: the decoder synced before (the slot's flags are on the
-// host), and the export orders itself on the engine's and the caller's stream
-static int hb_export_tensor(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
+// host), and the export orders itself on the engine's and the caller's stream;
+// resized: desc is an h264mi_tensor_resize_desc
+static int hb_export(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream, bool resized)
 {
     HipBackendCtx *c = (HipBackendCtx *)vctx;
     if (slot < 0 || slot >= c->nslots) return -1;
     const int lane = c->lane;
     std::unique_lock<std::mutex> l;
     if (c->sh) l = std::unique_lock<std::mutex>(c->sh->mu);
-    if (h264mi_engine_export_tensor(c->e, 1, &lane, &slot, (const h264mi_tensor_desc *)desc, d_dst, 0, hip_stream))
+    if (resized ? h264mi_engine_export_tensor_resized(c->e, 1, &lane, &slot, (const h264mi_tensor_resize_desc *)desc,
+                                                      d_dst, 0, hip_stream)
+                : h264mi_engine_export_tensor(c->e, 1, &lane, &slot, (const h264mi_tensor_desc *)desc, d_dst, 0,
+                                              hip_stream))
         return -1;
     if (c->sh) HIPCHECK(hipEventRecord(c->ev_last, engine_stream(c->e)));
     c->enq++;
     return slot_flagged(c, slot, false);
+}
+
+static int hb_export_tensor(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
+{
+    return hb_export(vctx, slot, desc, d_dst, hip_stream, false);
+}
+
+static int hb_export_tensor_resized(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
+{
+    return hb_export(vctx, slot, desc, d_dst, hip_stream, true);
 }
 
 // Pinned host blocks (decoder output frames) kept after free for the next
@@ -675,6 +693,7 @@ extern "C" H264Backend h264mi_hip_backend_create(int device)
     be.read_rgba = hb_read_rgba;
     be.read_crop = h264mi_engine_read_crop && h264mi_crop_device_pitch ? hb_read_crop : NULL;
     be.export_tensor = h264mi_engine_export_tensor ? hb_export_tensor : NULL;
+    be.export_tensor_resized = h264mi_engine_export_tensor_resized ? hb_export_tensor_resized : NULL;
     be.host_alloc = hb_host_alloc;
     be.host_free = hb_host_free;
     be.records_wait = hb_records_wait;

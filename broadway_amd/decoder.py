@@ -28,13 +28,17 @@ of the wasm glue of Decoder/src/Decoder.c:44-162:
   delivers the whole picture.
 
 * ``tensor: true`` or ``tensor: {"dtype": ..., "mode": ..., "mean": ...,
-  "std": ..., "scale": ..., "bias": ...}`` (an extension for device consumers;
-  needs torch, imported only on this path): nothing is copied to the host.
+  "std": ..., "scale": ..., "bias": ..., "size": (oh, ow)}`` (an extension for
+  device consumers; needs torch, imported only on this path): nothing is
+  copied to the host.
   ``onPictureDecoded(tensor, width, height, infos)`` receives a new
   ``(planes, height, width)`` torch tensor on the decoder's GPU, cropped to the
   SPS crop window, built by ``H264SwDecNextPictureTensor`` on torch's current
   stream -- the arguments of ``Engine.to_tensor`` (default: RGB, float16,
-  scale 1/255).  It combines with neither ``rgb`` nor ``crop`` (ValueError).
+  scale 1/255).  With ``size`` the crop window is resized on the GPU
+  (``H264SwDecNextPictureTensorResized``): the tensor is ``(planes, oh, ow)``
+  and the callback's width and height are ``ow`` and ``oh``.  It combines with
+  neither ``rgb`` nor ``crop`` (ValueError).
 
 Unlike the reference module (a single global instance) every ``Decoder`` has
 its own H264SwDec instance, so several streams can be decoded side by side.
@@ -67,15 +71,17 @@ class Decoder:
         self._rgb = bool(self.options.get("rgb"))
         self._crop = bool(self.options.get("crop"))
         self._tensor = self.options.get("tensor") or None
+        self._resized = False
         if self._tensor is not None:
             if self._rgb or self._crop:
                 raise ValueError("tensor: not combinable with rgb or crop (mode='rgb' and the SPS window are part of it)")
             opts = {} if self._tensor is True else dict(self._tensor)
-            unknown = set(opts) - {"dtype", "mode", "mean", "std", "scale", "bias"}
+            unknown = set(opts) - {"dtype", "mode", "mean", "std", "scale", "bias", "size"}
             if unknown:
                 raise ValueError(f"tensor: unknown keys {sorted(unknown)}")
             from .engine import tensor_desc          # (imports torch)
             self._tensor = tensor_desc(None, **opts)
+            self._resized = opts.get("size") is not None
             self._device = int(os.environ.get("H264MI_DEVICE") or 0)     # the GPU H264SwDecInit takes (api.c)
         self._L = _lib.mi()
         inst = C.c_void_p()
@@ -136,8 +142,9 @@ class Decoder:
                     dev = torch.device("cuda", self._device)
                     with torch.cuda.device(dev):
                         out = torch.empty((planes, h, w), dtype=dtype, device=dev)
-                    ret = L.H264SwDecNextPictureTensor(self._inst, C.byref(self._pic), 0, C.byref(desc),
-                                                       out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+                    nxt = L.H264SwDecNextPictureTensorResized if self._resized else L.H264SwDecNextPictureTensor
+                    ret = nxt(self._inst, C.byref(self._pic), 0, C.byref(desc), out.data_ptr(),
+                              torch.cuda.current_stream(dev).cuda_stream)
                     if ret == _lib.H264SWDEC_PARAM_ERR:
                         raise RuntimeError("tensor: the backend cannot export device tensors "
                                            "(there is no host fallback)")
@@ -176,6 +183,8 @@ class Decoder:
     def _out_size(self):
         """(width, height) of the pictures handed to onPictureDecoded."""
         i = self._info
+        if self._tensor is not None and self._resized:
+            return self._tensor[0].ow, self._tensor[0].oh
         if (self._crop or self._tensor is not None) and i.croppingFlag:
             return i.cropParams.cropOutWidth, i.cropParams.cropOutHeight
         return i.picWidth, i.picHeight

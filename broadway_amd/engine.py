@@ -33,11 +33,25 @@ def tensor_affine(mean: Sequence[float], std: Sequence[float]) -> Tuple[Tuple[fl
     return scale, bias
 
 
-def tensor_desc(window, mode="rgb", dtype=None, scale=None, bias=None, mean=None, std=None):
+def tensor_desc(window, mode="rgb", dtype=None, scale=None, bias=None, mean=None, std=None, size=None):
     """(``_lib.TensorDesc``, planes, torch dtype) of a tensor export
     (Engine.to_tensor, Decoder's ``tensor`` option); window = (x, y, cw, ch),
-    or None for the decoder's SPS crop window (cw = 0 in the descriptor)."""
+    or None for the decoder's SPS crop window (cw = 0 in the descriptor).
+    With ``size`` = (oh, ow), each 1..16384, the descriptor is a
+    ``_lib.TensorResizeDesc`` of the resized export (its ``t`` is the one
+    above)."""
     import torch
+    if size is not None:
+        try:
+            oh, ow = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError(f"size {size!r}: (oh, ow)") from None
+        if not (1 <= oh <= _lib.RESIZE_MAX_DIM and 1 <= ow <= _lib.RESIZE_MAX_DIM):
+            raise ValueError(f"size {size!r}: oh and ow are 1..{_lib.RESIZE_MAX_DIM}")
+        t, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std)
+        d = _lib.TensorResizeDesc()
+        d.t, d.ow, d.oh, d.filter = t, ow, oh, _lib.RESIZE_TRIANGLE
+        return d, planes, dtype
     dtype = torch.float16 if dtype is None else dtype
     dts = {torch.uint8: _lib.TENSOR_U8, torch.float16: _lib.TENSOR_F16, torch.bfloat16: _lib.TENSOR_BF16,
            torch.float32: _lib.TENSOR_F32}
@@ -240,7 +254,7 @@ class Engine:
         return out
 
     def to_tensor(self, streams: Sequence[int], slots: Sequence[int], window=None, mode: str = "rgb", dtype=None,
-                  scale=None, bias=None, mean=None, std=None, out=None, stream=None):
+                  scale=None, bias=None, mean=None, std=None, out=None, stream=None, size=None):
         """The slots (streams[k], slots[k]) as one ``(n, planes, ch, cw)``
         torch tensor on ``cuda:{self.device}``, built on the GPU and never
         copied to the host: planes R, G, B (``mode="rgb"``, the values of
@@ -250,7 +264,10 @@ class Engine:
         ``fma(c, scale[p], bias[p])`` in fp32, rounded once more to the 16-bit
         types; scale and bias are scalars or per-plane triples (default
         1 / 255 and 0), or come from ``mean`` / ``std`` (``tensor_affine``);
-        uint8 ignores them.
+        uint8 ignores them.  ``size`` = (oh, ow): the window's 8-bit samples
+        resized on the GPU before that conversion (antialiased triangle
+        filter in integer arithmetic; a window at most 32 times
+        the output on each axis) -- the result is ``(n, planes, oh, ow)``.
 
         The export is ordered on ``stream`` (a torch.cuda.Stream; default:
         torch's current stream of the device): it starts after the work queued
@@ -266,8 +283,8 @@ class Engine:
             raise ValueError("streams and slots name the same, non-zero number of pictures")
         if window is None:
             window = (0, 0, self.w_mbs * 16, self.h_mbs * 16)
-        desc, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std)
-        shape = (n, planes, desc.ch, desc.cw)
+        desc, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std, size)
+        shape = (n, planes, desc.ch, desc.cw) if size is None else (n, planes, desc.oh, desc.ow)
         dev = torch.device("cuda", self.device)
         if out is None:
             if min(shape) < 1:
@@ -281,10 +298,10 @@ class Engine:
         st = stream if stream is not None else cur
         if st != cur:
             out.record_stream(st)       # (the caching allocator: the block is in use on `stream` too)
-        if self._L.h264mi_engine_export_tensor(self._h, n, (C.c_int * n)(*streams), (C.c_int * n)(*slots),
-                                               C.byref(desc), out.data_ptr(),
-                                               planes * desc.ch * desc.cw * out.element_size(), st.cuda_stream) != 0:
-            raise RuntimeError("h264mi_engine_export_tensor failed (stream, slot or window out of range?)")
+        export = self._L.h264mi_engine_export_tensor if size is None else self._L.h264mi_engine_export_tensor_resized
+        if export(self._h, n, (C.c_int * n)(*streams), (C.c_int * n)(*slots), C.byref(desc), out.data_ptr(),
+                  planes * shape[2] * shape[3] * out.element_size(), st.cuda_stream) != 0:
+            raise RuntimeError(f"{export.__name__} failed (stream, slot, window or size out of range?)")
         return out
 
     @property

@@ -148,6 +148,20 @@ typedef struct { int x, y, cw, ch, mode, dtype; float scale[3], bias[3]; } h264m
  * export: there is no host fallback. */
 H264SwDecRet H264SwDecNextPictureTensor(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
                                         const h264mi_tensor_desc *desc, void *d_dst, void *hip_stream);
+/* The tensor resized on the GPU (resize.hip): the window of `t`,
+ * as the uint8 samples above, filtered per plane to oh x ow samples (1 ..
+ * 16384 each, odd allowed) by an antialiased triangle filter in integer
+ * arithmetic -- bilinear with half-pixel centres when upscaling, the triangle
+ * widened by the ratio when downscaling, at most 32 source samples per output
+ * and axis --, then converted as above: (3 | 1, oh, ow) elements.  With (oh,
+ * ow) == (ch, cw) the bytes are those of the unresized tensor.  `filter` is
+ * H264MI_RESIZE_TRIANGLE; other values are refused. */
+enum { H264MI_RESIZE_TRIANGLE = 0 };
+typedef struct { h264mi_tensor_desc t; int ow, oh, filter; } h264mi_tensor_resize_desc;
+/* NextPictureTensor with the resized tensor of `desc` (not NULL) at d_dst;
+ * desc->t.cw == 0 takes the active SPS's crop window.  Otherwise as above. */
+H264SwDecRet H264SwDecNextPictureTensorResized(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
+                                               const h264mi_tensor_resize_desc *desc, void *d_dst, void *hip_stream);
 /* Extension (no reference counterpart): where an instance's time went, in
  * seconds since H264SwDecInit -- host parse (NAL extraction, headers, CAVLC /
  * MB layer, DPB, concealment), record upload + kernel launch, waiting for the
@@ -341,6 +355,18 @@ int  h264mi_tensor_device_pitch(const void *d_in, const size_t *in_offsets, int 
  * a bad stream, slot or desc, or when d_out is not on the engine's device. */
 int  h264mi_engine_export_tensor(h264mi_engine *e, int n, const int *streams, const int *slots,
                                  const h264mi_tensor_desc *desc, void *d_out, size_t out_stride, void *hip_stream);
+/* the two calls above with the resized tensor of an h264mi_tensor_resize_desc:
+ * picture k's (planes, oh, ow) elements at d_out + k * out_stride, nothing
+ * else written.  Stateless (the filter taps are derived in the kernel): no
+ * device allocation, no copy, no host synchronisation.  -1, nothing launched,
+ * also for ow or oh outside 1 .. 16384, a window more than 32 times the output
+ * on an axis, or filter != H264MI_RESIZE_TRIANGLE. */
+int  h264mi_tensor_resize_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width, int height,
+                                       int cpitch, const h264mi_tensor_resize_desc *desc, void *d_out,
+                                       size_t out_stride, void *hip_stream);
+int  h264mi_engine_export_tensor_resized(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                         const h264mi_tensor_resize_desc *desc, void *d_out, size_t out_stride,
+                                         void *hip_stream);
 int  h264mi_engine_sync(h264mi_engine *e);
 /* number of (launch, picture) slots flagged since the last call: residual
  * range errors (reference transform.c:181) or a bounded wait that expired;

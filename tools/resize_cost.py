@@ -1,0 +1,123 @@
+"""Diagnostics (not a test): what the resized tensor export costs (resize.hip)
+against the full-size export a caller would otherwise run in front of a resize
+kernel of its own.  One process, device events, warm-up, legs alternating;
+writes profiles/resize_cost.json (or the path given).  Conventions of
+tools/tensor_cost.py.
+
+8 pictures 1920x1088 in the frame-slot layout, window 1920x1080, RGB: resized
+to 224x224 and to 384x640 (oh x ow) as fp16 and as uint8, against k_tensor's
+full-size fp16 export (h264mi_tensor_device_pitch) of the same slots in the
+same run.  The bar: a resized launch takes no longer than the comparator's
+median plus the comparator's own spread (max - min).  Consecutive launches
+rotate through NSETS input and output buffer sets.
+
+With 6 sets the comparator's launches move more than the 256 MB Infinity Cache
+holds, but a resized leg's 24 launches touch only the 6 x 25.6 MB of input and
+little output, which the cache can keep once read.  The same legs are therefore
+measured a second time over 12 input sets (307 MB), where every launch reads
+HBM; both results are written, the bar is judged on each.
+
+Usage: python tools/resize_cost.py [out.json]"""
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from broadway_amd import _lib  # noqa: E402
+from broadway_amd.engine import tensor_desc  # noqa: E402
+
+W, H, CW, CH, NP = 1920, 1088, 1920, 1080, 8
+SAMPLES, REPS, NSETS = 15, 24, 6
+SIZES = [(224, 224), (384, 640)]                        # (oh, ow)
+
+
+def stats(us):
+    q = statistics.quantiles(us, n=4)
+    return {"median_us": round(statistics.median(us), 2), "min_us": round(min(us), 2), "max_us": round(max(us), 2),
+            "iqr_us": round(q[2] - q[0], 2)}
+
+
+def kernel_legs(torch, L, nsets):
+    cpitch = 1024                                       # H264MI_CPITCH(120)
+    slot = W * H + cpitch * H
+    gen_ = torch.Generator(device="cuda").manual_seed(3)
+    sets = range(nsets)
+    rbytes = NP * CW * CH * 3 // 2
+    d_in = [torch.randint(0, 256, (NP * slot,), dtype=torch.uint8, device="cuda", generator=gen_) for _ in sets]
+    offs = (C.c_size_t * NP)(*[k * slot for k in range(NP)])
+    st = torch.cuda.current_stream().cuda_stream
+
+    def chk(rc):
+        if rc != 0:
+            raise RuntimeError("launch failed")
+
+    desc, planes, _ = tensor_desc((0, 0, CW, CH), "rgb", torch.float16)
+    full = [torch.empty((NP, planes, CH, CW), dtype=torch.float16, device="cuda") for _ in range(NSETS)]
+    fstride = planes * CH * CW * 2
+    legs = {"tensor_rgb_float16_full": (lambda i: chk(L.h264mi_tensor_device_pitch(
+        d_in[i].data_ptr(), offs, NP, W, H, cpitch, C.byref(desc), full[i % NSETS].data_ptr(), fstride, st)),
+        NP * fstride)}
+    keep = []
+    for oh, ow in SIZES:
+        for dtype in (torch.float16, torch.uint8):
+            rdesc, planes, _ = tensor_desc((0, 0, CW, CH), "rgb", dtype, size=(oh, ow))
+            outs = [torch.empty((NP, planes, oh, ow), dtype=dtype, device="cuda") for _ in range(NSETS)]
+            stride = planes * oh * ow * outs[0].element_size()
+            keep.append((rdesc, outs))
+
+            def f(i, rdesc=rdesc, outs=outs, stride=stride):
+                chk(L.h264mi_tensor_resize_device_pitch(d_in[i].data_ptr(), offs, NP, W, H, cpitch, C.byref(rdesc),
+                                                        outs[i % NSETS].data_ptr(), stride, st))
+            legs[f"resize_rgb_{str(dtype).split('.')[1]}_{oh}x{ow}"] = (f, NP * stride)
+    us = {k: [] for k in legs}
+    for k, (f, _) in legs.items():                      # warm-up: code objects, every shape
+        for i in sets:
+            f(i)
+    torch.cuda.synchronize()
+    for _ in range(SAMPLES):
+        for k, (f, _) in legs.items():                  # alternating, same process
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for r in range(REPS):
+                f(r % nsets)
+            e1.record()
+            e1.synchronize()
+            us[k].append(e0.elapsed_time(e1) * 1000.0 / REPS)
+    out = {}
+    for k, (_, wbytes) in legs.items():
+        s = stats(us[k])
+        s["bytes_read"], s["bytes_written"] = rbytes, wbytes
+        out[k] = s
+    b = out["tensor_rgb_float16_full"]
+    spread = round(b["max_us"] - b["min_us"], 2)
+    bar = round(b["median_us"] + spread, 2)
+    out["bar"] = {"comparator": "tensor_rgb_float16_full", "comparator_median_us": b["median_us"],
+                  "comparator_spread_us": spread, "bar_us": bar}
+    for k in [k for k in legs if k != "tensor_rgb_float16_full"]:
+        out[k]["over_bar_us"] = round(out[k]["median_us"] - bar, 2)
+        out[k]["meets_bar"] = bool(out[k]["median_us"] <= bar)
+        out[k]["median_over_comparator_median"] = round(out[k]["median_us"] / b["median_us"], 3)
+    return out
+
+
+def main():
+    import torch
+    assert torch.cuda.is_available(), "resize_cost.py measures on the GPU"
+    L = _lib.mi()
+    res = {"shape": {"pictures": NP, "coded": [W, H], "window": [0, 0, CW, CH], "mode": "rgb", "sizes_oh_ow": SIZES,
+                     "samples": SAMPLES, "launches_per_sample": REPS, "buffer_sets_rotated": NSETS},
+           "kernel_6_sets": kernel_legs(torch, L, NSETS)}
+    torch.cuda.empty_cache()
+    res["kernel_12_input_sets_hbm_cold"] = kernel_legs(torch, L, 2 * NSETS)
+    path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "resize_cost.json")
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res, indent=1))
+
+
+if __name__ == "__main__":
+    main()
