@@ -1806,9 +1806,29 @@ __device__ void row_pp(const ReconArgs &a, int p, int r, PPLds &L, const int w, 
         }
         PPT(0);
         if (a.row_prio_split) __builtin_amdgcn_s_setprio(3);
+        // Refresh of the top-halo poll: the read of entry c in flight has
+        // landed long ago where this is called (its tags are tested first, so
+        // a wave never has two polls in flight); if it came back stale, read
+        // again now, so that the round trip through this CU's memory queue
+        // runs under the work that follows and not after V on the chain.
+        // Reading a granule that was current already is harmless: an entry
+        // is written once per epoch.  No loop, no sleep: the wait proper is
+        // the loop after V.
+        auto repoll = [&]() {
+            if (top_on) {
+                const bool mine = lane < 24;
+                if (__builtin_amdgcn_ballot_w64(mine && (uint32_t)(gr >> 32) != tag) != 0) {
+                    if (mine) gr = ld_granT<UPL>(tga);
+                }
+            }
+        };
         // ---- the chain: MB c-1's H pass done -> its columns 12..15
         uint32_t vhalo = 0;     // the vertical pass's left halo (MB c-1's columns 12..15), c > 0
         if (c > 0) {
+#ifdef STUDY_POLL_PRE_HDONE
+            // study build: one more refresh before the (idle) hdone spin
+            repoll();
+#endif
             unsigned spins = 0;
             while (__builtin_amdgcn_readfirstlane(lds_ld(&L.hdone)) < c) {
                 // (no sleep: the partner's hdone store is the chain's next step)
@@ -1828,6 +1848,10 @@ __device__ void row_pp(const ReconArgs &a, int p, int r, PPLds &L, const int w, 
             wave_sync();
             if (lane == 0) lds_st(&R->consumed, 0);
         }
+        // ---- entry c's poll again, to land during V (the speculative read at
+        //      the top of the iteration is 1-2 us old by now: in a row that
+        //      runs in lockstep with the row above it is almost always stale)
+        repoll();
         // ---- vertical edges
         // (measured: reading the left halo straight from the partner's region
         // inside V and releasing it after the MB

@@ -1,0 +1,117 @@
+"""The row wave's top-halo poll (recon_kernels.hip row_pp): the read of the
+row above's mailbox entry c is issued at the top of MB c's iteration, once
+more before the vertical pass when it came back stale, and again after it
+until the entry's tag is the launch's epoch.  Whatever the timing, H(c) must
+take the row above's final rows 12..15 of this launch -- never a stale entry
+of the launch before, whose mailbox it reuses under a new epoch -- so every
+picture of every launch is compared byte for byte with the oracle's decode
+(integer work: no tolerance).
+
+Shapes: one MB column (the c > 0 / hdone branch never runs), one MB per row
+wave, three columns, and an odd width at which the two row waves' last MBs
+differ.  Each run decodes four streams of one size whose deblocking mix
+makes the top edge filtered for all, for none and for some MBs of a row."""
+import functools
+
+import pytest
+
+import oracle as O
+from broadway_amd import _lib, gen
+from broadway_amd.engine import Capture
+
+pytestmark = pytest.mark.gpu
+
+SIZES = [(1, 3), (2, 4), (3, 5), (13, 9)]
+NFRAMES = 9
+
+
+def _mixes(w, h):
+    """(slices, dbf_idc1_pct, dbf_idc2_pct) of the four streams of a run."""
+    return [
+        (2, 0, 0),                      # idc 0 only: every MB below row 0 filters its top edge
+        # idc 2, one slice per MB row.  The generator moves every slice end
+        # by up to 3 MBs, so a few MBs next to the boundaries still have the
+        # MB above in their own slice: nearly none does ...
+        (h, 0, 100),
+        (max(2, h - 1), 50, 50),        # idc 1 / 2 mixed, slice boundaries inside rows: some do
+        (w * h, 0, 100),                # ... and with a slice per MB, none at all
+    ]
+
+
+@functools.lru_cache(maxsize=None)
+def _streams(w, h, ionly):
+    """The run's streams and the oracle's pictures of each (computed once,
+    shared by every case of the size; read only)."""
+    out = []
+    for i, (slices, idc1, idc2) in enumerate(_mixes(w, h)):
+        s = gen.generate(2, 90 + i, nframes=NFRAMES, w_mbs=w, h_mbs=h, crop_bottom=0, slices=slices,
+                         gop=1 if ionly else 5, dbf_idc1_pct=idc1, dbf_idc2_pct=idc2)
+        frames, errs = O.decode(s)[:2]
+        assert errs == 0 and len(frames) == NFRAMES
+        out.append((s, tuple(frames)))
+    return tuple(out)
+
+
+# (pipe, BENCH_DEP_MODE, environment, I-only, MC waves expected at the last launch)
+# Frame-pipelined launches always run single-row workgroups with two MC waves,
+# so the workgroup shapes are forced at one picture per launch.
+SHAPES = {
+    "pipe1": (1, None, {}, False, None),
+    "pipe1_mc2": (1, None, {"H264MI_MC_WAVES": "2"}, False, 2),
+    "pipe1_mc3": (1, None, {"H264MI_MC_WAVES": "3"}, False, 3),
+    "pipe1_ionly_mc6": (1, None, {}, True, 6),
+    "pipe1_rpw2": (1, None, {"H264MI_RPW": "2"}, False, None),
+    "pipe3_rows": (3, "rows", {}, False, 2),
+    "pipe3_cols": (3, "cols", {}, False, 2),
+}
+
+
+@pytest.mark.parametrize("check", [False, True], ids=["plain", "check"])
+@pytest.mark.parametrize("shape", sorted(SHAPES))
+@pytest.mark.parametrize("wh", SIZES, ids=lambda wh: f"{wh[0]}x{wh[1]}")
+def test_top_halo_poll_vs_oracle(wh, shape, check, monkeypatch):
+    """Nine pictures of four streams (top edge filtered for all / none / some
+    MBs of a row), one or three pictures of each per launch, so that several
+    launches reuse the mailboxes under new epochs; rows or (row, column)
+    dependencies between the pictures of a launch; 2, 3 and 6 MC waves per row
+    workgroup, two rows per workgroup (the LDS mailbox); each also through
+    the dependency-checker instances (H264MI_CHECK=1)."""
+    import bench
+    pipe, mode, env, ionly, nmc = SHAPES[shape]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    if mode:
+        monkeypatch.setenv("BENCH_DEP_MODE", mode)
+    if check:
+        monkeypatch.setenv("H264MI_CHECK", "1")
+    w, h = wh
+    data = _streams(w, h, ionly)
+    caps = [Capture(s) for s, _ in data]
+    refs = [r for _, r in data]
+    assert all(c.errors == 0 and c.w_mbs == w and c.h_mbs == h for c in caps)
+    n = min(c.npics for c in caps)
+    n -= n % pipe
+    assert n == NFRAMES
+    run = bench.DeviceRun(_lib.mi(), caps, 0, n, pipe)
+    try:
+        assert run.P == pipe
+        assert len(run.launches) >= 3
+        for i, launch in enumerate(run.launches):
+            run.launch(i)
+            run.eng.sync()
+            for step in launch:
+                for s, k in enumerate(step):
+                    got = run.eng.read(s, int(run.slot_of[k][s])).tobytes()
+                    assert got == refs[s][k], f"stream {s} picture {k}"
+            if pipe > 1:
+                assert run.eng.last_deps() == (1 if mode == "rows" else 2)
+        if nmc is not None:
+            assert run.eng.last_mc_waves() == nmc
+        if check:
+            assert run.eng.kernel_name() == "k_wgpp_check"
+            assert run.eng.error_bits() == 0
+        else:
+            assert run.eng.kernel_name() == "k_wgpp"
+        assert run.eng.errors() == 0
+    finally:
+        run.free()
