@@ -88,6 +88,18 @@ class TensorResizeDesc(C.Structure):
     _fields_ = [("t", TensorDesc), ("ow", C.c_int), ("oh", C.c_int), ("filter", C.c_int)]
 
 
+class MbInfoDesc(C.Structure):
+    """h264mi_mbinfo_desc (include/h264mi.h)."""
+    _fields_ = [(n, C.c_int) for n in ("bx", "by", "bw", "bh", "nch", "dtype")] + \
+               [("ch", C.c_int * 16), ("scale", C.c_float * 16), ("bias", C.c_float * 16)]
+
+
+# channel ids of MbInfoDesc.ch, by name, and the int16 element type
+MBINFO_CHANNELS = {"mvx": 0, "mvy": 1, "ref_idx": 2, "ref_slot": 3, "mb_type": 4, "qp": 5, "intra_mode": 6,
+                   "coded": 7, "slice": 8}
+MBINFO_MAX_CH = 16
+TENSOR_I16 = 4
+
 TENSOR_RGB, TENSOR_GRAY = 0, 1
 RESIZE_TRIANGLE = 0
 RESIZE_MAX_DIM = 16384
@@ -215,6 +227,20 @@ def mi() -> C.CDLL:
         L.h264mi_engine_export_tensor_resized.restype = i32
         L.H264SwDecNextPictureTensorResized.argtypes = [vp, C.POINTER(H264SwDecPicture), u32, rd, vp, vp]
         L.H264SwDecNextPictureTensorResized.restype = i32
+    if hasattr(L, "h264mi_mbinfo_device"):                  # (optional, as above)
+        md = C.POINTER(MbInfoDesc)
+        L.h264mi_mbinfo_device.argtypes = [vp, C.POINTER(sz), i32, i32, i32, md, vp, sz, vp]
+        L.h264mi_mbinfo_device.restype = i32
+        L.h264mi_engine_keep_records.argtypes = [vp, i32]
+        L.h264mi_engine_keep_records.restype = i32
+        L.h264mi_engine_forget_records.argtypes = [vp, i32, i32]
+        L.h264mi_engine_forget_records.restype = i32
+        L.h264mi_engine_export_mbinfo.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), md, vp, sz, vp]
+        L.h264mi_engine_export_mbinfo.restype = i32
+        L.H264SwDecKeepMbInfo.argtypes = [vp, u32]
+        L.H264SwDecKeepMbInfo.restype = i32
+        L.H264SwDecLastPictureMbInfo.argtypes = [vp, md, vp, vp]
+        L.H264SwDecLastPictureMbInfo.restype = i32
     L.h264mi_engine_sync.argtypes = [vp]
     L.h264mi_engine_sync.restype = i32
     L.h264mi_engine_kernel.argtypes = [vp]

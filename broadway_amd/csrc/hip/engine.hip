@@ -7,6 +7,7 @@
 #include "crop.hip"
 #include "tensor.hip"
 #include "resize.hip"
+#include "mbinfo.hip"
 #include "conceal.hip"
 #include <hip/hip_ext.h>
 
@@ -88,6 +89,7 @@ struct h264mi_engine {
     int tev_stride, tev_seq;  // record every tev_stride-th launch (h264mi_engine_set_timing_stride)
     uint8_t *d_rgba;          // h264mi_engine_read_rgba / _read_crop staging (w*h*4 B, allocated on first use)
     hipEvent_t ev_exp_in, ev_exp_out;   // h264mi_engine_export_tensor: the caller's stream -> ours -> the caller's (created on first use)
+    MbRec *d_keep;            // h264mi_engine_keep_records: per (stream, slot) the records of the last reconstruction into it (NULL: off)
     int steps;                // pictures per stream per launch (h264mi_engine_set_steps)
     unsigned long long *d_prog;   // per picture row of a launch, per row wave: {MBs stored, epoch} (frame-pipelined launches)
     unsigned *d_done;             // per picture row of a launch: epoch once the row is stored
@@ -289,6 +291,7 @@ extern "C" void h264mi_engine_destroy(h264mi_engine *e)
     if (e->st) (void)hipStreamSynchronize(e->st);
     free_pic_buffers(e);
     (void)hipFree(e->d_rgba);
+    (void)hipFree(e->d_keep);
     (void)hipFree(e->d_frames); (void)hipFree(e->d_prof); (void)hipFree(e->d_rec); (void)hipFree(e->d_coef);
     (void)hipFree(e->d_pics); (void)hipFree(e->d_gjunk);
     (void)hipHostFree(e->h_rec); (void)hipHostFree(e->h_coef); (void)hipHostFree(e->h_pics);
@@ -560,6 +563,18 @@ static int launch_batch(h264mi_engine *e, int S, int P, const MbRec *d_rec, cons
     return 0;
 }
 
+// record retention (h264mi_engine_keep_records): the uploaded batch's records,
+// picture i at d_rec + i * nmbs, into the kept batches of the slots they were
+// reconstructed into -- one device-to-device copy each on the engine's stream,
+// behind the upload and the launch reading them and ahead of the next upload
+static int keep_batch(h264mi_engine *e, int npics, const int *stream, const int *cur_slot)
+{
+    for (int i = 0; i < npics; i++)
+        HIPCHECK(hipMemcpyAsync(e->d_keep + ((size_t)stream[i] * e->nslots + cur_slot[i]) * e->nmbs,
+                                e->d_rec + (size_t)i * e->nmbs, sizeof(MbRec) * e->nmbs, hipMemcpyDeviceToDevice, e->st));
+    return 0;
+}
+
 // intra_heavy: the batch's launch shape hint when the caller knows it (the
 // host path counts intra MBs while parsing); -1: derive it from the records
 
@@ -614,7 +629,8 @@ int engine_decode_host(h264mi_engine *e, int npics, const int *stream, const int
     int heavy = intra_heavy > 0;
     for (int i = 0; i < npics && !heavy && intra_heavy < 0; i++) heavy = (e->h_pics[i].flags & PD_INTRA_HEAVY) != 0;
     e->launch_intra = heavy;
-    return launch_batch(e, npics, 1, e->d_rec, e->d_coef, e->d_pics, NULL, NULL, NULL);
+    if (launch_batch(e, npics, 1, e->d_rec, e->d_coef, e->d_pics, NULL, NULL, NULL)) return -1;
+    return e->d_keep ? keep_batch(e, npics, stream, cur_slot) : 0;
 }
 
 int engine_decode_direct(h264mi_engine *e, int stream, int cur_slot, const void *rec, const int16_t *coef,
@@ -649,7 +665,8 @@ int engine_decode_direct(h264mi_engine *e, int stream, int cur_slot, const void 
     HIPCHECK(hipMemcpyAsync(e->d_pics, e->h_pics, sizeof(PicDesc), hipMemcpyHostToDevice, e->st));
     HIPCHECK(hipEventRecord(e->ev_staged, e->st));
     e->launch_intra = intra_heavy >= 0 ? intra_heavy : (pd.flags & PD_INTRA_HEAVY) != 0;
-    return launch_batch(e, 1, 1, e->d_rec, e->d_coef, e->d_pics, NULL, NULL, NULL);
+    if (launch_batch(e, 1, 1, e->d_rec, e->d_coef, e->d_pics, NULL, NULL, NULL)) return -1;
+    return e->d_keep ? keep_batch(e, 1, &stream, &cur_slot) : 0;
 }
 
 int engine_records_wait(h264mi_engine *e)
@@ -1178,6 +1195,127 @@ extern "C" int h264mi_engine_export_tensor_resized(h264mi_engine *e, int n, cons
     return engine_export(e, n, streams, slots, desc ? &desc->t : NULL, desc, d_out, out_stride, stream);
 }
 
+// a field descriptor h264mi_mbinfo_device accepts on a w_mbs x h_mbs picture
+static bool mbinfo_desc_ok(const h264mi_mbinfo_desc *d, int w_mbs, int h_mbs)
+{
+    if (!d || d->bx < 0 || d->by < 0 || d->bw < 1 || d->bh < 1 || d->bw > 4 * w_mbs - d->bx || d->bh > 4 * h_mbs - d->by ||
+        d->nch < 1 || d->nch > H264MI_MBINFO_MAX_CH ||
+        (d->dtype != H264MI_TENSOR_F16 && d->dtype != H264MI_TENSOR_BF16 && d->dtype != H264MI_TENSOR_F32 &&
+         d->dtype != H264MI_TENSOR_I16))
+        return false;
+    for (int c = 0; c < d->nch; c++)
+        if (d->ch[c] < 0 || d->ch[c] >= H264MI_MBINFO_NCHANNELS) return false;
+    return true;
+}
+
+// Motion vectors and MB side information as planar fields (mbinfo.hip): the
+// window desc->(bx, by, bw, bh) of the 4x4-block grid of the npics record
+// batches (w_mbs * h_mbs MbRec each) that start rec_offsets[k] bytes after
+// d_recs, as contiguous (nch, bh, bw) elements of desc->dtype at d_out + k *
+// out_stride; device pointers, asynchronous on `stream`; MBINFO_MAX_PICS
+// pictures per launch.  -1 (nothing launched) on a bad argument.
+extern "C" int h264mi_mbinfo_device(const void *d_recs, const size_t *rec_offsets, int npics, int w_mbs, int h_mbs,
+                                    const h264mi_mbinfo_desc *desc, void *d_out, size_t out_stride, void *stream)
+{
+    static_assert(H264MI_TENSOR_I16 == TENSOR_I16 && H264MI_MBINFO_MAX_CH == MBINFO_MAX_CH &&
+                      H264MI_MBINFO_NCHANNELS == MBI_NCHANNELS && H264MI_MBINFO_MVX == MBI_MVX &&
+                      H264MI_MBINFO_MVY == MBI_MVY && H264MI_MBINFO_REF_IDX == MBI_REF_IDX &&
+                      H264MI_MBINFO_REF_SLOT == MBI_REF_SLOT && H264MI_MBINFO_MB_TYPE == MBI_MB_TYPE &&
+                      H264MI_MBINFO_QP == MBI_QP && H264MI_MBINFO_INTRA_MODE == MBI_INTRA_MODE &&
+                      H264MI_MBINFO_CODED == MBI_CODED && H264MI_MBINFO_SLICE == MBI_SLICE,
+                  "include/h264mi.h and mbinfo.hip name the same channels and element types");
+    if (!d_recs || !rec_offsets || !d_out || npics < 1 || w_mbs < 1 || h_mbs < 1 || w_mbs > 65535 || h_mbs > 65535 ||
+        ((size_t)(uintptr_t)d_recs & 15) || !mbinfo_desc_ok(desc, w_mbs, h_mbs))
+        return -1;
+    for (int k = 0; k < npics; k++)
+        if (rec_offsets[k] % sizeof(MbRec)) return -1;
+    const size_t es = (size_t)tensor_elem_size(desc->dtype);
+    if (((size_t)(uintptr_t)d_out | out_stride) & (es - 1)) return -1;
+    const bool v16 = !(((size_t)(uintptr_t)d_out | out_stride | (size_t)desc->bw * es) & 15);
+    mbinfo_args a;
+    a.rec = (const uint8_t *)d_recs;
+    a.w_mbs = w_mbs;
+    a.bx = desc->bx; a.by = desc->by; a.bw = desc->bw; a.bh = desc->bh; a.nch = desc->nch;
+    a.out_stride = out_stride;
+    for (int c = 0; c < MBINFO_MAX_CH; c++) {
+        a.ch[c] = c < desc->nch ? (uint8_t)desc->ch[c] : 0;
+        a.scale[c] = c < desc->nch ? desc->scale[c] : 0.0f;
+        a.bias[c] = c < desc->nch ? desc->bias[c] : 0.0f;
+    }
+    for (int k0 = 0; k0 < npics; k0 += MBINFO_MAX_PICS) {
+        const int n = npics - k0 < MBINFO_MAX_PICS ? npics - k0 : MBINFO_MAX_PICS;
+        for (int k = 0; k < MBINFO_MAX_PICS; k++) a.off[k] = k < n ? rec_offsets[k0 + k] : 0;
+        a.out = (uint8_t *)d_out + (size_t)k0 * out_stride;
+        mbinfo_launch(desc->dtype, v16, n, (hipStream_t)stream, a);
+        HIPCHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+// Record retention: one batch per (stream, slot), 0xFF-filled ("no
+// information") until a reconstruction into the slot copies its records there
+// (keep_batch).  Off waits for the engine's stream (exports run on it) and frees.
+extern "C" int h264mi_engine_keep_records(h264mi_engine *e, int on)
+{
+    if (!e) return -1;
+    if ((on != 0) == (e->d_keep != NULL)) return 0;
+    HIPCHECK(hipSetDevice(e->dev));
+    const size_t bytes = sizeof(MbRec) * e->nmbs * e->nslots * e->nstreams;
+    if (on) {
+        HIPCHECK(hipMalloc(&e->d_keep, bytes));
+        if (hipMemsetAsync(e->d_keep, 0xFF, bytes, e->st) != hipSuccess) {
+            (void)hipFree(e->d_keep);
+            e->d_keep = NULL;
+            return -1;
+        }
+        return 0;
+    }
+    HIPCHECK(hipStreamSynchronize(e->st));
+    (void)hipFree(e->d_keep);
+    e->d_keep = NULL;
+    return 0;
+}
+
+extern "C" int h264mi_engine_forget_records(h264mi_engine *e, int stream, int slot)
+{
+    if (!e || !e->d_keep || stream < 0 || stream >= e->nstreams || slot < 0 || slot >= e->nslots) return -1;
+    HIPCHECK(hipSetDevice(e->dev));
+    HIPCHECK(hipMemsetAsync(e->d_keep + ((size_t)stream * e->nslots + slot) * e->nmbs, 0xFF, sizeof(MbRec) * e->nmbs, e->st));
+    return 0;
+}
+
+// The kept batches of the slots (streams[k], slots[k]) as fields in the
+// caller's memory: ordered between the caller's stream and ours as
+// engine_export orders a tensor export, with the same pair of events
+extern "C" int h264mi_engine_export_mbinfo(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                           const h264mi_mbinfo_desc *desc, void *d_out, size_t out_stride, void *stream)
+{
+    if (!e || !e->d_keep || n < 1 || !streams || !slots || !d_out || !mbinfo_desc_ok(desc, e->w, e->h)) return -1;
+    for (int k = 0; k < n; k++)
+        if (streams[k] < 0 || streams[k] >= e->nstreams || slots[k] < 0 || slots[k] >= e->nslots) return -1;
+    const size_t es = (size_t)tensor_elem_size(desc->dtype);
+    if (((size_t)(uintptr_t)d_out | out_stride) & (es - 1)) return -1;
+    if (h264mi_pointer_device(d_out) != e->dev) return -1;
+    HIPCHECK(hipSetDevice(e->dev));
+    if (!e->ev_exp_in) HIPCHECK(hipEventCreateWithFlags(&e->ev_exp_in, hipEventDisableTiming));
+    if (!e->ev_exp_out) HIPCHECK(hipEventCreateWithFlags(&e->ev_exp_out, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(e->ev_exp_in, (hipStream_t)stream));
+    HIPCHECK(hipStreamWaitEvent(e->st, e->ev_exp_in, 0));
+    int rc = 0;
+    for (int k0 = 0; k0 < n && !rc; k0 += MBINFO_MAX_PICS) {
+        size_t off[MBINFO_MAX_PICS];
+        const int m = n - k0 < MBINFO_MAX_PICS ? n - k0 : MBINFO_MAX_PICS;
+        for (int k = 0; k < m; k++)
+            off[k] = sizeof(MbRec) * e->nmbs * ((size_t)streams[k0 + k] * e->nslots + slots[k0 + k]);
+        rc = h264mi_mbinfo_device(e->d_keep, off, m, e->w, e->h, desc, (uint8_t *)d_out + (size_t)k0 * out_stride,
+                                  out_stride, e->st);
+    }
+    // (also after a failed launch: whatever reached our stream stays ordered)
+    HIPCHECK(hipEventRecord(e->ev_exp_out, e->st));
+    HIPCHECK(hipStreamWaitEvent((hipStream_t)stream, e->ev_exp_out, 0));
+    return rc;
+}
+
 extern "C" void *h264mi_engine_frame_ptr(h264mi_engine *e, int stream, int slot)
 {
     if (!e) return NULL;
@@ -1305,6 +1443,7 @@ int engine_reuse(h264mi_engine *e)
     e->err_bits = 0;          // the previous owner's device / checker flags
     e->steps = 1;
     e->last_kernel = NULL;
+    if (h264mi_engine_keep_records(e, 0)) return -1;      // the previous owner's retention
     // the epoch keeps counting: the mailboxes hold tags of earlier launches only
     HIPCHECK(hipMemsetAsync(e->d_frames, 0, e->frame_bytes * e->nslots * e->nstreams, e->st));
     return 0;

@@ -24,7 +24,8 @@
 #define TENSOR_MAX_PICS 32          // pictures per launch (their offsets travel in the kernel arguments)
 
 enum { TENSOR_RGB = 0, TENSOR_GRAY = 1 };
-enum { TENSOR_U8 = 0, TENSOR_F16 = 1, TENSOR_BF16 = 2, TENSOR_F32 = 3 };
+enum { TENSOR_U8 = 0, TENSOR_F16 = 1, TENSOR_BF16 = 2, TENSOR_F32 = 3,
+       TENSOR_I16 = 4 };            // int16: mbinfo.hip only (the pixel exports refuse it)
 
 struct tensor_args {
     const uint8_t *in;
@@ -57,15 +58,22 @@ __device__ __forceinline__ void tensor_load(const uint8_t *s, uint32_t (&d)[NW])
     for (int j = 0; j < NW; j++) d[j] = __builtin_amdgcn_alignbyte(e[j + 1], e[j], sh);
 }
 
+// the fp32 value f as a float element type's bits (16-bit types: one
+// round-to-nearest-even conversion)
+template <int DT>
+__device__ __forceinline__ uint32_t tensor_float_bits(float f)
+{
+    if constexpr (DT == TENSOR_F16) return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f);
+    if constexpr (DT == TENSOR_BF16) return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)f);
+    return __builtin_bit_cast(uint32_t, f);
+}
+
 // element i of a plane row: the sample c as the element type's bits
 template <int DT>
 __device__ __forceinline__ uint32_t tensor_elem(uint32_t c, float s, float b)
 {
     if constexpr (DT == TENSOR_U8) return c;
-    const float f = __builtin_fmaf((float)c, s, b);
-    if constexpr (DT == TENSOR_F16) return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f);
-    if constexpr (DT == TENSOR_BF16) return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)f);
-    return __builtin_bit_cast(uint32_t, f);
+    return tensor_float_bits<DT>(__builtin_fmaf((float)c, s, b));
 }
 
 // one plane row of an item: the samples c[0 .. n) as elements at d.  V16:

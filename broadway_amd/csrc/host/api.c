@@ -145,6 +145,7 @@ H264SwDecRet H264SwDecDecode(H264SwDecInst decInst, H264SwDecInput *pInput, H264
     u8 *p = pInput->pStream;
     pOutput->pStrmCurrPos = NULL;
     c->dec.intra_conceal = (int)pInput->intraConcealmentMethod;
+    c->dec.last_out_slot1 = 0;      /* H264SwDecLastPictureMbInfo: this call may decode into that picture's slot */
     do {
         int r;
         uint32_t nread = 0;
@@ -337,6 +338,53 @@ H264SwDecRet H264SwDecNextPictureTensorResized(H264SwDecInst decInst, H264SwDecP
     pOutput->picId = id;
     pOutput->isIdrPicture = idr;
     pOutput->nbrOfErrMBs = em;
+    return H264SWDEC_PIC_RDY;
+}
+
+/* Record retention for H264SwDecLastPictureMbInfo (include/h264mi.h): the
+ * backend keeps it across configure, so it may be called before the headers */
+H264SwDecRet H264SwDecKeepMbInfo(H264SwDecInst decInst, u32 on)
+{
+    if (decInst == NULL) return H264SWDEC_PARAM_ERR;
+    DecContainer *c = (DecContainer *)decInst;
+    if (!c->dec.be.keep_records || !c->dec.be.export_mbinfo) return H264SWDEC_PARAM_ERR;
+    if (c->dec.be.keep_records(c->dec.be.ctx, on != 0)) return H264SWDEC_PARAM_ERR;
+    c->dec.keep_mbinfo = on != 0;
+    return H264SWDEC_OK;
+}
+
+/* The MB side-information field of the picture the last H264SwDecNextPicture*
+ * call delivered (include/h264mi.h); desc->bw == 0: the blocks covering the
+ * active SPS's crop window.  The DPB is not touched.  Everything the export
+ * can refuse is checked before anything is queued. */
+H264SwDecRet H264SwDecLastPictureMbInfo(H264SwDecInst decInst, const h264mi_mbinfo_desc *desc, void *d_dst,
+                                        void *hip_stream)
+{
+    if (decInst == NULL || desc == NULL || d_dst == NULL) return H264SWDEC_PARAM_ERR;
+    DecContainer *c = (DecContainer *)decInst;
+    if (!c->dec.be.export_mbinfo || !c->dec.keep_mbinfo) return H264SWDEC_PARAM_ERR;
+    h264mi_mbinfo_desc m = *desc;
+    if (m.nch < 1 || m.nch > H264MI_MBINFO_MAX_CH ||
+        (m.dtype != H264MI_TENSOR_F16 && m.dtype != H264MI_TENSOR_BF16 && m.dtype != H264MI_TENSOR_F32 &&
+         m.dtype != H264MI_TENSOR_I16))
+        return H264SWDEC_PARAM_ERR;
+    for (int k = 0; k < m.nch; k++)
+        if (m.ch[k] < 0 || m.ch[k] >= H264MI_MBINFO_NCHANNELS) return H264SWDEC_PARAM_ERR;
+    if ((size_t)(uintptr_t)d_dst & (m.dtype == H264MI_TENSOR_F32 ? 3u : 1u)) return H264SWDEC_PARAM_ERR;
+    const Sps *s = h264dec_active_sps(&c->dec);
+    if (!s || !c->dec.last_out_slot1) return H264SWDEC_OK;      /* no picture delivered */
+    const int bw_all = 4 * (int)s->w_mbs, bh_all = 4 * (int)s->h_mbs;
+    if (m.bw == 0) {
+        const int x = s->crop ? 2 * (int)s->crop_l : 0, y = s->crop ? 2 * (int)s->crop_t : 0;
+        const int cw = 4 * bw_all - x - (s->crop ? 2 * (int)s->crop_r : 0);
+        const int ch = 4 * bh_all - y - (s->crop ? 2 * (int)s->crop_b : 0);
+        m.bx = x >> 2; m.by = y >> 2;
+        m.bw = ((x + cw + 3) >> 2) - m.bx; m.bh = ((y + ch + 3) >> 2) - m.by;
+    }
+    if (m.bx < 0 || m.by < 0 || m.bw < 1 || m.bh < 1 || m.bw > bw_all - m.bx || m.bh > bh_all - m.by)
+        return H264SWDEC_PARAM_ERR;
+    if (c->dec.be.export_mbinfo(c->dec.be.ctx, c->dec.last_out_slot1 - 1, &m, d_dst, hip_stream))
+        return H264SWDEC_PARAM_ERR;         /* (d_dst not on the decoder's GPU) */
     return H264SWDEC_PIC_RDY;
 }
 

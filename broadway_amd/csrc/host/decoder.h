@@ -53,6 +53,13 @@ typedef struct H264Backend {
     int  (*export_tensor)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
     /* the same, resized on the GPU (desc: a checked h264mi_tensor_resize_desc) */
     int  (*export_tensor_resized)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
+    /* optional: from the next decode on, keep (on != 0) each picture's records
+     * on the device until its slot is decoded into again; survives configure */
+    int  (*keep_records)(void *ctx, int on);
+    /* optional: the kept records of slot as the MB side-information field of
+     * desc (a checked h264mi_mbinfo_desc) into device memory d_dst, ordered on
+     * hip_stream like export_tensor; 0 ok, -1 failure */
+    int  (*export_mbinfo)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
     /* optional: host memory for the output frames (pinned by the HIP
      * backend, so each picture's D2H copy runs at DMA speed); NULL: malloc */
     void *(*host_alloc)(void *ctx, size_t bytes);
@@ -129,6 +136,11 @@ typedef struct H264Dec {
      * out_frames are not started (nobody reads them); a plain next_output
      * clears it and reads synchronously until the copies are back */
     int      out_cropped;
+    /* the backend keeps records (H264SwDecKeepMbInfo), and the slot of the
+     * picture the last next_output of any kind delivered, plus one (0: none
+     * since the last H264SwDecDecode) */
+    int      keep_mbinfo;
+    int      last_out_slot1;
     /* statistics */
     uint64_t pics_decoded, alg_ref_bytes, coded_blocks;
     /* speculative parallel slice parsing (specparse.c); NULL: off */

@@ -193,6 +193,7 @@ struct HipBackendCtx {
     unsigned ndecodes, force_flag_at;
     int nslots;
     unsigned enq, synced;   // work items queued on the engine's stream / of those, waited for by hb_sync
+    bool keep;              // keep_records: asked for by the decoder, applied to every engine configured from then on
 };
 
 extern "C" int h264mi_set_share(int lanes)
@@ -320,6 +321,47 @@ static bool wait_launched(SharedEng *sh, unsigned long long mine)
     return true;
 }
 
+// Weak like the crop and tensor entry points below: a backend built against
+// the CPU stand-in of the engine leaves keep_records and export_mbinfo NULL.
+extern "C" int h264mi_engine_keep_records(h264mi_engine *e, int on) __attribute__((weak));
+extern "C" int h264mi_engine_forget_records(h264mi_engine *e, int stream, int slot) __attribute__((weak));
+extern "C" int h264mi_engine_export_mbinfo(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                           const h264mi_mbinfo_desc *desc, void *d_out, size_t out_stride,
+                                           void *hip_stream) __attribute__((weak));
+
+// c->keep onto the instance's engine.  A shared engine's retention is only
+// ever switched on: its other instances may be using it.
+static int hb_keep_apply(HipBackendCtx *c)
+{
+    if (!c->sh) return h264mi_engine_keep_records(c->e, c->keep);
+    if (!c->keep) return 0;
+    std::lock_guard<std::mutex> l(c->sh->mu);
+    return h264mi_engine_keep_records(c->e, 1);
+}
+
+static int hb_keep_records(void *vctx, int on)
+{
+    HipBackendCtx *c = (HipBackendCtx *)vctx;
+    c->keep = on != 0;
+    return c->e ? hb_keep_apply(c) : 0;
+}
+
+// the kept records of slot as a field (desc: a checked h264mi_mbinfo_desc) at
+// d_dst; ordered like hb_export, nothing waits
+static int hb_export_mbinfo(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
+{
+    HipBackendCtx *c = (HipBackendCtx *)vctx;
+    if (!c->e || slot < 0 || slot >= c->nslots) return -1;
+    const int lane = c->lane;
+    std::unique_lock<std::mutex> l;
+    if (c->sh) l = std::unique_lock<std::mutex>(c->sh->mu);
+    if (h264mi_engine_export_mbinfo(c->e, 1, &lane, &slot, (const h264mi_mbinfo_desc *)desc, d_dst, 0, hip_stream))
+        return -1;
+    if (c->sh) HIPCHECK(hipEventRecord(c->ev_last, engine_stream(c->e)));
+    c->enq++;
+    return 0;
+}
+
 static int hb_configure(void *vctx, int w_mbs, int h_mbs, int nslots)
 {
     HipBackendCtx *c = (HipBackendCtx *)vctx;
@@ -341,6 +383,7 @@ static int hb_configure(void *vctx, int w_mbs, int h_mbs, int nslots)
         c->lane = 0;
         c->e = engine_get(c->device, w_mbs, h_mbs, 1, nslots);
     }
+    if (c->e && c->keep && hb_keep_apply(c)) return -1;
     return c->e && c->pref ? 0 : -1;
 }
 
@@ -636,9 +679,12 @@ static int hb_copy(void *vctx, int dst, int src)
         std::lock_guard<std::mutex> l(c->sh->mu);
         HIPCHECK(hipMemcpyAsync(h264mi_engine_frame_ptr(c->e, c->lane, dst), h264mi_engine_frame_ptr(c->e, c->lane, src),
                                 engine_slot_bytes(c->e), hipMemcpyDeviceToDevice, engine_stream(c->e)));
+        // the copy is no reconstruction: dst's kept records say nothing about it
+        if (c->keep && h264mi_engine_forget_records && h264mi_engine_forget_records(c->e, c->lane, dst)) return -1;
         HIPCHECK(hipEventRecord(c->ev_last, engine_stream(c->e)));
         return 0;
     }
+    if (c->keep && h264mi_engine_forget_records && h264mi_engine_forget_records(c->e, 0, dst)) return -1;
     if (h264mi_engine_sync(c->e)) return -1;
     HIPCHECK(hipMemcpy(h264mi_engine_frame_ptr(c->e, 0, dst), h264mi_engine_frame_ptr(c->e, 0, src),
                        engine_slot_bytes(c->e), hipMemcpyDeviceToDevice));
@@ -694,6 +740,9 @@ extern "C" H264Backend h264mi_hip_backend_create(int device)
     be.read_crop = h264mi_engine_read_crop && h264mi_crop_device_pitch ? hb_read_crop : NULL;
     be.export_tensor = h264mi_engine_export_tensor ? hb_export_tensor : NULL;
     be.export_tensor_resized = h264mi_engine_export_tensor_resized ? hb_export_tensor_resized : NULL;
+    const bool mbinfo = h264mi_engine_keep_records && h264mi_engine_export_mbinfo;
+    be.keep_records = mbinfo ? hb_keep_records : NULL;
+    be.export_mbinfo = mbinfo ? hb_export_mbinfo : NULL;
     be.host_alloc = hb_host_alloc;
     be.host_free = hb_host_free;
     be.records_wait = hb_records_wait;

@@ -40,6 +40,16 @@ of the wasm glue of Decoder/src/Decoder.c:44-162:
   and the callback's width and height are ``ow`` and ``oh``.  It combines with
   neither ``rgb`` nor ``crop`` (ValueError).
 
+* ``mbinfo: true`` or ``mbinfo: {"channels": ..., "dtype": ..., "scale": ...,
+  "bias": ...}`` (an extension for device consumers; needs torch; combines
+  with every output mode above): the decoder keeps each picture's MB records
+  on the GPU, and before every ``onPictureDecoded`` call ``decoder.mbinfo`` is
+  a new ``(C, bh, bw)`` torch tensor on the decoder's GPU -- the delivered
+  picture's motion vectors and MB side information, one element per luma 4x4
+  block covering the SPS crop window, built by ``H264SwDecLastPictureMbInfo``
+  on torch's current stream; the arguments of ``Engine.to_mbinfo`` (default:
+  channels ("mvx", "mvy"), int16).
+
 Unlike the reference module (a single global instance) every ``Decoder`` has
 its own H264SwDec instance, so several streams can be decoded side by side.
 Reconstruction always runs on the GPU through libh264mi.so; ``sliceMode``
@@ -83,12 +93,26 @@ class Decoder:
             self._tensor = tensor_desc(None, **opts)
             self._resized = opts.get("size") is not None
             self._device = int(os.environ.get("H264MI_DEVICE") or 0)     # the GPU H264SwDecInit takes (api.c)
+        self._mbinfo = self.options.get("mbinfo") or None
+        self.mbinfo = None
+        if self._mbinfo is not None:
+            opts = {} if self._mbinfo is True else dict(self._mbinfo)
+            unknown = set(opts) - {"channels", "dtype", "scale", "bias"}
+            if unknown:
+                raise ValueError(f"mbinfo: unknown keys {sorted(unknown)}")
+            from .engine import mbinfo_desc          # (imports torch)
+            self._mbinfo = mbinfo_desc(opts.pop("channels", ("mvx", "mvy")), None, **opts)
+            self._device = int(os.environ.get("H264MI_DEVICE") or 0)
         self._L = _lib.mi()
         inst = C.c_void_p()
         ret = self._L.H264SwDecInit(C.byref(inst), 0)
         if ret != _lib.H264SWDEC_OK:
             raise RuntimeError(f"DECODER INITIALIZATION FAILED ({ret})")
         self._inst = inst
+        if self._mbinfo is not None and (not hasattr(self._L, "H264SwDecKeepMbInfo") or
+                                         self._L.H264SwDecKeepMbInfo(inst, 1) != _lib.H264SWDEC_OK):
+            self.close()
+            raise RuntimeError("mbinfo: the backend cannot keep MB records (there is no host fallback)")
         self._buf = (C.c_uint8 * STREAM_BUFFER_SIZE)()
         self._info = _lib.H264SwDecInfo()
         self._pic = _lib.H264SwDecPicture()
@@ -189,7 +213,27 @@ class Decoder:
             return i.cropParams.cropOutWidth, i.cropParams.cropOutHeight
         return i.picWidth, i.picHeight
 
+    def _export_mbinfo(self):
+        """The delivered picture's field over the blocks covering the crop
+        window (the window H264SwDecLastPictureMbInfo takes for bw == 0)."""
+        import torch
+        desc, nch, dtype = self._mbinfo
+        i = self._info
+        x, y, cw, ch = ((i.cropParams.cropLeftOffset, i.cropParams.cropTopOffset, i.cropParams.cropOutWidth,
+                         i.cropParams.cropOutHeight) if i.croppingFlag else (0, 0, i.picWidth, i.picHeight))
+        bw, bh = ((x + cw + 3) >> 2) - (x >> 2), ((y + ch + 3) >> 2) - (y >> 2)
+        dev = torch.device("cuda", self._device)
+        with torch.cuda.device(dev):
+            out = torch.empty((nch, bh, bw), dtype=dtype, device=dev)
+        ret = self._L.H264SwDecLastPictureMbInfo(self._inst, C.byref(desc), out.data_ptr(),
+                                                 torch.cuda.current_stream(dev).cuda_stream)
+        if ret != _lib.H264SWDEC_PIC_RDY:
+            raise RuntimeError(f"mbinfo: the backend cannot export the MB records ({ret}; there is no host fallback)")
+        return out
+
     def _emit(self, pic, rgba=None) -> None:
+        if self._mbinfo is not None:
+            self.mbinfo = self._export_mbinfo()
         w, h = self._out_size()
         if rgba is not None:
             buf = rgba

@@ -84,6 +84,55 @@ def tensor_desc(window, mode="rgb", dtype=None, scale=None, bias=None, mean=None
     return d, planes, dtype
 
 
+def mbinfo_desc(channels, window=None, dtype=None, scale=None, bias=None):
+    """(``_lib.MbInfoDesc``, number of channels, torch dtype) of an export of
+    motion vectors and MB side information (Engine.to_mbinfo, Decoder's
+    ``mbinfo`` option): ``channels`` names the planes, in order, repeats
+    allowed (1..16 of "mvx", "mvy", "ref_idx", "ref_slot", "mb_type", "qp",
+    "intra_mode", "coded", "slice"; include/h264mi.h defines them); window =
+    (bx, by, bw, bh) in 4x4 blocks, or None for the blocks covering the
+    decoder's SPS crop window (bw = 0 in the descriptor).  ``dtype``:
+    torch.int16 (the default; the integer itself) or float16 / bfloat16 /
+    float32, ``fma(v, scale[c], bias[c])`` of channel position c; scale and
+    bias are scalars or one value per channel, default 1 and 0."""
+    import torch
+    if isinstance(channels, str):
+        channels = (channels,)
+    channels = tuple(channels)
+    if not 1 <= len(channels) <= _lib.MBINFO_MAX_CH:
+        raise ValueError(f"channels: 1..{_lib.MBINFO_MAX_CH} names")
+    bad = [c for c in channels if c not in _lib.MBINFO_CHANNELS]
+    if bad:
+        raise ValueError(f"channels {bad}: each one of {sorted(_lib.MBINFO_CHANNELS)}")
+    dtype = torch.int16 if dtype is None else dtype
+    dts = {torch.int16: _lib.TENSOR_I16, torch.float16: _lib.TENSOR_F16, torch.bfloat16: _lib.TENSOR_BF16,
+           torch.float32: _lib.TENSOR_F32}
+    if dtype not in dts:
+        raise ValueError(f"dtype {dtype}: one of torch.int16, float16, bfloat16, float32")
+
+    def per_channel(v, default, what):
+        if v is None:
+            return (default,) * len(channels)
+        v = tuple(float(f) for f in v) if hasattr(v, "__len__") else (float(v),) * len(channels)
+        if len(v) != len(channels):
+            raise ValueError(f"{what}: a scalar or one value per channel")
+        return v
+
+    d = _lib.MbInfoDesc()
+    if window is not None:
+        try:
+            d.bx, d.by, d.bw, d.bh = (int(v) for v in window)
+        except (TypeError, ValueError):
+            raise ValueError(f"window {window!r}: (bx, by, bw, bh)") from None
+        if d.bx < 0 or d.by < 0 or d.bw < 1 or d.bh < 1:
+            raise ValueError(f"window {tuple(window)}: bx, by >= 0 and bw, bh >= 1 (4x4 blocks)")
+    d.nch, d.dtype = len(channels), dts[dtype]
+    d.ch[:len(channels)] = [_lib.MBINFO_CHANNELS[c] for c in channels]
+    d.scale[:len(channels)] = per_channel(scale, 1.0, "scale")
+    d.bias[:len(channels)] = per_channel(bias, 0.0, "bias")
+    return d, len(channels), dtype
+
+
 @dataclass
 class CapturedPicture:
     rec: int            # host address of w*h MbRec
@@ -302,6 +351,55 @@ class Engine:
         if export(self._h, n, (C.c_int * n)(*streams), (C.c_int * n)(*slots), C.byref(desc), out.data_ptr(),
                   planes * shape[2] * shape[3] * out.element_size(), st.cuda_stream) != 0:
             raise RuntimeError(f"{export.__name__} failed (stream, slot, window or size out of range?)")
+        return out
+
+    def keep_records(self, on: bool = True) -> None:
+        """Keep each picture's MB records on the device, per (stream, slot),
+        from the next ``decode`` on (to_mbinfo reads them); ``on=False`` waits
+        for the engine and frees them.  ``decode_device*`` launches retain
+        nothing."""
+        if self._L.h264mi_engine_keep_records(self._h, int(bool(on))) != 0:
+            raise RuntimeError("h264mi_engine_keep_records failed")
+
+    def forget_records(self, stream: int, slot: int) -> None:
+        """Mark the slot's kept records as "no information"."""
+        if self._L.h264mi_engine_forget_records(self._h, stream, slot) != 0:
+            raise RuntimeError("h264mi_engine_forget_records failed (keep_records off, or a bad stream or slot)")
+
+    def to_mbinfo(self, streams: Sequence[int], slots: Sequence[int], channels=("mvx", "mvy"), window=None,
+                  dtype=None, scale=None, bias=None, out=None, stream=None):
+        """Motion vectors and MB side information of the pictures last
+        decoded into the slots (streams[k], slots[k]) as one ``(n, C, bh,
+        bw)`` torch tensor on ``cuda:{self.device}``, one element per luma 4x4
+        block of ``window`` = (bx, by, bw, bh) in blocks (None: the whole
+        picture, 4 * h_mbs rows of 4 * w_mbs) and per name in ``channels``
+        (``mbinfo_desc``; a slot nothing was decoded into reads as "no
+        information").  Needs ``keep_records()`` before the decodes.  ``out``
+        and ``stream`` as for ``to_tensor``; the host is never synchronised."""
+        import torch
+        n = len(streams)
+        if n < 1 or len(slots) != n:
+            raise ValueError("streams and slots name the same, non-zero number of pictures")
+        if window is None:
+            window = (0, 0, self.w_mbs * 4, self.h_mbs * 4)
+        desc, nch, dtype = mbinfo_desc(channels, window, dtype, scale, bias)
+        shape = (n, nch, desc.bh, desc.bw)
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = torch.empty(shape, dtype=dtype, device=dev)
+        elif tuple(out.shape) != shape or out.dtype != dtype or out.device != dev or not out.is_contiguous():
+            raise ValueError(f"out: a contiguous {dtype} tensor of shape {shape} on {dev} "
+                             f"(got {out.dtype} {tuple(out.shape)} on {out.device})")
+        cur = torch.cuda.current_stream(dev)
+        st = stream if stream is not None else cur
+        if st != cur:
+            out.record_stream(st)       # (the caching allocator: the block is in use on `stream` too)
+        if self._L.h264mi_engine_export_mbinfo(self._h, n, (C.c_int * n)(*streams), (C.c_int * n)(*slots),
+                                               C.byref(desc), out.data_ptr(),
+                                               nch * desc.bh * desc.bw * out.element_size(), st.cuda_stream) != 0:
+            raise RuntimeError("h264mi_engine_export_mbinfo failed (keep_records off, or stream, slot or window "
+                               "out of range?)")
         return out
 
     @property

@@ -136,7 +136,8 @@ H264SwDecRet H264SwDecNextPictureCropped(H264SwDecInst decInst, H264SwDecPicture
  * p as one fp32 fused multiply-add, then rounded to nearest-even to the 16-bit
  * types.  GRAY uses scale[0] and bias[0]; uint8 ignores both. */
 enum { H264MI_TENSOR_RGB = 0, H264MI_TENSOR_GRAY = 1 };
-enum { H264MI_TENSOR_U8 = 0, H264MI_TENSOR_F16 = 1, H264MI_TENSOR_BF16 = 2, H264MI_TENSOR_F32 = 3 };
+enum { H264MI_TENSOR_U8 = 0, H264MI_TENSOR_F16 = 1, H264MI_TENSOR_BF16 = 2, H264MI_TENSOR_F32 = 3,
+       H264MI_TENSOR_I16 = 4 };     /* int16: the MB side-information field below only */
 typedef struct { int x, y, cw, ch, mode, dtype; float scale[3], bias[3]; } h264mi_tensor_desc;
 /* NextPicture, the picture exported to device memory instead of copied to the
  * host: d_dst (on the decoder's GPU, a multiple of the element size) receives
@@ -162,6 +163,59 @@ typedef struct { h264mi_tensor_desc t; int ow, oh, filter; } h264mi_tensor_resiz
  * desc->t.cw == 0 takes the active SPS's crop window.  Otherwise as above. */
 H264SwDecRet H264SwDecNextPictureTensorResized(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
                                                const h264mi_tensor_resize_desc *desc, void *d_dst, void *hip_stream);
+/* Motion vectors and MB side information as a device tensor (mbinfo.hip, DESIGN
+ * 3.5d; elsewhere: ffmpeg's export_mvs).  The field lives on the luma 4x4-block
+ * grid of the MB-aligned picture, BW = 4 * w_mbs columns by BH = 4 * h_mbs
+ * rows.  Block (X, Y) belongs to MB (X >> 2, Y >> 2), record (Y >> 2) * w_mbs +
+ * (X >> 2) of the picture's MbRec batch (include/h264mi_records.h); with (x, y)
+ * = (X & 3, Y & 3) it is the record's z-scan block b = (y >> 1) * 8 + (x >> 1)
+ * * 4 + (y & 1) * 2 + (x & 1), in 8x8 partition b >> 2.  A channel is one
+ * integer v per block, of record r:
+ *   MVX, MVY    r.mv[b][0], r.mv[b][1] (quarter-pel) of MBT_INTER / MBT_SKIP; else 0
+ *   REF_IDX     MBT_INTER: (r.refidx >> 4 * (b >> 2)) & 15; MBT_SKIP: 0; else -1
+ *   REF_SLOT    r.ref[b >> 2] of MBT_INTER / MBT_SKIP; else -1
+ *   MB_TYPE     r.type (MBT_*, 0..4)
+ *   QP          r.qp
+ *   INTRA_MODE  MBT_I4x4: Intra4x4PredMode of the block, (r.i4[b >> 1] >> (b & 1)
+ *               * 4) & 15; MBT_I16: 16 + (r.pred & 3); else -1
+ *   CODED       bit b of r.cbits
+ *   SLICE       r.slice
+ * A record whose type byte is 255 carries no information (a frame slot no
+ * picture was decoded into, or one filled by a slot copy): MVX, MVY and CODED
+ * are 0 there, every other channel -1.
+ * The window (bx, by, bw, bh) is in blocks, anywhere inside BW x BH; ch[0 ..
+ * nch) are channel ids, any order, repeats allowed.  Elements: H264MI_TENSOR_I16
+ * (v's low 16 bits; scale and bias ignored) or F16 / BF16 / F32,
+ * fma((float)v, scale[c], bias[c]) of channel position c, converted as for
+ * h264mi_tensor_desc; U8 is refused. */
+enum { H264MI_MBINFO_MVX = 0, H264MI_MBINFO_MVY = 1, H264MI_MBINFO_REF_IDX = 2, H264MI_MBINFO_REF_SLOT = 3,
+       H264MI_MBINFO_MB_TYPE = 4, H264MI_MBINFO_QP = 5, H264MI_MBINFO_INTRA_MODE = 6, H264MI_MBINFO_CODED = 7,
+       H264MI_MBINFO_SLICE = 8, H264MI_MBINFO_NCHANNELS = 9 };
+#define H264MI_MBINFO_MAX_CH 16
+typedef struct {
+    int bx, by, bw, bh, nch, dtype;
+    int ch[16];
+    float scale[16], bias[16];
+} h264mi_mbinfo_desc;
+/* Keep every picture's record batch on the device until its frame slot is
+ * decoded into again (on != 0; 0 frees them), from the next picture on; it
+ * survives a change of picture size, and on a shared engine (h264mi_set_share)
+ * it switches retention on for the engine.  H264SWDEC_PARAM_ERR when the
+ * backend cannot keep records. */
+H264SwDecRet H264SwDecKeepMbInfo(H264SwDecInst decInst, u32 on);
+/* The field of the picture most recently delivered by any H264SwDecNextPicture*
+ * call of the instance, as (nch, bh, bw) elements at d_dst (on the decoder's
+ * GPU, a multiple of the element size), ordered on `hip_stream` as
+ * h264mi_engine_export_mbinfo orders it.  The DPB is not touched: the call goes
+ * with the picture, it does not replace it.  Valid until the next
+ * H264SwDecDecode, like pOutputPicture.  desc->bw == 0: the blocks covering the
+ * active SPS's crop window (x, y, cw, ch): bx = x >> 2, bw = ((x + cw + 3) >> 2)
+ * - bx, by and bh likewise.  H264SWDEC_PIC_RDY after an export, H264SWDEC_OK
+ * when no picture has been delivered (since the last H264SwDecDecode),
+ * H264SWDEC_PARAM_ERR -- nothing queued -- without H264SwDecKeepMbInfo, on a
+ * bad desc or d_dst and when the backend cannot export. */
+H264SwDecRet H264SwDecLastPictureMbInfo(H264SwDecInst decInst, const h264mi_mbinfo_desc *desc, void *d_dst,
+                                        void *hip_stream);
 /* Extension (no reference counterpart): where an instance's time went, in
  * seconds since H264SwDecInit -- host parse (NAL extraction, headers, CAVLC /
  * MB layer, DPB, concealment), record upload + kernel launch, waiting for the
@@ -367,6 +421,38 @@ int  h264mi_tensor_resize_device_pitch(const void *d_in, const size_t *in_offset
 int  h264mi_engine_export_tensor_resized(h264mi_engine *e, int n, const int *streams, const int *slots,
                                          const h264mi_tensor_resize_desc *desc, void *d_out, size_t out_stride,
                                          void *hip_stream);
+/* the MB side-information field (h264mi_mbinfo_desc above) of npics record
+ * batches of w_mbs * h_mbs MbRec each, batch k starting rec_offsets[k] bytes (a
+ * host array of multiples of 96; any order, repeats allowed) after d_recs
+ * (16-byte aligned): picture k's (nch, bh, bw) elements, contiguous, at d_out +
+ * k * out_stride.  d_out and out_stride are multiples of the element size;
+ * where they and the row bytes are multiples of 16 a lane stores 16 bytes at a
+ * time.  Nothing outside the nch * bh * bw elements of each picture is written.
+ * Stateless; device pointers, asynchronous on `hip_stream`.  -1 on a bad
+ * argument, nothing launched.  For callers that hold their records on the
+ * device (h264mi_engine_decode_device*). */
+int  h264mi_mbinfo_device(const void *d_recs, const size_t *rec_offsets, int npics, int w_mbs, int h_mbs,
+                          const h264mi_mbinfo_desc *desc, void *d_out, size_t out_stride, void *hip_stream);
+/* record retention: on != 0 allocates one record batch per (stream, slot),
+ * filled with 0xFF bytes ("no information"); from then on h264mi_engine_decode
+ * and the H264SwDec* path copy each picture's records into the batch of the
+ * slot it is reconstructed into (one device-to-device copy on the engine's
+ * stream), so a slot's batch is that of the last reconstruction into it.  The
+ * decode_device* launches retain nothing: their callers own the records.  0
+ * (the default) waits for the engine's stream and frees the batches.  Returns
+ * 0, or -1 on a bad argument / HIP error. */
+int  h264mi_engine_keep_records(h264mi_engine *e, int on);
+/* refills the slot's batch with 0xFF bytes, behind the work queued on the
+ * engine (its picture did not come from a reconstruction); -1 when retention
+ * is off or on a bad stream or slot */
+int  h264mi_engine_forget_records(h264mi_engine *e, int stream, int slot);
+/* the kept batches of the slots (streams[k], slots[k]), k < n, as fields in the
+ * caller's memory, ordered as h264mi_engine_export_tensor orders its export (no
+ * host synchronisation; a later decode into one of the slots waits for the
+ * export).  -1 when retention is off, on a bad stream, slot or desc, or when
+ * d_out is not on the engine's device. */
+int  h264mi_engine_export_mbinfo(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                 const h264mi_mbinfo_desc *desc, void *d_out, size_t out_stride, void *hip_stream);
 int  h264mi_engine_sync(h264mi_engine *e);
 /* number of (launch, picture) slots flagged since the last call: residual
  * range errors (reference transform.c:181) or a bounded wait that expired;
