@@ -94,6 +94,15 @@ class MbInfoDesc(C.Structure):
                [("ch", C.c_int * 16), ("scale", C.c_float * 16), ("bias", C.c_float * 16)]
 
 
+class ResidualDesc(C.Structure):
+    """h264mi_residual_desc (include/h264mi.h)."""
+    _fields_ = [(n, C.c_int) for n in ("x", "y", "cw", "ch", "planes", "dtype")] + \
+               [("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
+# ResidualDesc.planes, by name
+RESID_PLANES = {"y": 0, "uv": 1, "yuv": 2}
+
 # channel ids of MbInfoDesc.ch, by name, and the int16 element type
 MBINFO_CHANNELS = {"mvx": 0, "mvy": 1, "ref_idx": 2, "ref_slot": 3, "mb_type": 4, "qp": 5, "intra_mode": 6,
                    "coded": 7, "slice": 8}
@@ -241,6 +250,18 @@ def mi() -> C.CDLL:
         L.H264SwDecKeepMbInfo.restype = i32
         L.H264SwDecLastPictureMbInfo.argtypes = [vp, md, vp, vp]
         L.H264SwDecLastPictureMbInfo.restype = i32
+    if hasattr(L, "h264mi_residual_device"):                # (optional, as above)
+        rs = C.POINTER(ResidualDesc)
+        L.h264mi_residual_device.argtypes = [vp, C.POINTER(sz), vp, C.POINTER(u32), sz, i32, i32, i32, rs, vp, sz, vp]
+        L.h264mi_residual_device.restype = i32
+        L.h264mi_engine_keep_coefs.argtypes = [vp, i32]
+        L.h264mi_engine_keep_coefs.restype = i32
+        L.h264mi_engine_export_residual.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), rs, vp, sz, vp]
+        L.h264mi_engine_export_residual.restype = i32
+        L.H264SwDecKeepResidual.argtypes = [vp, u32]
+        L.H264SwDecKeepResidual.restype = i32
+        L.H264SwDecLastPictureResidual.argtypes = [vp, rs, vp, vp]
+        L.H264SwDecLastPictureResidual.restype = i32
     L.h264mi_engine_sync.argtypes = [vp]
     L.h264mi_engine_sync.restype = i32
     L.h264mi_engine_kernel.argtypes = [vp]

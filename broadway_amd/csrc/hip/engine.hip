@@ -8,6 +8,7 @@
 #include "tensor.hip"
 #include "resize.hip"
 #include "mbinfo.hip"
+#include "residual.hip"
 #include "conceal.hip"
 #include <hip/hip_ext.h>
 
@@ -89,7 +90,11 @@ struct h264mi_engine {
     int tev_stride, tev_seq;  // record every tev_stride-th launch (h264mi_engine_set_timing_stride)
     uint8_t *d_rgba;          // h264mi_engine_read_rgba / _read_crop staging (w*h*4 B, allocated on first use)
     hipEvent_t ev_exp_in, ev_exp_out;   // h264mi_engine_export_tensor: the caller's stream -> ours -> the caller's (created on first use)
-    MbRec *d_keep;            // h264mi_engine_keep_records: per (stream, slot) the records of the last reconstruction into it (NULL: off)
+    MbRec *d_keep;            // h264mi_engine_keep_records: per (stream, slot) the records of the last reconstruction into it (NULL: off),
+                              // and one more batch that stays 0xFF ("no information")
+    int keep_rec;             // the caller's own switch (d_keep is also held while d_keepc is)
+    int16_t *d_keepc;         // h264mi_engine_keep_coefs: per (stream, slot) that reconstruction's coefficient blocks (NULL: off)
+    uint8_t *keepc_ok;        // per (stream, slot): d_keepc holds the blocks d_keep's records index (host)
     int steps;                // pictures per stream per launch (h264mi_engine_set_steps)
     unsigned long long *d_prog;   // per picture row of a launch, per row wave: {MBs stored, epoch} (frame-pipelined launches)
     unsigned *d_done;             // per picture row of a launch: epoch once the row is stored
@@ -292,6 +297,8 @@ extern "C" void h264mi_engine_destroy(h264mi_engine *e)
     free_pic_buffers(e);
     (void)hipFree(e->d_rgba);
     (void)hipFree(e->d_keep);
+    (void)hipFree(e->d_keepc);
+    free(e->keepc_ok);
     (void)hipFree(e->d_frames); (void)hipFree(e->d_prof); (void)hipFree(e->d_rec); (void)hipFree(e->d_coef);
     (void)hipFree(e->d_pics); (void)hipFree(e->d_gjunk);
     (void)hipHostFree(e->h_rec); (void)hipHostFree(e->h_coef); (void)hipHostFree(e->h_pics);
@@ -575,6 +582,29 @@ static int keep_batch(h264mi_engine *e, int npics, const int *stream, const int 
     return 0;
 }
 
+// coefficient retention (h264mi_engine_keep_coefs): a kept batch holds the
+// worst case of every MB -- 16 luma, 8 chroma AC, 1 luma DC and 2 chroma DC
+// blocks (I_PCM's 12 fit)
+#define KEEP_COEF_MB 27
+static size_t keepc_cap(const h264mi_engine *e) { return (size_t)KEEP_COEF_MB * e->nmbs; }
+
+// the same for the uploaded pool: picture i's ncoef[i] blocks, which follow
+// those of the pictures before it in d_coef, to the start of its slot's kept
+// batch (the records are picture-relative: the kept base is 0).  A picture
+// with more blocks than a batch holds is not kept and its slot exports zeros.
+static int keep_coef_batch(h264mi_engine *e, int npics, const int *stream, const int *cur_slot, const uint32_t *ncoef)
+{
+    size_t cbase = 0;
+    for (int i = 0; i < npics; cbase += ncoef[i++]) {
+        const size_t k = (size_t)stream[i] * e->nslots + cur_slot[i];
+        e->keepc_ok[k] = ncoef[i] <= keepc_cap(e);
+        if (e->keepc_ok[k] && ncoef[i])
+            HIPCHECK(hipMemcpyAsync(e->d_keepc + k * keepc_cap(e) * 16, e->d_coef + cbase * 16, (size_t)ncoef[i] * 32,
+                                    hipMemcpyDeviceToDevice, e->st));
+    }
+    return 0;
+}
+
 // intra_heavy: the batch's launch shape hint when the caller knows it (the
 // host path counts intra MBs while parsing); -1: derive it from the records
 
@@ -630,7 +660,8 @@ int engine_decode_host(h264mi_engine *e, int npics, const int *stream, const int
     for (int i = 0; i < npics && !heavy && intra_heavy < 0; i++) heavy = (e->h_pics[i].flags & PD_INTRA_HEAVY) != 0;
     e->launch_intra = heavy;
     if (launch_batch(e, npics, 1, e->d_rec, e->d_coef, e->d_pics, NULL, NULL, NULL)) return -1;
-    return e->d_keep ? keep_batch(e, npics, stream, cur_slot) : 0;
+    if (e->d_keep && keep_batch(e, npics, stream, cur_slot)) return -1;
+    return e->d_keepc ? keep_coef_batch(e, npics, stream, cur_slot, ncoef) : 0;
 }
 
 int engine_decode_direct(h264mi_engine *e, int stream, int cur_slot, const void *rec, const int16_t *coef,
@@ -666,7 +697,8 @@ int engine_decode_direct(h264mi_engine *e, int stream, int cur_slot, const void 
     HIPCHECK(hipEventRecord(e->ev_staged, e->st));
     e->launch_intra = intra_heavy >= 0 ? intra_heavy : (pd.flags & PD_INTRA_HEAVY) != 0;
     if (launch_batch(e, 1, 1, e->d_rec, e->d_coef, e->d_pics, NULL, NULL, NULL)) return -1;
-    return e->d_keep ? keep_batch(e, 1, &stream, &cur_slot) : 0;
+    if (e->d_keep && keep_batch(e, 1, &stream, &cur_slot)) return -1;
+    return e->d_keepc ? keep_coef_batch(e, 1, &stream, &cur_slot, &ncoef) : 0;
 }
 
 int engine_records_wait(h264mi_engine *e)
@@ -1255,12 +1287,15 @@ extern "C" int h264mi_mbinfo_device(const void *d_recs, const size_t *rec_offset
 // Record retention: one batch per (stream, slot), 0xFF-filled ("no
 // information") until a reconstruction into the slot copies its records there
 // (keep_batch).  Off waits for the engine's stream (exports run on it) and frees.
-extern "C" int h264mi_engine_keep_records(h264mi_engine *e, int on)
+// (One batch more than the slots: it is never copied into, and
+// h264mi_engine_export_residual reads it for a slot whose coefficients it does
+// not hold.)  keep_hold is the switch itself; the records are held while the
+// caller's switch or coefficient retention is on.
+static int keep_hold(h264mi_engine *e, int on)
 {
-    if (!e) return -1;
     if ((on != 0) == (e->d_keep != NULL)) return 0;
     HIPCHECK(hipSetDevice(e->dev));
-    const size_t bytes = sizeof(MbRec) * e->nmbs * e->nslots * e->nstreams;
+    const size_t bytes = sizeof(MbRec) * e->nmbs * ((size_t)e->nslots * e->nstreams + 1);
     if (on) {
         HIPCHECK(hipMalloc(&e->d_keep, bytes));
         if (hipMemsetAsync(e->d_keep, 0xFF, bytes, e->st) != hipSuccess) {
@@ -1276,10 +1311,48 @@ extern "C" int h264mi_engine_keep_records(h264mi_engine *e, int on)
     return 0;
 }
 
+extern "C" int h264mi_engine_keep_records(h264mi_engine *e, int on)
+{
+    if (!e) return -1;
+    e->keep_rec = on != 0;
+    return keep_hold(e, e->keep_rec || e->d_keepc);
+}
+
+// Coefficient retention: one worst-case batch per (stream, slot), filled by
+// keep_coef_batch; it holds the records as well while it is on.  A slot's
+// blocks count only with the records of the same reconstruction, so switching
+// on starts with no slot valid.  Off waits for the engine's stream and frees.
+extern "C" int h264mi_engine_keep_coefs(h264mi_engine *e, int on)
+{
+    if (!e) return -1;
+    if ((on != 0) == (e->d_keepc != NULL)) return 0;
+    HIPCHECK(hipSetDevice(e->dev));
+    if (on) {
+        const size_t nb = (size_t)e->nslots * e->nstreams;
+        if (keep_hold(e, 1)) return -1;
+        e->keepc_ok = (uint8_t *)calloc(nb, 1);
+        if (!e->keepc_ok || hipMalloc(&e->d_keepc, nb * keepc_cap(e) * 32) != hipSuccess) {
+            free(e->keepc_ok);
+            e->keepc_ok = NULL;
+            e->d_keepc = NULL;
+            (void)keep_hold(e, e->keep_rec);
+            return -1;
+        }
+        return 0;
+    }
+    HIPCHECK(hipStreamSynchronize(e->st));
+    (void)hipFree(e->d_keepc);
+    free(e->keepc_ok);
+    e->d_keepc = NULL;
+    e->keepc_ok = NULL;
+    return keep_hold(e, e->keep_rec);
+}
+
 extern "C" int h264mi_engine_forget_records(h264mi_engine *e, int stream, int slot)
 {
     if (!e || !e->d_keep || stream < 0 || stream >= e->nstreams || slot < 0 || slot >= e->nslots) return -1;
     HIPCHECK(hipSetDevice(e->dev));
+    if (e->keepc_ok) e->keepc_ok[(size_t)stream * e->nslots + slot] = 0;
     HIPCHECK(hipMemsetAsync(e->d_keep + ((size_t)stream * e->nslots + slot) * e->nmbs, 0xFF, sizeof(MbRec) * e->nmbs, e->st));
     return 0;
 }
@@ -1309,6 +1382,102 @@ extern "C" int h264mi_engine_export_mbinfo(h264mi_engine *e, int n, const int *s
             off[k] = sizeof(MbRec) * e->nmbs * ((size_t)streams[k0 + k] * e->nslots + slots[k0 + k]);
         rc = h264mi_mbinfo_device(e->d_keep, off, m, e->w, e->h, desc, (uint8_t *)d_out + (size_t)k0 * out_stride,
                                   out_stride, e->st);
+    }
+    // (also after a failed launch: whatever reached our stream stays ordered)
+    HIPCHECK(hipEventRecord(e->ev_exp_out, e->st));
+    HIPCHECK(hipStreamWaitEvent((hipStream_t)stream, e->ev_exp_out, 0));
+    return rc;
+}
+
+// a residual descriptor h264mi_residual_device accepts on a w_mbs x h_mbs picture
+static bool residual_desc_ok(const h264mi_residual_desc *d, int w_mbs, int h_mbs)
+{
+    if (!d || d->x < 0 || d->y < 0 || d->cw < 1 || d->ch < 1 || d->cw > 16 * w_mbs - d->x || d->ch > 16 * h_mbs - d->y ||
+        (d->planes != H264MI_RESID_Y && d->planes != H264MI_RESID_UV && d->planes != H264MI_RESID_YUV) ||
+        (d->dtype != H264MI_TENSOR_F16 && d->dtype != H264MI_TENSOR_BF16 && d->dtype != H264MI_TENSOR_F32 &&
+         d->dtype != H264MI_TENSOR_I16))
+        return false;
+    return d->planes != H264MI_RESID_UV || !((d->x | d->y | d->cw | d->ch) & 1);
+}
+
+// The decoded residual as planar tensors (residual.hip): the window desc->(x,
+// y, cw, ch), in luma samples of the MB-aligned picture, of the npics pictures
+// whose record batches (w_mbs * h_mbs MbRec each) start rec_offsets[k] bytes
+// after d_recs and whose coefficient blocks start coef_bases[k] blocks after
+// d_coef, a pool of coef_blocks blocks; picture k's planes, contiguous, at
+// d_out + k * out_stride; device pointers, asynchronous on `stream`;
+// RESID_MAX_PICS pictures per launch.  -1 (nothing launched) on a bad argument.
+extern "C" int h264mi_residual_device(const void *d_recs, const size_t *rec_offsets, const void *d_coef,
+                                      const uint32_t *coef_bases, size_t coef_blocks, int npics, int w_mbs, int h_mbs,
+                                      const h264mi_residual_desc *desc, void *d_out, size_t out_stride, void *stream)
+{
+    static_assert(H264MI_RESID_Y == RESID_Y && H264MI_RESID_UV == RESID_UV && H264MI_RESID_YUV == RESID_YUV,
+                  "include/h264mi.h and residual.hip name the same planes");
+    if (!d_recs || !rec_offsets || !d_coef || !coef_bases || !d_out || npics < 1 || w_mbs < 1 || h_mbs < 1 ||
+        w_mbs > 65535 || h_mbs > 65535 || (((size_t)(uintptr_t)d_recs | (size_t)(uintptr_t)d_coef) & 15) ||
+        !residual_desc_ok(desc, w_mbs, h_mbs))
+        return -1;
+    for (int k = 0; k < npics; k++)
+        if (rec_offsets[k] % sizeof(MbRec)) return -1;
+    const size_t es = (size_t)tensor_elem_size(desc->dtype);
+    if (((size_t)(uintptr_t)d_out | out_stride) & (es - 1)) return -1;
+    const size_t ow = (size_t)(desc->planes == H264MI_RESID_UV ? desc->cw / 2 : desc->cw);
+    const bool v16 = !(((size_t)(uintptr_t)d_out | out_stride | ow * es) & 15);
+    residual_args a;
+    a.rec = (const uint8_t *)d_recs;
+    a.coef = (const int16_t *)d_coef;
+    a.coef_blocks = coef_blocks;
+    a.w_mbs = w_mbs;
+    a.x = desc->x; a.y = desc->y; a.cw = desc->cw; a.ch = desc->ch; a.planes = desc->planes;
+    a.out_stride = out_stride;
+    for (int c = 0; c < 3; c++) { a.scale[c] = desc->scale[c]; a.bias[c] = desc->bias[c]; }
+    for (int k0 = 0; k0 < npics; k0 += RESID_MAX_PICS) {
+        const int n = npics - k0 < RESID_MAX_PICS ? npics - k0 : RESID_MAX_PICS;
+        for (int k = 0; k < RESID_MAX_PICS; k++) {
+            a.off[k] = k < n ? rec_offsets[k0 + k] : 0;
+            a.cbase[k] = k < n ? coef_bases[k0 + k] : 0;
+        }
+        a.out = (uint8_t *)d_out + (size_t)k0 * out_stride;
+        residual_launch(desc->dtype, v16, n, (hipStream_t)stream, a);
+        HIPCHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+// The kept records and coefficients of the slots (streams[k], slots[k]) as
+// residual tensors in the caller's memory, ordered like
+// h264mi_engine_export_mbinfo.  A slot whose coefficients are not held (nothing
+// decoded into it since retention went on, forgotten, or more blocks than a
+// batch holds) reads the spare 0xFF record batch: zeros.
+extern "C" int h264mi_engine_export_residual(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                             const h264mi_residual_desc *desc, void *d_out, size_t out_stride,
+                                             void *stream)
+{
+    if (!e || !e->d_keepc || !e->d_keep || n < 1 || !streams || !slots || !d_out || !residual_desc_ok(desc, e->w, e->h))
+        return -1;
+    for (int k = 0; k < n; k++)
+        if (streams[k] < 0 || streams[k] >= e->nstreams || slots[k] < 0 || slots[k] >= e->nslots) return -1;
+    const size_t es = (size_t)tensor_elem_size(desc->dtype);
+    if (((size_t)(uintptr_t)d_out | out_stride) & (es - 1)) return -1;
+    if (h264mi_pointer_device(d_out) != e->dev) return -1;
+    HIPCHECK(hipSetDevice(e->dev));
+    if (!e->ev_exp_in) HIPCHECK(hipEventCreateWithFlags(&e->ev_exp_in, hipEventDisableTiming));
+    if (!e->ev_exp_out) HIPCHECK(hipEventCreateWithFlags(&e->ev_exp_out, hipEventDisableTiming));
+    HIPCHECK(hipEventRecord(e->ev_exp_in, (hipStream_t)stream));
+    HIPCHECK(hipStreamWaitEvent(e->st, e->ev_exp_in, 0));
+    const size_t nb = (size_t)e->nslots * e->nstreams;
+    int rc = 0;
+    for (int k0 = 0; k0 < n && !rc; k0 += RESID_MAX_PICS) {
+        size_t off[RESID_MAX_PICS];
+        uint32_t cbase[RESID_MAX_PICS];
+        const int m = n - k0 < RESID_MAX_PICS ? n - k0 : RESID_MAX_PICS;
+        for (int k = 0; k < m; k++) {
+            const size_t b = (size_t)streams[k0 + k] * e->nslots + slots[k0 + k];
+            off[k] = sizeof(MbRec) * e->nmbs * (e->keepc_ok[b] ? b : nb);
+            cbase[k] = (uint32_t)(b * keepc_cap(e));
+        }
+        rc = h264mi_residual_device(e->d_keep, off, e->d_keepc, cbase, nb * keepc_cap(e), m, e->w, e->h, desc,
+                                    (uint8_t *)d_out + (size_t)k0 * out_stride, out_stride, e->st);
     }
     // (also after a failed launch: whatever reached our stream stays ordered)
     HIPCHECK(hipEventRecord(e->ev_exp_out, e->st));
@@ -1443,7 +1612,7 @@ int engine_reuse(h264mi_engine *e)
     e->err_bits = 0;          // the previous owner's device / checker flags
     e->steps = 1;
     e->last_kernel = NULL;
-    if (h264mi_engine_keep_records(e, 0)) return -1;      // the previous owner's retention
+    if (h264mi_engine_keep_coefs(e, 0) || h264mi_engine_keep_records(e, 0)) return -1;      // the previous owner's retention
     // the epoch keeps counting: the mailboxes hold tags of earlier launches only
     HIPCHECK(hipMemsetAsync(e->d_frames, 0, e->frame_bytes * e->nslots * e->nstreams, e->st));
     return 0;

@@ -145,7 +145,7 @@ H264SwDecRet H264SwDecDecode(H264SwDecInst decInst, H264SwDecInput *pInput, H264
     u8 *p = pInput->pStream;
     pOutput->pStrmCurrPos = NULL;
     c->dec.intra_conceal = (int)pInput->intraConcealmentMethod;
-    c->dec.last_out_slot1 = 0;      /* H264SwDecLastPictureMbInfo: this call may decode into that picture's slot */
+    c->dec.last_out_slot1 = 0;      /* H264SwDecLastPictureMbInfo / Residual: this call may decode into that picture's slot */
     do {
         int r;
         uint32_t nread = 0;
@@ -384,6 +384,50 @@ H264SwDecRet H264SwDecLastPictureMbInfo(H264SwDecInst decInst, const h264mi_mbin
     if (m.bx < 0 || m.by < 0 || m.bw < 1 || m.bh < 1 || m.bw > bw_all - m.bx || m.bh > bh_all - m.by)
         return H264SWDEC_PARAM_ERR;
     if (c->dec.be.export_mbinfo(c->dec.be.ctx, c->dec.last_out_slot1 - 1, &m, d_dst, hip_stream))
+        return H264SWDEC_PARAM_ERR;         /* (d_dst not on the decoder's GPU) */
+    return H264SWDEC_PIC_RDY;
+}
+
+/* Coefficient retention for H264SwDecLastPictureResidual (include/h264mi.h) */
+H264SwDecRet H264SwDecKeepResidual(H264SwDecInst decInst, u32 on)
+{
+    if (decInst == NULL) return H264SWDEC_PARAM_ERR;
+    DecContainer *c = (DecContainer *)decInst;
+    if (!c->dec.be.keep_coefs || !c->dec.be.export_residual) return H264SWDEC_PARAM_ERR;
+    if (c->dec.be.keep_coefs(c->dec.be.ctx, on != 0)) return H264SWDEC_PARAM_ERR;
+    c->dec.keep_residual = on != 0;
+    return H264SWDEC_OK;
+}
+
+/* The residual of the picture the last H264SwDecNextPicture* call delivered
+ * (include/h264mi.h); desc->cw == desc->ch == 0: the active SPS's crop window.
+ * The DPB is not touched.  Everything the export can refuse is checked before
+ * anything is queued. */
+H264SwDecRet H264SwDecLastPictureResidual(H264SwDecInst decInst, const h264mi_residual_desc *desc, void *d_dst,
+                                          void *hip_stream)
+{
+    if (decInst == NULL || desc == NULL || d_dst == NULL) return H264SWDEC_PARAM_ERR;
+    DecContainer *c = (DecContainer *)decInst;
+    if (!c->dec.be.export_residual || !c->dec.keep_residual) return H264SWDEC_PARAM_ERR;
+    h264mi_residual_desc m = *desc;
+    if ((m.planes != H264MI_RESID_Y && m.planes != H264MI_RESID_UV && m.planes != H264MI_RESID_YUV) ||
+        (m.dtype != H264MI_TENSOR_F16 && m.dtype != H264MI_TENSOR_BF16 && m.dtype != H264MI_TENSOR_F32 &&
+         m.dtype != H264MI_TENSOR_I16))
+        return H264SWDEC_PARAM_ERR;
+    if ((size_t)(uintptr_t)d_dst & (m.dtype == H264MI_TENSOR_F32 ? 3u : 1u)) return H264SWDEC_PARAM_ERR;
+    const Sps *s = h264dec_active_sps(&c->dec);
+    if (!s || !c->dec.last_out_slot1) return H264SWDEC_OK;      /* no picture delivered */
+    const int w = 16 * (int)s->w_mbs, h = 16 * (int)s->h_mbs;
+    if (m.cw == 0 && m.ch == 0) {
+        m.x = s->crop ? 2 * (int)s->crop_l : 0;
+        m.y = s->crop ? 2 * (int)s->crop_t : 0;
+        m.cw = w - m.x - (s->crop ? 2 * (int)s->crop_r : 0);
+        m.ch = h - m.y - (s->crop ? 2 * (int)s->crop_b : 0);
+    }
+    if (m.x < 0 || m.y < 0 || m.cw < 1 || m.ch < 1 || m.cw > w - m.x || m.ch > h - m.y ||
+        (m.planes == H264MI_RESID_UV && ((m.x | m.y | m.cw | m.ch) & 1)))
+        return H264SWDEC_PARAM_ERR;
+    if (c->dec.be.export_residual(c->dec.be.ctx, c->dec.last_out_slot1 - 1, &m, d_dst, hip_stream))
         return H264SWDEC_PARAM_ERR;         /* (d_dst not on the decoder's GPU) */
     return H264SWDEC_PIC_RDY;
 }

@@ -60,6 +60,11 @@ typedef struct H264Backend {
      * desc (a checked h264mi_mbinfo_desc) into device memory d_dst, ordered on
      * hip_stream like export_tensor; 0 ok, -1 failure */
     int  (*export_mbinfo)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
+    /* optional: the same for each picture's coefficient blocks (and its
+     * records), and slot's kept picture as the residual tensor of desc (a
+     * checked h264mi_residual_desc) */
+    int  (*keep_coefs)(void *ctx, int on);
+    int  (*export_residual)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
     /* optional: host memory for the output frames (pinned by the HIP
      * backend, so each picture's D2H copy runs at DMA speed); NULL: malloc */
     void *(*host_alloc)(void *ctx, size_t bytes);
@@ -140,6 +145,7 @@ typedef struct H264Dec {
      * picture the last next_output of any kind delivered, plus one (0: none
      * since the last H264SwDecDecode) */
     int      keep_mbinfo;
+    int      keep_residual;     /* the same for the coefficients (H264SwDecKeepResidual) */
     int      last_out_slot1;
     /* statistics */
     uint64_t pics_decoded, alg_ref_bytes, coded_blocks;

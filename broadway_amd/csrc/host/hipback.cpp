@@ -194,6 +194,7 @@ struct HipBackendCtx {
     int nslots;
     unsigned enq, synced;   // work items queued on the engine's stream / of those, waited for by hb_sync
     bool keep;              // keep_records: asked for by the decoder, applied to every engine configured from then on
+    bool keepc;             // keep_coefs: the same
 };
 
 extern "C" int h264mi_set_share(int lanes)
@@ -362,6 +363,41 @@ static int hb_export_mbinfo(void *vctx, int slot, const void *desc, void *d_dst,
     return 0;
 }
 
+// The same pair for the coefficients and the residual export.
+extern "C" int h264mi_engine_keep_coefs(h264mi_engine *e, int on) __attribute__((weak));
+extern "C" int h264mi_engine_export_residual(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                             const h264mi_residual_desc *desc, void *d_out, size_t out_stride,
+                                             void *hip_stream) __attribute__((weak));
+
+static int hb_keepc_apply(HipBackendCtx *c)
+{
+    if (!c->sh) return h264mi_engine_keep_coefs(c->e, c->keepc);
+    if (!c->keepc) return 0;
+    std::lock_guard<std::mutex> l(c->sh->mu);
+    return h264mi_engine_keep_coefs(c->e, 1);
+}
+
+static int hb_keep_coefs(void *vctx, int on)
+{
+    HipBackendCtx *c = (HipBackendCtx *)vctx;
+    c->keepc = on != 0;
+    return c->e ? hb_keepc_apply(c) : 0;
+}
+
+static int hb_export_residual(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
+{
+    HipBackendCtx *c = (HipBackendCtx *)vctx;
+    if (!c->e || slot < 0 || slot >= c->nslots) return -1;
+    const int lane = c->lane;
+    std::unique_lock<std::mutex> l;
+    if (c->sh) l = std::unique_lock<std::mutex>(c->sh->mu);
+    if (h264mi_engine_export_residual(c->e, 1, &lane, &slot, (const h264mi_residual_desc *)desc, d_dst, 0, hip_stream))
+        return -1;
+    if (c->sh) HIPCHECK(hipEventRecord(c->ev_last, engine_stream(c->e)));
+    c->enq++;
+    return 0;
+}
+
 static int hb_configure(void *vctx, int w_mbs, int h_mbs, int nslots)
 {
     HipBackendCtx *c = (HipBackendCtx *)vctx;
@@ -384,6 +420,7 @@ static int hb_configure(void *vctx, int w_mbs, int h_mbs, int nslots)
         c->e = engine_get(c->device, w_mbs, h_mbs, 1, nslots);
     }
     if (c->e && c->keep && hb_keep_apply(c)) return -1;
+    if (c->e && c->keepc && hb_keepc_apply(c)) return -1;
     return c->e && c->pref ? 0 : -1;
 }
 
@@ -680,11 +717,11 @@ static int hb_copy(void *vctx, int dst, int src)
         HIPCHECK(hipMemcpyAsync(h264mi_engine_frame_ptr(c->e, c->lane, dst), h264mi_engine_frame_ptr(c->e, c->lane, src),
                                 engine_slot_bytes(c->e), hipMemcpyDeviceToDevice, engine_stream(c->e)));
         // the copy is no reconstruction: dst's kept records say nothing about it
-        if (c->keep && h264mi_engine_forget_records && h264mi_engine_forget_records(c->e, c->lane, dst)) return -1;
+        if ((c->keep || c->keepc) && h264mi_engine_forget_records && h264mi_engine_forget_records(c->e, c->lane, dst)) return -1;
         HIPCHECK(hipEventRecord(c->ev_last, engine_stream(c->e)));
         return 0;
     }
-    if (c->keep && h264mi_engine_forget_records && h264mi_engine_forget_records(c->e, 0, dst)) return -1;
+    if ((c->keep || c->keepc) && h264mi_engine_forget_records && h264mi_engine_forget_records(c->e, 0, dst)) return -1;
     if (h264mi_engine_sync(c->e)) return -1;
     HIPCHECK(hipMemcpy(h264mi_engine_frame_ptr(c->e, 0, dst), h264mi_engine_frame_ptr(c->e, 0, src),
                        engine_slot_bytes(c->e), hipMemcpyDeviceToDevice));
@@ -743,6 +780,9 @@ extern "C" H264Backend h264mi_hip_backend_create(int device)
     const bool mbinfo = h264mi_engine_keep_records && h264mi_engine_export_mbinfo;
     be.keep_records = mbinfo ? hb_keep_records : NULL;
     be.export_mbinfo = mbinfo ? hb_export_mbinfo : NULL;
+    const bool resid = mbinfo && h264mi_engine_keep_coefs && h264mi_engine_export_residual;
+    be.keep_coefs = resid ? hb_keep_coefs : NULL;
+    be.export_residual = resid ? hb_export_residual : NULL;
     be.host_alloc = hb_host_alloc;
     be.host_free = hb_host_free;
     be.records_wait = hb_records_wait;

@@ -50,6 +50,17 @@ of the wasm glue of Decoder/src/Decoder.c:44-162:
   on torch's current stream; the arguments of ``Engine.to_mbinfo`` (default:
   channels ("mvx", "mvy"), int16).
 
+* ``residual: true`` or ``residual: {"planes": ..., "dtype": ..., "scale": ...,
+  "bias": ...}`` (an extension for device consumers; needs torch; combines
+  with every output mode above and with ``mbinfo``): the decoder keeps each
+  picture's coefficient blocks and records on the GPU, and before every
+  ``onPictureDecoded`` call ``decoder.residual`` is a new ``(1 | 2 | 3, rows,
+  columns)`` torch tensor on the decoder's GPU -- the delivered picture's
+  decoded residual over the SPS crop window ("uv": half of it each way; the
+  window must then be even), built by ``H264SwDecLastPictureResidual`` on
+  torch's current stream; the arguments of ``Engine.to_residual`` (default:
+  planes "y", int16).
+
 Unlike the reference module (a single global instance) every ``Decoder`` has
 its own H264SwDec instance, so several streams can be decoded side by side.
 Reconstruction always runs on the GPU through libh264mi.so; ``sliceMode``
@@ -103,6 +114,16 @@ class Decoder:
             from .engine import mbinfo_desc          # (imports torch)
             self._mbinfo = mbinfo_desc(opts.pop("channels", ("mvx", "mvy")), None, **opts)
             self._device = int(os.environ.get("H264MI_DEVICE") or 0)
+        self._residual = self.options.get("residual") or None
+        self.residual = None
+        if self._residual is not None:
+            opts = {} if self._residual is True else dict(self._residual)
+            unknown = set(opts) - {"planes", "dtype", "scale", "bias"}
+            if unknown:
+                raise ValueError(f"residual: unknown keys {sorted(unknown)}")
+            from .engine import residual_desc        # (imports torch)
+            self._residual = residual_desc(opts.pop("planes", "y"), None, **opts)
+            self._device = int(os.environ.get("H264MI_DEVICE") or 0)
         self._L = _lib.mi()
         inst = C.c_void_p()
         ret = self._L.H264SwDecInit(C.byref(inst), 0)
@@ -113,6 +134,10 @@ class Decoder:
                                          self._L.H264SwDecKeepMbInfo(inst, 1) != _lib.H264SWDEC_OK):
             self.close()
             raise RuntimeError("mbinfo: the backend cannot keep MB records (there is no host fallback)")
+        if self._residual is not None and (not hasattr(self._L, "H264SwDecKeepResidual") or
+                                           self._L.H264SwDecKeepResidual(inst, 1) != _lib.H264SWDEC_OK):
+            self.close()
+            raise RuntimeError("residual: the backend cannot keep coefficients (there is no host fallback)")
         self._buf = (C.c_uint8 * STREAM_BUFFER_SIZE)()
         self._info = _lib.H264SwDecInfo()
         self._pic = _lib.H264SwDecPicture()
@@ -231,7 +256,27 @@ class Decoder:
             raise RuntimeError(f"mbinfo: the backend cannot export the MB records ({ret}; there is no host fallback)")
         return out
 
+    def _export_residual(self):
+        """The delivered picture's residual over the crop window (the window
+        H264SwDecLastPictureResidual takes for cw == ch == 0)."""
+        import torch
+        desc, npl, dtype = self._residual
+        i = self._info
+        cw, ch = ((i.cropParams.cropOutWidth, i.cropParams.cropOutHeight) if i.croppingFlag
+                  else (i.picWidth, i.picHeight))
+        hs = 1 if desc.planes == _lib.RESID_PLANES["uv"] else 0
+        dev = torch.device("cuda", self._device)
+        with torch.cuda.device(dev):
+            out = torch.empty((npl, ch >> hs, cw >> hs), dtype=dtype, device=dev)
+        ret = self._L.H264SwDecLastPictureResidual(self._inst, C.byref(desc), out.data_ptr(),
+                                                   torch.cuda.current_stream(dev).cuda_stream)
+        if ret != _lib.H264SWDEC_PIC_RDY:
+            raise RuntimeError(f"residual: the backend cannot export the residual ({ret}; there is no host fallback)")
+        return out
+
     def _emit(self, pic, rgba=None) -> None:
+        if self._residual is not None:
+            self.residual = self._export_residual()
         if self._mbinfo is not None:
             self.mbinfo = self._export_mbinfo()
         w, h = self._out_size()

@@ -133,6 +133,51 @@ def mbinfo_desc(channels, window=None, dtype=None, scale=None, bias=None):
     return d, len(channels), dtype
 
 
+def residual_desc(planes="y", window=None, dtype=None, scale=None, bias=None):
+    """(``_lib.ResidualDesc``, number of planes, torch dtype) of an export of
+    the decoded residual (Engine.to_residual, Decoder's ``residual`` option;
+    include/h264mi.h defines the field): ``planes`` is "y" (one plane), "uv"
+    (Cb and Cr at half resolution) or "yuv" (three planes at luma resolution,
+    chroma by nearest neighbour); window = (x, y, cw, ch) in luma samples of
+    the MB-aligned picture, all even for "uv", or None for the decoder's SPS
+    crop window (cw = ch = 0 in the descriptor).  ``dtype``: torch.int16 (the
+    default; the integer itself) or float16 / bfloat16 / float32, ``fma(v,
+    scale[c], bias[c])`` of plane position c; scale and bias are scalars or
+    one value per plane, default 1 and 0."""
+    import torch
+    if planes not in _lib.RESID_PLANES:
+        raise ValueError(f"planes {planes!r}: one of {sorted(_lib.RESID_PLANES)}")
+    np_ = {"y": 1, "uv": 2, "yuv": 3}[planes]
+    dtype = torch.int16 if dtype is None else dtype
+    dts = {torch.int16: _lib.TENSOR_I16, torch.float16: _lib.TENSOR_F16, torch.bfloat16: _lib.TENSOR_BF16,
+           torch.float32: _lib.TENSOR_F32}
+    if dtype not in dts:
+        raise ValueError(f"dtype {dtype}: one of torch.int16, float16, bfloat16, float32")
+
+    def per_plane(v, default, what):
+        if v is None:
+            return (default,) * np_
+        v = tuple(float(f) for f in v) if hasattr(v, "__len__") else (float(v),) * np_
+        if len(v) != np_:
+            raise ValueError(f"{what}: a scalar or one value per plane")
+        return v
+
+    d = _lib.ResidualDesc()
+    if window is not None:
+        try:
+            d.x, d.y, d.cw, d.ch = (int(v) for v in window)
+        except (TypeError, ValueError):
+            raise ValueError(f"window {window!r}: (x, y, cw, ch)") from None
+        if d.x < 0 or d.y < 0 or d.cw < 1 or d.ch < 1:
+            raise ValueError(f"window {tuple(window)}: x, y >= 0 and cw, ch >= 1 (luma samples)")
+        if planes == "uv" and (d.x | d.y | d.cw | d.ch) & 1:
+            raise ValueError(f"window {tuple(window)}: x, y, cw and ch are even for planes 'uv'")
+    d.planes, d.dtype = _lib.RESID_PLANES[planes], dts[dtype]
+    d.scale[:np_] = per_plane(scale, 1.0, "scale")
+    d.bias[:np_] = per_plane(bias, 0.0, "bias")
+    return d, np_, dtype
+
+
 @dataclass
 class CapturedPicture:
     rec: int            # host address of w*h MbRec
@@ -399,6 +444,53 @@ class Engine:
                                                C.byref(desc), out.data_ptr(),
                                                nch * desc.bh * desc.bw * out.element_size(), st.cuda_stream) != 0:
             raise RuntimeError("h264mi_engine_export_mbinfo failed (keep_records off, or stream, slot or window "
+                               "out of range?)")
+        return out
+
+    def keep_coefs(self, on: bool = True) -> None:
+        """Keep each picture's coefficient blocks, and its records, on the
+        device, per (stream, slot), from the next ``decode`` on (to_residual
+        reads them): 27 blocks of 32 bytes per MB and slot, 7.05 MB per 1080p
+        slot.  ``on=False`` waits for the engine, frees them and leaves the
+        records to ``keep_records``' own switch.  ``decode_device*`` launches
+        retain nothing."""
+        if self._L.h264mi_engine_keep_coefs(self._h, int(bool(on))) != 0:
+            raise RuntimeError("h264mi_engine_keep_coefs failed")
+
+    def to_residual(self, streams: Sequence[int], slots: Sequence[int], planes="y", window=None, dtype=None,
+                    scale=None, bias=None, out=None, stream=None):
+        """The decoded residual of the pictures last decoded into the slots
+        (streams[k], slots[k]) as one ``(n, 1 | 2 | 3, rows, columns)`` torch
+        tensor on ``cuda:{self.device}``: ``planes`` "y" and "yuv" give ``(ch,
+        cw)`` planes of ``window`` = (x, y, cw, ch) in luma samples (None: the
+        whole MB-aligned picture), "uv" ``(ch / 2, cw / 2)`` (``residual_desc``;
+        a slot nothing was decoded into reads as zeros).  Needs
+        ``keep_coefs()`` before the decodes.  ``out`` and ``stream`` as for
+        ``to_tensor``; the host is never synchronised."""
+        import torch
+        n = len(streams)
+        if n < 1 or len(slots) != n:
+            raise ValueError("streams and slots name the same, non-zero number of pictures")
+        if window is None:
+            window = (0, 0, self.w_mbs * 16, self.h_mbs * 16)
+        desc, npl, dtype = residual_desc(planes, window, dtype, scale, bias)
+        hs = 1 if planes == "uv" else 0
+        shape = (n, npl, desc.ch >> hs, desc.cw >> hs)
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = torch.empty(shape, dtype=dtype, device=dev)
+        elif tuple(out.shape) != shape or out.dtype != dtype or out.device != dev or not out.is_contiguous():
+            raise ValueError(f"out: a contiguous {dtype} tensor of shape {shape} on {dev} "
+                             f"(got {out.dtype} {tuple(out.shape)} on {out.device})")
+        cur = torch.cuda.current_stream(dev)
+        st = stream if stream is not None else cur
+        if st != cur:
+            out.record_stream(st)       # (the caching allocator: the block is in use on `stream` too)
+        if self._L.h264mi_engine_export_residual(self._h, n, (C.c_int * n)(*streams), (C.c_int * n)(*slots),
+                                                 C.byref(desc), out.data_ptr(),
+                                                 npl * shape[2] * shape[3] * out.element_size(), st.cuda_stream) != 0:
+            raise RuntimeError("h264mi_engine_export_residual failed (keep_coefs off, or stream, slot or window "
                                "out of range?)")
         return out
 

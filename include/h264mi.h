@@ -216,6 +216,58 @@ H264SwDecRet H264SwDecKeepMbInfo(H264SwDecInst decInst, u32 on);
  * bad desc or d_dst and when the backend cannot export. */
 H264SwDecRet H264SwDecLastPictureMbInfo(H264SwDecInst decInst, const h264mi_mbinfo_desc *desc, void *d_dst,
                                         void *hip_stream);
+/* The decoded residual as a device tensor (residual.hip): the
+ * prediction error the stream carries, which neither the reconstruction (clip
+ * and in-loop deblocking lose it) nor a frame difference gives back.  Three
+ * planes on the MB-aligned picture: Y 16 * h_mbs rows of 16 * w_mbs samples, Cb
+ * and Cr 8 * h_mbs rows of 8 * w_mbs each.  A sample is one integer v, of its
+ * MB's record r (include/h264mi_records.h) and its 4x4 block b, the r.cbits bit
+ * index: 0..15 luma in z-scan order, 16..19 Cb, 20..23 Cr.
+ *   r.type MBT_INTER, MBT_I4x4 or MBT_I16 and b in the residual mask -- the
+ *   blocks with bit b of r.cbits set, all 16 luma blocks of an MBT_I16 record
+ *   with bit 24 (luma DC) set, all of Cb with bit 25 and all of Cr with bit 26
+ *   (chroma DC) set: v is the sample of the block's inverse transform.  The
+ *   block's levels, if bit b is set, are dequantised from scan order (LevelScale
+ *   of qp % 6 shifted left by qp / 6, with r.qp for luma and r.qpc for chroma;
+ *   position 0 of an MBT_I16 luma block and of a chroma block carries no level);
+ *   position 0 is replaced by the block's output of the I16 luma-DC transform
+ *   (0 without bit 24) or of the chroma-DC transform (0 without the plane's
+ *   bit); then the 4x4 inverse transform with (x + 32) >> 6, all in 32-bit
+ *   integers (the reference's ProcessResidual: h264bsdProcessLumaDc,
+ *   h264bsdProcessChromaDc, h264bsdProcessBlock).
+ *   Every other block of those MBs, and every sample of MBT_SKIP, MBT_IPCM and
+ *   type-255 ("no information") records: v = 0.  Their cbits and coef are not
+ *   looked at.
+ * v is clamped to [-32768, 32767]; a stream the decoder accepts stays inside
+ * [-512, 511] (beyond it the picture is an error), so the clamp only makes
+ * every input well defined.
+ * planes: H264MI_RESID_Y one plane at full resolution; H264MI_RESID_UV two (Cb,
+ * Cr) at half resolution -- x, y, cw, ch are in luma samples and must all be
+ * even, the planes are ch / 2 rows of cw / 2; H264MI_RESID_YUV three at luma
+ * resolution, the chroma sample of luma (X, Y) being (X >> 1, Y >> 1).  The
+ * window (x, y, cw, ch) lies anywhere inside the MB-aligned picture.  Elements:
+ * H264MI_TENSOR_I16 (v) or F16 / BF16 / F32, fma((float)v, scale[c], bias[c])
+ * of plane position c, converted as for h264mi_tensor_desc; U8 is refused. */
+enum { H264MI_RESID_Y = 0, H264MI_RESID_UV = 1, H264MI_RESID_YUV = 2 };
+typedef struct { int x, y, cw, ch, planes, dtype; float scale[3], bias[3]; } h264mi_residual_desc;
+/* Keep every picture's coefficient blocks, and its records, on the device until
+ * its frame slot is decoded into again (on != 0; 0 frees them and leaves record
+ * retention as H264SwDecKeepMbInfo set it), from the next picture on.  It costs
+ * 27 blocks of 32 bytes per MB and frame slot (7.05 MB per 1080p slot); it
+ * survives a change of picture size, and on a shared engine it is only ever
+ * switched on.  H264SWDEC_PARAM_ERR when the backend cannot keep them. */
+H264SwDecRet H264SwDecKeepResidual(H264SwDecInst decInst, u32 on);
+/* The residual of the picture most recently delivered by any H264SwDecNextPicture*
+ * call of the instance, as its planes at d_dst (on the decoder's GPU, a multiple
+ * of the element size), ordered on `hip_stream` as h264mi_engine_export_residual
+ * orders it.  The DPB is not touched.  Valid until the next H264SwDecDecode.
+ * desc->cw == 0 and desc->ch == 0: the active SPS's crop window.
+ * H264SWDEC_PIC_RDY after an export, H264SWDEC_OK when no picture has been
+ * delivered (since the last H264SwDecDecode), H264SWDEC_PARAM_ERR -- nothing
+ * queued -- without H264SwDecKeepResidual, on a bad desc or d_dst and when the
+ * backend cannot export. */
+H264SwDecRet H264SwDecLastPictureResidual(H264SwDecInst decInst, const h264mi_residual_desc *desc, void *d_dst,
+                                          void *hip_stream);
 /* Extension (no reference counterpart): where an instance's time went, in
  * seconds since H264SwDecInit -- host parse (NAL extraction, headers, CAVLC /
  * MB layer, DPB, concealment), record upload + kernel launch, waiting for the
@@ -439,7 +491,8 @@ int  h264mi_mbinfo_device(const void *d_recs, const size_t *rec_offsets, int npi
  * slot it is reconstructed into (one device-to-device copy on the engine's
  * stream), so a slot's batch is that of the last reconstruction into it.  The
  * decode_device* launches retain nothing: their callers own the records.  0
- * (the default) waits for the engine's stream and frees the batches.  Returns
+ * (the default) waits for the engine's stream and frees the batches -- unless
+ * h264mi_engine_keep_coefs is on, which holds them until it goes off.  Returns
  * 0, or -1 on a bad argument / HIP error. */
 int  h264mi_engine_keep_records(h264mi_engine *e, int on);
 /* refills the slot's batch with 0xFF bytes, behind the work queued on the
@@ -453,6 +506,43 @@ int  h264mi_engine_forget_records(h264mi_engine *e, int stream, int slot);
  * d_out is not on the engine's device. */
 int  h264mi_engine_export_mbinfo(h264mi_engine *e, int n, const int *streams, const int *slots,
                                  const h264mi_mbinfo_desc *desc, void *d_out, size_t out_stride, void *hip_stream);
+/* the residual (h264mi_residual_desc above) of npics pictures of w_mbs * h_mbs
+ * MBs: picture k's record batch starts rec_offsets[k] bytes (a host array of
+ * multiples of 96) after d_recs, and its records' coef indices count from
+ * block coef_bases[k] (a host array) of the pool d_coef of coef_blocks blocks
+ * of 16 int16 (both pointers 16-byte aligned; any order, repeats allowed).
+ * Picture k's planes, contiguous, go to d_out + k * out_stride.  An MB whose
+ * blocks (coef_bases[k] + r.coef + the number of bits 0..26 set in r.cbits)
+ * would end beyond coef_blocks is not read and exports zeros.  d_out and
+ * out_stride are multiples of the element size; where they and a plane row's
+ * bytes are multiples of 16 a lane stores 16 bytes at a time.  Nothing outside
+ * each picture's planes is written.  Stateless; device pointers, asynchronous
+ * on `hip_stream`.  -1 on a bad argument, nothing launched. */
+int  h264mi_residual_device(const void *d_recs, const size_t *rec_offsets, const void *d_coef,
+                            const uint32_t *coef_bases, size_t coef_blocks, int npics, int w_mbs, int h_mbs,
+                            const h264mi_residual_desc *desc, void *d_out, size_t out_stride, void *hip_stream);
+/* coefficient retention: on != 0 allocates, per (stream, slot), one batch of the
+ * worst case of 27 blocks of 32 bytes per MB (16 luma, 8 chroma AC, 1 luma DC,
+ * 2 chroma DC; I_PCM's 12 fit) -- 7.05 MB per 1080p slot, just under 1 GB for
+ * eight streams of 17 slots -- and holds the records as h264mi_engine_keep_records
+ * does while it is on; from then on h264mi_engine_decode and the H264SwDec* path
+ * copy each picture's blocks into the batch of the slot it is reconstructed into
+ * (one more device-to-device copy on the engine's stream).  A picture with more
+ * blocks than a batch holds is not kept; its slot then exports zeros, like a slot
+ * nothing was decoded into and one h264mi_engine_forget_records was called for.
+ * The decode_device* launches retain nothing.  0 (the default: nothing is
+ * allocated or queued) waits for the engine's stream, frees the batches and
+ * leaves the records to h264mi_engine_keep_records' own switch.  Returns 0, or
+ * -1 on a bad argument / HIP error. */
+int  h264mi_engine_keep_coefs(h264mi_engine *e, int on);
+/* the kept pictures of the slots (streams[k], slots[k]), k < n, as residual
+ * tensors in the caller's memory, ordered as h264mi_engine_export_mbinfo orders
+ * its export (no host synchronisation; a later decode into one of the slots
+ * waits for the export).  -1 when coefficient retention is off, on a bad stream,
+ * slot or desc, or when d_out is not on the engine's device. */
+int  h264mi_engine_export_residual(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                   const h264mi_residual_desc *desc, void *d_out, size_t out_stride,
+                                   void *hip_stream);
 int  h264mi_engine_sync(h264mi_engine *e);
 /* number of (launch, picture) slots flagged since the last call: residual
  * range errors (reference transform.c:181) or a bounded wait that expired;
