@@ -74,7 +74,8 @@ class GenParams(C.Structure):
         "poc_type", "coef_pct", "level_tail_pct", "mv_jitter", "offpic_pct",
         "log2_max_frame_num", "poc_swap",
         "err_range_pct", "drop_slice_pct", "trunc_slice_pct", "drop_pic_pct", "gaps_allowed",
-        "nonref_pct", "ref_mod_pct", "mmco_pct", "lt_idr_pct", "crop_left", "crop_top")] + [("seed", C.c_uint64)]
+        "nonref_pct", "ref_mod_pct", "mmco_pct", "lt_idr_pct", "crop_left", "crop_top",
+        "vui_matrix", "vui_full_range")] + [("seed", C.c_uint64)]
 
 
 class TensorDesc(C.Structure):
@@ -110,6 +111,13 @@ MBINFO_MAX_CH = 16
 TENSOR_I16 = 4
 
 TENSOR_RGB, TENSOR_GRAY = 0, 1
+# the colour set of an RGB tensor, bits 8..11 of TensorDesc.mode, by name; with
+# "stream", bits 12..13 say what to take where the stream names no matrix
+TENSOR_COLOURS = {"reference": 0, "bt601-full": 1, "bt709": 2, "bt709-full": 3, "stream": 15}
+TENSOR_COLOUR_NAMES = ("reference", "bt601-full", "bt709", "bt709-full")
+TENSOR_COLOUR_STREAM = 15
+TENSOR_UNSPECIFIED = {"bt601": 0, "bt709": 1, "size": 2}
+TENSOR_COLOUR_SHIFT, TENSOR_UNSPEC_SHIFT = 8, 12
 RESIZE_TRIANGLE = 0
 RESIZE_MAX_DIM = 16384
 TENSOR_U8, TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 0, 1, 2, 3
@@ -228,6 +236,13 @@ def mi() -> C.CDLL:
         L.h264mi_engine_export_tensor.restype = i32
         L.H264SwDecNextPictureTensor.argtypes = [vp, C.POINTER(H264SwDecPicture), u32, td, vp, vp]
         L.H264SwDecNextPictureTensor.restype = i32
+    if hasattr(L, "h264mi_tensor_colour_coeffs"):       # (optional, as above)
+        L.h264mi_tensor_colour_coeffs.argtypes = [i32, C.POINTER(i32 * 6)]
+        L.h264mi_tensor_colour_coeffs.restype = i32
+        L.h264mi_tensor_colour_resolve.argtypes = [i32] * 5
+        L.h264mi_tensor_colour_resolve.restype = i32
+        L.H264SwDecLastTensorColour.argtypes = [vp]
+        L.H264SwDecLastTensorColour.restype = i32
     if hasattr(L, "h264mi_tensor_resize_device_pitch"):     # (optional, as above)
         rd = C.POINTER(TensorResizeDesc)
         L.h264mi_tensor_resize_device_pitch.argtypes = [vp, C.POINTER(sz), i32, i32, i32, i32, rd, vp, sz, vp]

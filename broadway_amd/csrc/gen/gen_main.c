@@ -16,7 +16,8 @@ static const struct { const char *n; size_t off; } kFields[] = {
     FIELD(qp_delta), FIELD(dbf_idc1_pct), FIELD(dbf_idc2_pct), FIELD(dbf_off),
     FIELD(num_ref_frames), FIELD(cip), FIELD(chroma_qp_offset), FIELD(poc_type),
     FIELD(coef_pct), FIELD(level_tail_pct), FIELD(mv_jitter), FIELD(offpic_pct),
-    FIELD(log2_max_frame_num), FIELD(crop_left), FIELD(crop_top)};
+    FIELD(log2_max_frame_num), FIELD(crop_left), FIELD(crop_top),
+    FIELD(vui_matrix), FIELD(vui_full_range)};
 
 int main(int argc, char **argv)
 {

@@ -273,7 +273,28 @@ static void write_sps(Gen *g)
         bw_ue(&bw, (uint32_t)(p->crop_left / 2)); bw_ue(&bw, (uint32_t)(p->crop_right / 2));
         bw_ue(&bw, (uint32_t)(p->crop_top / 2)); bw_ue(&bw, (uint32_t)(p->crop_bottom / 2));
     }
-    bw_put(&bw, 0, 1);             /* vui_parameters_present_flag */
+    bw_put(&bw, (uint32_t)(p->vui_matrix != 0), 1);     /* vui_parameters_present_flag */
+    if (p->vui_matrix) {
+        /* a VUI that carries a video signal type and nothing else */
+        const int desc = p->vui_matrix > 0;
+        bw_put(&bw, 0, 1);         /* aspect_ratio_info_present_flag */
+        bw_put(&bw, 0, 1);         /* overscan_info_present_flag */
+        bw_put(&bw, 1, 1);         /* video_signal_type_present_flag */
+        bw_put(&bw, 5, 3);         /* video_format: unspecified */
+        bw_put(&bw, (uint32_t)(p->vui_full_range != 0), 1);
+        bw_put(&bw, (uint32_t)desc, 1);                 /* colour_description_present_flag */
+        if (desc) {
+            bw_put(&bw, 2, 8);     /* colour_primaries: unspecified */
+            bw_put(&bw, 2, 8);     /* transfer_characteristics: unspecified */
+            bw_put(&bw, (uint32_t)(p->vui_matrix & 255), 8);
+        }
+        bw_put(&bw, 0, 1);         /* chroma_loc_info_present_flag */
+        bw_put(&bw, 0, 1);         /* timing_info_present_flag */
+        bw_put(&bw, 0, 1);         /* nal_hrd_parameters_present_flag */
+        bw_put(&bw, 0, 1);         /* vcl_hrd_parameters_present_flag */
+        bw_put(&bw, 0, 1);         /* pic_struct_present_flag */
+        bw_put(&bw, 0, 1);         /* bitstream_restriction_flag */
+    }
     bw_trailing(&bw);
     emit_nal(&g->out, 3, 7, &bw);
     bw_free(&bw);

@@ -56,6 +56,14 @@ typedef struct GenParams {
     /* SPS frame_crop_left_offset / frame_crop_top_offset, luma pixels (even);
      * both 0 leaves the stream byte-identical */
     int crop_left, crop_top;
+    /* SPS VUI colour signalling; both 0 leaves the stream byte-identical
+     * (vui_parameters_present_flag = 0).  vui_matrix > 0: a VUI whose only
+     * content is a video signal type (video_format 5) with a colour
+     * description: primaries and transfer 2 (unspecified) and this
+     * matrix_coefficients (1..255).  vui_matrix = -1: the video signal type
+     * without a colour description.  vui_full_range: its
+     * video_full_range_flag (ignored without a VUI). */
+    int vui_matrix, vui_full_range;
     uint64_t seed;
 } GenParams;
 

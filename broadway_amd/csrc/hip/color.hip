@@ -43,6 +43,47 @@ __device__ __forceinline__ void rgba_group_px(uint32_t y0, uint32_t y1, uint32_t
     }
 }
 
+// The same pixels with the colour set of the caller's choice (the tensor
+// exports): six integers (ky, k0, crv, cgu, cgv, cbu),
+//   a0 = ky Y + k0
+//   R = (a0 + crv (V - 128)) >> 10
+//   G = (a0 - cgu (U - 128) - cgv (V - 128)) >> 10
+//   B = (a0 + cbu (U - 128)) >> 10          (arithmetic shifts)
+// each clamped to [0, 255]; (1192, -1192 * 16, 1634, 400, 832, 2066) is
+// rgba_px.  The six are wave-uniform (kernel arguments, SGPRs), and a VALU
+// instruction of gfx9 reads one SGPR: k0 goes into the three chroma terms
+// of a 2x2 block (one multiply-add each with the addend in a VGPR, two for
+// G), so that a pixel's channel is one multiply-add ky * Y + term with ky its
+// only uniform operand.  Every product has 24-bit factors and every sum fits
+// 24 bits signed (|term| < 2^20, ky Y < 2^19).
+struct colour_set {
+    int ky, k0, crv, cgu, cgv, cbu;
+};
+
+__device__ __forceinline__ uint32_t rgba_px_set(int y, int ky, int cr, int cg, int cb)
+{
+    const int a = __mul24(ky, y);
+    const int r = med3i((a + cr) >> 10, 0, 255);
+    const int g = med3i((a + cg) >> 10, 0, 255);
+    const int b = med3i((a + cb) >> 10, 0, 255);
+    return 0xFF000000u | ((uint32_t)b << 16) | ((uint32_t)g << 8) | (uint32_t)r;
+}
+
+__device__ __forceinline__ void rgba_group_px_set(const colour_set &cs, uint32_t y0, uint32_t y1, uint32_t u2, uint32_t v2,
+                                                  uint32_t (&o0)[4], uint32_t (&o1)[4])
+{
+    const int ky = cs.ky, k0 = cs.k0, crv = cs.crv, ncgu = -cs.cgu, ncgv = -cs.cgv, cbu = cs.cbu;
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        const int u = (int)((u2 >> (8 * k)) & 255) - 128, v = (int)((v2 >> (8 * k)) & 255) - 128;
+        const int cr = __mul24(crv, v) + k0, cg = __mul24(ncgv, v) + (__mul24(ncgu, u) + k0), cb = __mul24(cbu, u) + k0;
+        o0[2 * k] = rgba_px_set((int)((y0 >> (16 * k)) & 255), ky, cr, cg, cb);
+        o0[2 * k + 1] = rgba_px_set((int)((y0 >> (16 * k + 8)) & 255), ky, cr, cg, cb);
+        o1[2 * k] = rgba_px_set((int)((y1 >> (16 * k)) & 255), ky, cr, cg, cb);
+        o1[2 * k + 1] = rgba_px_set((int)((y1 >> (16 * k + 8)) & 255), ky, cr, cg, cb);
+    }
+}
+
 // one 4-column group (2 chroma samples) of two rows
 __device__ __forceinline__ void rgba_group(const uint8_t *Y, const uint8_t *U, const uint8_t *V, uint8_t *O,
                                            int width, size_t yo, size_t co)

@@ -1087,14 +1087,31 @@ extern "C" int h264mi_engine_read_crop(h264mi_engine *e, int stream, int slot, i
     return 0;
 }
 
+// a mode the engine-level exports accept: RGB with a colour id 0..3 (bits 12
+// and 13 mean nothing without STREAM, which needs a stream: refused) or GRAY
+// with no colour bits, and no bit from 14 up
+static bool tensor_mode_ok(int mode)
+{
+    if (mode & ~0x3FFF) return false;
+    if (H264MI_TENSOR_LAYOUT(mode) == H264MI_TENSOR_GRAY) return mode == H264MI_TENSOR_GRAY;
+    return H264MI_TENSOR_LAYOUT(mode) == H264MI_TENSOR_RGB && H264MI_TENSOR_COLOUR(mode) < TENSOR_COLOUR_SETS;
+}
+
 // a window / mode / dtype a tensor export accepts (the window rules are
 // h264mi_crop_device_pitch's)
 static bool tensor_desc_ok(const h264mi_tensor_desc *t, int width, int height)
 {
     return t && t->x >= 0 && t->y >= 0 && t->cw > 0 && t->ch > 0 && !((t->x | t->y | t->cw | t->ch) & 1) &&
-           t->cw <= width - t->x && t->ch <= height - t->y &&
-           (t->mode == H264MI_TENSOR_RGB || t->mode == H264MI_TENSOR_GRAY) && t->dtype >= H264MI_TENSOR_U8 &&
-           t->dtype <= H264MI_TENSOR_F32;
+           t->cw <= width - t->x && t->ch <= height - t->y && tensor_mode_ok(t->mode) &&
+           t->dtype >= H264MI_TENSOR_U8 && t->dtype <= H264MI_TENSOR_F32;
+}
+
+extern "C" int h264mi_tensor_colour_coeffs(int id, int out[6])
+{
+    if (id < 0 || id >= TENSOR_COLOUR_SETS || !out) return -1;
+    const colour_set &c = tensor_colour_sets[id];
+    out[0] = c.ky; out[1] = c.k0; out[2] = c.crv; out[3] = c.cgu; out[4] = c.cgv; out[5] = c.cbu;
+    return 0;
 }
 
 // a resize descriptor h264mi_tensor_resize_device_pitch accepts
@@ -1117,8 +1134,9 @@ extern "C" int h264mi_tensor_device_pitch(const void *d_in, const size_t *in_off
 {
     static_assert(H264MI_TENSOR_RGB == TENSOR_RGB && H264MI_TENSOR_GRAY == TENSOR_GRAY &&
                       H264MI_TENSOR_U8 == TENSOR_U8 && H264MI_TENSOR_F16 == TENSOR_F16 &&
-                      H264MI_TENSOR_BF16 == TENSOR_BF16 && H264MI_TENSOR_F32 == TENSOR_F32,
-                  "include/h264mi.h and tensor.hip name the same modes and element types");
+                      H264MI_TENSOR_BF16 == TENSOR_BF16 && H264MI_TENSOR_F32 == TENSOR_F32 &&
+                      H264MI_TENSOR_COLOUR_BT709_FULL == TENSOR_COLOUR_SETS - 1,
+                  "include/h264mi.h and tensor.hip name the same modes, element types and colour sets");
     if (!d_in || !in_offsets || !d_out || width <= 0 || height <= 0 || ((width | height) & 1) || npics < 1 ||
         cpitch < width / 2 || !tensor_desc_ok(desc, width, height))
         return -1;
@@ -1131,11 +1149,14 @@ extern "C" int h264mi_tensor_device_pitch(const void *d_in, const size_t *in_off
     a.x = desc->x; a.y = desc->y; a.cw = desc->cw; a.ch = desc->ch;
     a.out_stride = out_stride;
     for (int p = 0; p < 3; p++) { a.scale[p] = desc->scale[p]; a.bias[p] = desc->bias[p]; }
+    // (set 0 runs the kernels with the reference's literals)
+    const int colour = H264MI_TENSOR_COLOUR(desc->mode);
+    a.col = tensor_colour_sets[colour];
     for (int k0 = 0; k0 < npics; k0 += TENSOR_MAX_PICS) {
         const int n = npics - k0 < TENSOR_MAX_PICS ? npics - k0 : TENSOR_MAX_PICS;
         for (int k = 0; k < TENSOR_MAX_PICS; k++) a.in_off[k] = k < n ? in_offsets[k0 + k] : 0;
         a.out = (uint8_t *)d_out + (size_t)k0 * out_stride;
-        tensor_launch(desc->mode, desc->dtype, v16, n, (hipStream_t)stream, a);
+        tensor_launch(H264MI_TENSOR_LAYOUT(desc->mode), desc->dtype, v16, colour != 0, n, (hipStream_t)stream, a);
         HIPCHECK(hipGetLastError());
     }
     return 0;
@@ -1164,11 +1185,13 @@ extern "C" int h264mi_tensor_resize_device_pitch(const void *d_in, const size_t 
     a.t.out_stride = out_stride;
     a.ow = desc->ow; a.oh = desc->oh;
     for (int p = 0; p < 3; p++) { a.t.scale[p] = t->scale[p]; a.t.bias[p] = t->bias[p]; }
+    const int colour = H264MI_TENSOR_COLOUR(t->mode);
+    a.t.col = tensor_colour_sets[colour];
     for (int k0 = 0; k0 < npics; k0 += TENSOR_MAX_PICS) {
         const int n = npics - k0 < TENSOR_MAX_PICS ? npics - k0 : TENSOR_MAX_PICS;
         for (int k = 0; k < TENSOR_MAX_PICS; k++) a.t.in_off[k] = k < n ? in_offsets[k0 + k] : 0;
         a.t.out = (uint8_t *)d_out + (size_t)k0 * out_stride;
-        resize_launch(t->mode, t->dtype, n, (hipStream_t)stream, a);
+        resize_launch(H264MI_TENSOR_LAYOUT(t->mode), t->dtype, colour != 0, n, (hipStream_t)stream, a);
         HIPCHECK(hipGetLastError());
     }
     return 0;

@@ -91,7 +91,7 @@ __device__ __forceinline__ void resize_taps(uint32_t n, uint32_t m, uint32_t j, 
 // the upper byte of the pair that ends with it (the byte in front of a chroma
 // plane is the plane's in front of it); columns 2 and 3 of that group hold
 // garbage no tap reads.
-template <int MODE, int NIT>
+template <int MODE, int NIT, bool COL>
 __device__ __forceinline__ void resize_stage(const tensor_args &a, const uint8_t *Y, const uint8_t *U, const uint8_t *V,
                                              uint32_t *stage, int pitch, int ng, int nit, int xs0, int r0, int tid)
 {
@@ -117,7 +117,8 @@ __device__ __forceinline__ void resize_stage(const tensor_args &a, const uint8_t
     for (int i = 0; i < NIT; i++) {
         uint32_t o0[4], o1[4];
         if (MODE == TENSOR_RGB) {
-            rgba_group_px(y0[i][0], y1[i][0], u[i], v[i], o0, o1);
+            if constexpr (COL) rgba_group_px_set(a.col, y0[i][0], y1[i][0], u[i], v[i], o0, o1);
+            else rgba_group_px(y0[i][0], y1[i][0], u[i], v[i], o0, o1);
         } else {
 #pragma unroll
             for (int k = 0; k < 4; k++) {
@@ -137,8 +138,9 @@ __device__ __forceinline__ void resize_stage(const tensor_args &a, const uint8_t
 }
 
 // grid: (tiles of RESIZE_TW x RESIZE_TH outputs in raster order, pictures of
-// this launch), 256 threads
-template <int MODE, int DT>
+// this launch), 256 threads; COL (RGB only): the pixels of the colour set
+// ra.t.col instead of the reference's
+template <int MODE, int DT, bool COL = false>
 __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const resize_args ra)
 {
     constexpr int ES = tensor_elem_size(DT);
@@ -192,9 +194,9 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const resize_a
         const int nr = ye - r0 < rc ? ye - r0 : rc;         // source rows of this chunk
         // stage: (row pair, 4-column group) items, groups fastest, at most 3 per thread
         const int nit = ((nr + 1) >> 1) * ng;
-        if (nit <= RESIZE_THREADS) resize_stage<MODE, 1>(a, Y, U, V, stage, pitch, ng, nit, xs0, r0, tid);
-        else if (nit <= 2 * RESIZE_THREADS) resize_stage<MODE, 2>(a, Y, U, V, stage, pitch, ng, nit, xs0, r0, tid);
-        else resize_stage<MODE, 3>(a, Y, U, V, stage, pitch, ng, nit, xs0, r0, tid);
+        if (nit <= RESIZE_THREADS) resize_stage<MODE, 1, COL>(a, Y, U, V, stage, pitch, ng, nit, xs0, r0, tid);
+        else if (nit <= 2 * RESIZE_THREADS) resize_stage<MODE, 2, COL>(a, Y, U, V, stage, pitch, ng, nit, xs0, r0, tid);
+        else resize_stage<MODE, 3, COL>(a, Y, U, V, stage, pitch, ng, nit, xs0, r0, tid);
         __syncthreads();
         // horizontal: (source row, output column) items, rows fastest
         for (int it = tid; it < (RESIZE_TW << lrc); it += RESIZE_THREADS) {
@@ -251,12 +253,19 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const resize_a
     }
 }
 
-static void resize_launch(int mode, int dt, int npics, hipStream_t st, const resize_args &a)
+static void resize_launch(int mode, int dt, bool col, int npics, hipStream_t st, const resize_args &a)
 {
     const unsigned ntx = (unsigned)(a.ow + RESIZE_TW - 1) / RESIZE_TW, nty = (unsigned)(a.oh + RESIZE_TH - 1) / RESIZE_TH;
     const dim3 grid(ntx * nty, npics), block(RESIZE_THREADS);
 #define RESIZE_CASE(M, D) \
     if (mode == M && dt == D) hipLaunchKernelGGL((k_tensor_resize<M, D>), grid, block, 0, st, a);
+#define RESIZE_COL_CASE(D)                                                                      \
+    if (mode == TENSOR_RGB && dt == D && col) {                                                 \
+        hipLaunchKernelGGL((k_tensor_resize<TENSOR_RGB, D, true>), grid, block, 0, st, a);      \
+        return;                                                                                 \
+    }
+    RESIZE_COL_CASE(TENSOR_U8) RESIZE_COL_CASE(TENSOR_F16) RESIZE_COL_CASE(TENSOR_BF16) RESIZE_COL_CASE(TENSOR_F32)
+#undef RESIZE_COL_CASE
     RESIZE_CASE(TENSOR_RGB, TENSOR_U8) RESIZE_CASE(TENSOR_RGB, TENSOR_F16)
     RESIZE_CASE(TENSOR_RGB, TENSOR_BF16) RESIZE_CASE(TENSOR_RGB, TENSOR_F32)
     RESIZE_CASE(TENSOR_GRAY, TENSOR_U8) RESIZE_CASE(TENSOR_GRAY, TENSOR_F16)

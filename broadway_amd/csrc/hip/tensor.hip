@@ -1,7 +1,8 @@
 // Decoded pictures as device tensors: the window (x, y, cw, ch -- all even) of
 // each of a list of pictures as contiguous planes, (3, ch, cw) R G B with the
-// pixel values of color.hip (rgba_group_px; x and y are even, so the RGB of the
-// crop is the crop of the RGB) or (1, ch, cw) luma, as uint8, fp16, bf16 or
+// pixel values of color.hip (rgba_group_px, or rgba_group_px_set with one of
+// the colour sets below; x and y are even, so the RGB of the crop is the crop
+// of the RGB) or (1, ch, cw) luma, as uint8, fp16, bf16 or
 // fp32.  The float types hold fma((float)c, scale[p], bias[p]) of plane p: one
 // fp32 fused multiply-add, then (16-bit types) one round-to-nearest-even
 // conversion (v_cvt_f16_f32 / v_cvt_pk_bf16_f32).  Input as in crop.hip: luma
@@ -33,7 +34,21 @@ struct tensor_args {
     int width, height, cpitch, x, y, cw, ch;
     size_t out_stride;
     float scale[3], bias[3];
+    colour_set col;                 // COL kernels only (tensor_colour_sets[id], id != 0)
     unsigned long long in_off[TENSOR_MAX_PICS];
+};
+
+// the colour sets of the RGB exports by id (include/h264mi.h):
+// (ky, k0, crv, cgu, cgv, cbu).  Set 0 is color.hip's rgba_px (the reference's
+// converter, no rounding term) and runs as literals (COL = false); 1..3 round
+// to nearest, k0 = 512 - ky * yoff, and each coefficient is 1024 c rounded to
+// nearest of BT.601 full, BT.709 limited, BT.709 full.
+#define TENSOR_COLOUR_SETS 4
+static const colour_set tensor_colour_sets[TENSOR_COLOUR_SETS] = {
+    {1192, -1192 * 16, 1634, 400, 832, 2066},
+    {1024, 512, 1436, 352, 731, 1815},
+    {1192, 512 - 1192 * 16, 1836, 218, 546, 2163},
+    {1024, 512, 1613, 192, 479, 1900},
 };
 
 typedef float tensor_f32x2 __attribute__((ext_vector_type(2)));
@@ -122,8 +137,10 @@ __device__ __forceinline__ void tensor_store(const uint32_t (&c)[N], int n, floa
 }
 
 // grid: (ceil(items / 128) blocks of 64 threads, pictures of this launch),
-// items = the window's (row pair, 4 * NG-column group) pairs in raster order
-template <int MODE, int DT, bool V16>
+// items = the window's (row pair, 4 * NG-column group) pairs in raster order;
+// COL (RGB only): the pixels of a.col (rgba_group_px_set) instead of the
+// reference's literal constants
+template <int MODE, int DT, bool V16, bool COL = false>
 __global__ __launch_bounds__(64) void k_tensor(const tensor_args a)
 {
     constexpr int ES = tensor_elem_size(DT);
@@ -174,8 +191,9 @@ __global__ __launch_bounds__(64) void k_tensor(const tensor_args a)
         for (int k = 0; k < NG; k++) {
             if (MODE == TENSOR_RGB) {
                 uint32_t o0[4], o1[4];
-                rgba_group_px(y0[k], y1[k], (u[k >> 1] >> (16 * (k & 1))) & 0xFFFFu, (v[k >> 1] >> (16 * (k & 1))) & 0xFFFFu,
-                              o0, o1);
+                const uint32_t u2 = (u[k >> 1] >> (16 * (k & 1))) & 0xFFFFu, v2 = (v[k >> 1] >> (16 * (k & 1))) & 0xFFFFu;
+                if constexpr (COL) rgba_group_px_set(a.col, y0[k], y1[k], u2, v2, o0, o1);
+                else rgba_group_px(y0[k], y1[k], u2, v2, o0, o1);
 #pragma unroll
                 for (int i = 0; i < 4; i++)
 #pragma unroll
@@ -201,8 +219,9 @@ __global__ __launch_bounds__(64) void k_tensor(const tensor_args a)
     }
 }
 
-// launch for (mode, dtype, v16); items per row pair as in the kernel
-static void tensor_launch(int mode, int dt, bool v16, int npics, hipStream_t st, const tensor_args &a)
+// launch for (mode, dtype, v16); items per row pair as in the kernel; col: the
+// RGB pixels of a.col
+static void tensor_launch(int mode, int dt, bool v16, bool col, int npics, hipStream_t st, const tensor_args &a)
 {
     const int nc = v16 ? 16 / tensor_elem_size(dt) : 4;
     const int nf = ((a.cw + nc - 1) / nc) * (a.ch >> 1);
@@ -212,6 +231,14 @@ static void tensor_launch(int mode, int dt, bool v16, int npics, hipStream_t st,
         if (v16) hipLaunchKernelGGL((k_tensor<M, D, true>), grid, block, 0, st, a);       \
         else hipLaunchKernelGGL((k_tensor<M, D, false>), grid, block, 0, st, a);          \
     }
+#define TENSOR_COL_CASE(D)                                                                        \
+    if (mode == TENSOR_RGB && dt == D && col) {                                                   \
+        if (v16) hipLaunchKernelGGL((k_tensor<TENSOR_RGB, D, true, true>), grid, block, 0, st, a); \
+        else hipLaunchKernelGGL((k_tensor<TENSOR_RGB, D, false, true>), grid, block, 0, st, a);   \
+        return;                                                                                   \
+    }
+    TENSOR_COL_CASE(TENSOR_U8) TENSOR_COL_CASE(TENSOR_F16) TENSOR_COL_CASE(TENSOR_BF16) TENSOR_COL_CASE(TENSOR_F32)
+#undef TENSOR_COL_CASE
     TENSOR_CASE(TENSOR_RGB, TENSOR_U8) TENSOR_CASE(TENSOR_RGB, TENSOR_F16)
     TENSOR_CASE(TENSOR_RGB, TENSOR_BF16) TENSOR_CASE(TENSOR_RGB, TENSOR_F32)
     TENSOR_CASE(TENSOR_GRAY, TENSOR_U8) TENSOR_CASE(TENSOR_GRAY, TENSOR_F16)

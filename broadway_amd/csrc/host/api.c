@@ -271,8 +271,7 @@ H264SwDecRet H264SwDecNextPictureTensor(H264SwDecInst decInst, H264SwDecPicture 
         t.dtype = H264MI_TENSOR_F16;
         for (int p = 0; p < 3; p++) t.scale[p] = 1.0f / 255.0f;
     }
-    if ((t.mode != H264MI_TENSOR_RGB && t.mode != H264MI_TENSOR_GRAY) || t.dtype < H264MI_TENSOR_U8 ||
-        t.dtype > H264MI_TENSOR_F32)
+    if (h264mi_tensor_colour_resolve(t.mode, 2, 0, 2, 2) < 0 || t.dtype < H264MI_TENSOR_U8 || t.dtype > H264MI_TENSOR_F32)
         return H264SWDEC_PARAM_ERR;
     const size_t es = t.dtype == H264MI_TENSOR_U8 ? 1 : t.dtype == H264MI_TENSOR_F32 ? 4 : 2;
     if ((size_t)(uintptr_t)d_dst & (es - 1)) return H264SWDEC_PARAM_ERR;
@@ -311,7 +310,7 @@ H264SwDecRet H264SwDecNextPictureTensorResized(H264SwDecInst decInst, H264SwDecP
     if (!c->dec.be.export_tensor_resized) return H264SWDEC_PARAM_ERR;
     h264mi_tensor_resize_desc r = *desc;
     h264mi_tensor_desc *t = &r.t;
-    if ((t->mode != H264MI_TENSOR_RGB && t->mode != H264MI_TENSOR_GRAY) || t->dtype < H264MI_TENSOR_U8 ||
+    if (h264mi_tensor_colour_resolve(t->mode, 2, 0, 2, 2) < 0 || t->dtype < H264MI_TENSOR_U8 ||
         t->dtype > H264MI_TENSOR_F32 || r.filter != H264MI_RESIZE_TRIANGLE || r.ow < 1 || r.oh < 1 || r.ow > 16384 ||
         r.oh > 16384)
         return H264SWDEC_PARAM_ERR;
@@ -339,6 +338,13 @@ H264SwDecRet H264SwDecNextPictureTensorResized(H264SwDecInst decInst, H264SwDecP
     pOutput->isIdrPicture = idr;
     pOutput->nbrOfErrMBs = em;
     return H264SWDEC_PIC_RDY;
+}
+
+/* the colour id of the last tensor either call above delivered; -1: none yet */
+int H264SwDecLastTensorColour(H264SwDecInst decInst)
+{
+    if (decInst == NULL) return -1;
+    return ((DecContainer *)decInst)->dec.last_tensor_colour1 - 1;
 }
 
 /* Record retention for H264SwDecLastPictureMbInfo (include/h264mi.h): the

@@ -1,6 +1,7 @@
 /* Host decoder control -- see decoder.h. */
 #include "decoder.h"
 #include "../common/tables.h"
+#include "../../../include/h264mi.h"
 
 #include <stdlib.h>
 #include <stdatomic.h>
@@ -411,6 +412,11 @@ static int finish_picture(H264Dec *d, int concealed_mbs)
     int poc = decode_poc(d, sps, &d->sh);
     if (d->valid_slice_in_au) {
         int is_idr = d->prev_nal.type == NAL_IDR;
+        /* what a tensor export with H264MI_TENSOR_COLOUR_STREAM goes by: the
+         * picture may leave the DPB when another SPS is active */
+        DpbPic *cur = &d->dpb.pic[d->dpb.cur];
+        cur->vui_matrix = (sps->vui_present && sps->colour_desc_present) ? sps->matrix_coeffs : 2;
+        cur->vui_full = (sps->vui_present && sps->video_full_range) ? 1 : 0;
         dpb_mark(&d->dpb, &d->sh, d->prev_nal.ref_idc != 0, d->sh.frame_num, poc, is_idr,
                  d->cur_pic_id, concealed_mbs);
     }
@@ -603,6 +609,26 @@ const uint8_t *h264dec_next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_id
     return h264dec_next_output_rgba(d, pic_id, is_idr, err_mbs, NULL);
 }
 
+/* The colour set of a tensor export (include/h264mi.h): the id in `mode`, or
+ * H264MI_TENSOR_COLOUR_STREAM resolved against a picture's colour signalling
+ * (matrix: matrix_coefficients, 2 where the SPS gives none; full:
+ * video_full_range_flag) and the export window's size; -1: a bad mode. */
+int h264mi_tensor_colour_resolve(int mode, int matrix, int full, int cw, int ch)
+{
+    if (mode & ~0x3FFF) return -1;
+    const int layout = H264MI_TENSOR_LAYOUT(mode), colour = H264MI_TENSOR_COLOUR(mode);
+    if (layout == H264MI_TENSOR_GRAY) return mode == H264MI_TENSOR_GRAY ? 0 : -1;
+    if (layout != H264MI_TENSOR_RGB) return -1;
+    if (colour != H264MI_TENSOR_COLOUR_STREAM) return colour <= H264MI_TENSOR_COLOUR_BT709_FULL ? colour : -1;
+    const int unspec = H264MI_TENSOR_UNSPEC(mode);
+    if (unspec > H264MI_TENSOR_UNSPEC_SIZE) return -1;
+    int bt709;
+    if (matrix == 1) bt709 = 1;
+    else if (matrix == 5 || matrix == 6) bt709 = 0;
+    else bt709 = unspec == H264MI_TENSOR_UNSPEC_BT709 || (unspec == H264MI_TENSOR_UNSPEC_SIZE && (cw >= 1280 || ch > 576));
+    return (bt709 ? H264MI_TENSOR_COLOUR_BT709 : H264MI_TENSOR_COLOUR_REFERENCE) + (full ? 1 : 0);
+}
+
 /* a tensor export (h264dec_next_output_tensor, resized: _tensor_resized);
  * failed: the backend refused it */
 typedef struct TensorOut {
@@ -629,11 +655,17 @@ const uint8_t *h264dec_next_output_crop(H264Dec *d, uint32_t *pic_id, uint32_t *
     return next_output(d, pic_id, is_idr, err_mbs, NULL, dst, rgba, NULL);
 }
 
+/* (a resize descriptor starts with its h264mi_tensor_desc) */
+static int tensor_mode_ok(const void *desc)
+{
+    return h264mi_tensor_colour_resolve(((const h264mi_tensor_desc *)desc)->mode, 2, 0, 2, 2) >= 0;
+}
+
 const uint8_t *h264dec_next_output_tensor(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
                                           const void *desc, void *d_dst, void *hip_stream, int *failed)
 {
     TensorOut t = {desc, d_dst, hip_stream, 0, 0};
-    const uint8_t *r = desc && d_dst ? next_output(d, pic_id, is_idr, err_mbs, NULL, NULL, 0, &t) : NULL;
+    const uint8_t *r = desc && d_dst && tensor_mode_ok(desc) ? next_output(d, pic_id, is_idr, err_mbs, NULL, NULL, 0, &t) : NULL;
     if (failed) *failed = t.failed;
     return r;
 }
@@ -642,7 +674,7 @@ const uint8_t *h264dec_next_output_tensor_resized(H264Dec *d, uint32_t *pic_id, 
                                                   const void *desc, void *d_dst, void *hip_stream, int *failed)
 {
     TensorOut t = {desc, d_dst, hip_stream, 0, 1};
-    const uint8_t *r = desc && d_dst ? next_output(d, pic_id, is_idr, err_mbs, NULL, NULL, 0, &t) : NULL;
+    const uint8_t *r = desc && d_dst && tensor_mode_ok(desc) ? next_output(d, pic_id, is_idr, err_mbs, NULL, NULL, 0, &t) : NULL;
     if (failed) *failed = t.failed;
     return r;
 }
@@ -674,9 +706,17 @@ static const uint8_t *next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr
     const double t1 = h264dec_now();
     int rr;
     if (tensor) {
-        rr = (tensor->resized ? d->be.export_tensor_resized : d->be.export_tensor)(d->be.ctx, o->slot, tensor->desc,
-                                                                                    tensor->d_dst, tensor->hip_stream);
+        /* the backend gets the colour id of this picture's own SPS in place of STREAM */
+        h264mi_tensor_resize_desc r;
+        memset(&r, 0, sizeof(r));
+        if (tensor->resized) r = *(const h264mi_tensor_resize_desc *)tensor->desc;
+        else r.t = *(const h264mi_tensor_desc *)tensor->desc;
+        const int colour = h264mi_tensor_colour_resolve(r.t.mode, o->vui_matrix, o->vui_full, r.t.cw, r.t.ch);
+        if (H264MI_TENSOR_LAYOUT(r.t.mode) == H264MI_TENSOR_RGB) r.t.mode = H264MI_TENSOR_MODE(H264MI_TENSOR_RGB, colour, 0);
+        rr = tensor->resized ? d->be.export_tensor_resized(d->be.ctx, o->slot, &r, tensor->d_dst, tensor->hip_stream)
+                             : d->be.export_tensor(d->be.ctx, o->slot, &r.t, tensor->d_dst, tensor->hip_stream);
         tensor->failed = rr < 0;
+        if (rr >= 0) d->last_tensor_colour1 = colour + 1;
     } else if (crop) {
         const int cl = sps->crop ? 2 * sps->crop_l : 0, ct = sps->crop ? 2 * sps->crop_t : 0;
         const int cr = sps->crop ? 2 * sps->crop_r : 0, cb = sps->crop ? 2 * sps->crop_b : 0;

@@ -147,6 +147,8 @@ typedef struct H264Dec {
     int      keep_mbinfo;
     int      keep_residual;     /* the same for the coefficients (H264SwDecKeepResidual) */
     int      last_out_slot1;
+    /* the colour id of the last tensor delivered (include/h264mi.h), plus one (0: none yet) */
+    int      last_tensor_colour1;
     /* statistics */
     uint64_t pics_decoded, alg_ref_bytes, coded_blocks;
     /* speculative parallel slice parsing (specparse.c); NULL: off */

@@ -102,6 +102,7 @@ static int output_picture(Dpb *d)
     if (d->num_out <= DPB_MAX) {
         DpbOut *o = &d->out[d->num_out++];
         o->slot = p->slot; o->is_idr = p->is_idr; o->pic_id = p->pic_id; o->err_mbs = p->err_mbs;
+        o->vui_matrix = p->vui_matrix; o->vui_full = p->vui_full;
     }
     p->to_display = 0;
     if (!IS_REF(p)) d->fullness--;
@@ -347,6 +348,7 @@ int dpb_mark(Dpb *d, const SliceHdr *sh, int is_ref, int frame_num, int poc, int
         if (d->num_out <= DPB_MAX) {
             DpbOut *o = &d->out[d->num_out++];
             o->slot = c->slot; o->is_idr = is_idr; o->pic_id = pic_id; o->err_mbs = err_mbs;
+            o->vui_matrix = c->vui_matrix; o->vui_full = c->vui_full;
         }
     } else {
         while (d->fullness > d->size) if (output_picture(d)) break;

@@ -23,9 +23,13 @@ typedef struct DpbPic {
     int poc;
     int to_display;
     int is_idr, pic_id, err_mbs;
+    /* the colour signalling of the SPS the picture was decoded under (the
+     * decoder sets them on the current entry before dpb_mark): matrix_coeffs,
+     * 2 where the SPS gives none, and video_full_range_flag */
+    int vui_matrix, vui_full;
 } DpbPic;
 
-typedef struct DpbOut { int slot, is_idr, pic_id, err_mbs; } DpbOut;
+typedef struct DpbOut { int slot, is_idr, pic_id, err_mbs, vui_matrix, vui_full; } DpbOut;
 
 typedef struct Dpb {
     DpbPic pic[DPB_MAX];

@@ -38,7 +38,14 @@ of the wasm glue of Decoder/src/Decoder.c:44-162:
   scale 1/255).  With ``size`` the crop window is resized on the GPU
   (``H264SwDecNextPictureTensorResized``): the tensor is ``(planes, oh, ow)``
   and the callback's width and height are ``ow`` and ``oh``.  It combines with
-  neither ``rgb`` nor ``crop`` (ValueError).
+  neither ``rgb`` nor ``crop`` (ValueError).  ``colour`` picks the colour set
+  of the R, G, B samples: "reference" (the default: BT.601 limited range, the
+  values of ``rgb: true``), "bt601-full", "bt709", "bt709-full", or "stream"
+  -- the set the VUI of each delivered picture's own SPS names
+  (matrix_coefficients 1: BT.709; 5, 6: BT.601; video_full_range_flag), and
+  where it names none the family of ``unspecified``: "bt601" (default),
+  "bt709" or "size" (BT.709 from 1280 columns or 577 rows of the exported
+  window).  ``decoder.tensor_colour`` names the set of the last tensor.
 
 * ``mbinfo: true`` or ``mbinfo: {"channels": ..., "dtype": ..., "scale": ...,
   "bias": ...}`` (an extension for device consumers; needs torch; combines
@@ -97,11 +104,11 @@ class Decoder:
             if self._rgb or self._crop:
                 raise ValueError("tensor: not combinable with rgb or crop (mode='rgb' and the SPS window are part of it)")
             opts = {} if self._tensor is True else dict(self._tensor)
-            unknown = set(opts) - {"dtype", "mode", "mean", "std", "scale", "bias", "size"}
+            unknown = set(opts) - {"dtype", "mode", "mean", "std", "scale", "bias", "size", "colour", "unspecified"}
             if unknown:
                 raise ValueError(f"tensor: unknown keys {sorted(unknown)}")
             from .engine import tensor_desc          # (imports torch)
-            self._tensor = tensor_desc(None, **opts)
+            self._tensor = tensor_desc(None, stream_ok=True, **opts)
             self._resized = opts.get("size") is not None
             self._device = int(os.environ.get("H264MI_DEVICE") or 0)     # the GPU H264SwDecInit takes (api.c)
         self._mbinfo = self.options.get("mbinfo") or None
@@ -291,6 +298,13 @@ class Decoder:
             infos[0]["finishDecoding"] = _now()
         self.infoAr = []
         self.onPictureDecoded(buf, w, h, infos)
+
+    @property
+    def tensor_colour(self) -> Optional[str]:
+        """The colour set of the last tensor delivered ("reference",
+        "bt601-full", "bt709" or "bt709-full"); None before the first."""
+        k = self._L.H264SwDecLastTensorColour(self._inst)
+        return _lib.TENSOR_COLOUR_NAMES[k] if k >= 0 else None
 
     def info(self) -> _lib.H264SwDecInfo:
         return self._info

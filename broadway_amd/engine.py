@@ -33,13 +33,42 @@ def tensor_affine(mean: Sequence[float], std: Sequence[float]) -> Tuple[Tuple[fl
     return scale, bias
 
 
-def tensor_desc(window, mode="rgb", dtype=None, scale=None, bias=None, mean=None, std=None, size=None):
+def tensor_colour_bits(colour, unspecified=None, mode="rgb", stream_ok=False):
+    """Bits 8..13 of a tensor descriptor's mode for the colour set ``colour``
+    (a key of ``_lib.TENSOR_COLOURS``; None is "reference").  "stream" -- the
+    set the delivered picture's VUI names, ``unspecified`` ("bt601", the
+    default, "bt709" or "size") where it names none -- belongs to the Decoder
+    (``stream_ok``); a colour goes with ``mode="rgb"`` only.  ValueError
+    otherwise."""
+    if colour is None and unspecified is None:
+        return 0
+    if mode != "rgb":
+        raise ValueError(f"colour / unspecified: mode {mode!r} has no colour set (only 'rgb')")
+    colour = "reference" if colour is None else colour
+    if not isinstance(colour, str) or colour not in _lib.TENSOR_COLOURS:
+        raise ValueError(f"colour {colour!r}: one of {sorted(_lib.TENSOR_COLOURS)}")
+    if colour != "stream":
+        if unspecified is not None:
+            raise ValueError("unspecified: goes with colour='stream'")
+        return _lib.TENSOR_COLOURS[colour] << _lib.TENSOR_COLOUR_SHIFT
+    if not stream_ok:
+        raise ValueError("colour 'stream': the Decoder's tensor option only (an engine knows no stream)")
+    unspecified = "bt601" if unspecified is None else unspecified
+    if not isinstance(unspecified, str) or unspecified not in _lib.TENSOR_UNSPECIFIED:
+        raise ValueError(f"unspecified {unspecified!r}: one of {sorted(_lib.TENSOR_UNSPECIFIED)}")
+    return (_lib.TENSOR_COLOUR_STREAM << _lib.TENSOR_COLOUR_SHIFT |
+            _lib.TENSOR_UNSPECIFIED[unspecified] << _lib.TENSOR_UNSPEC_SHIFT)
+
+
+def tensor_desc(window, mode="rgb", dtype=None, scale=None, bias=None, mean=None, std=None, size=None, colour=None,
+                unspecified=None, stream_ok=False):
     """(``_lib.TensorDesc``, planes, torch dtype) of a tensor export
     (Engine.to_tensor, Decoder's ``tensor`` option); window = (x, y, cw, ch),
     or None for the decoder's SPS crop window (cw = 0 in the descriptor).
     With ``size`` = (oh, ow), each 1..16384, the descriptor is a
     ``_lib.TensorResizeDesc`` of the resized export (its ``t`` is the one
-    above)."""
+    above).  ``colour``: the colour set of the R, G, B samples
+    (``tensor_colour_bits``; None: the reference's BT.601 limited range)."""
     import torch
     if size is not None:
         try:
@@ -48,7 +77,7 @@ def tensor_desc(window, mode="rgb", dtype=None, scale=None, bias=None, mean=None
             raise ValueError(f"size {size!r}: (oh, ow)") from None
         if not (1 <= oh <= _lib.RESIZE_MAX_DIM and 1 <= ow <= _lib.RESIZE_MAX_DIM):
             raise ValueError(f"size {size!r}: oh and ow are 1..{_lib.RESIZE_MAX_DIM}")
-        t, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std)
+        t, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std, None, colour, unspecified, stream_ok)
         d = _lib.TensorResizeDesc()
         d.t, d.ow, d.oh, d.filter = t, ow, oh, _lib.RESIZE_TRIANGLE
         return d, planes, dtype
@@ -60,6 +89,7 @@ def tensor_desc(window, mode="rgb", dtype=None, scale=None, bias=None, mean=None
         raise ValueError(f"dtype {dtype}: one of torch.uint8, float16, bfloat16, float32")
     if mode not in modes:
         raise ValueError(f"mode {mode!r}: 'rgb' or 'gray'")
+    colour_bits = tensor_colour_bits(colour, unspecified, mode, stream_ok)
     if (mean is None) != (std is None):
         raise ValueError("mean and std go together")
     if mean is not None:
@@ -78,6 +108,7 @@ def tensor_desc(window, mode="rgb", dtype=None, scale=None, bias=None, mean=None
     d = _lib.TensorDesc()
     d.x, d.y, d.cw, d.ch = (int(v) for v in window) if window is not None else (0, 0, 0, 0)
     d.mode, planes = modes[mode]
+    d.mode |= colour_bits
     d.dtype = dts[dtype]
     d.scale[:] = triple(scale, 1.0 / 255.0)
     d.bias[:] = triple(bias, 0.0)
@@ -348,7 +379,7 @@ class Engine:
         return out
 
     def to_tensor(self, streams: Sequence[int], slots: Sequence[int], window=None, mode: str = "rgb", dtype=None,
-                  scale=None, bias=None, mean=None, std=None, out=None, stream=None, size=None):
+                  scale=None, bias=None, mean=None, std=None, out=None, stream=None, size=None, colour=None):
         """The slots (streams[k], slots[k]) as one ``(n, planes, ch, cw)``
         torch tensor on ``cuda:{self.device}``, built on the GPU and never
         copied to the host: planes R, G, B (``mode="rgb"``, the values of
@@ -362,6 +393,10 @@ class Engine:
         resized on the GPU before that conversion (antialiased triangle
         filter in integer arithmetic; a window at most 32 times
         the output on each axis) -- the result is ``(n, planes, oh, ow)``.
+        ``colour`` (``mode="rgb"`` only): the colour set of the R, G, B
+        samples -- None / "reference" (BT.601 limited range, the values of
+        read_rgba), "bt601-full", "bt709" or "bt709-full" (DESIGN 3.5f); the
+        resize works on the samples of that set.
 
         The export is ordered on ``stream`` (a torch.cuda.Stream; default:
         torch's current stream of the device): it starts after the work queued
@@ -377,7 +412,7 @@ class Engine:
             raise ValueError("streams and slots name the same, non-zero number of pictures")
         if window is None:
             window = (0, 0, self.w_mbs * 16, self.h_mbs * 16)
-        desc, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std, size)
+        desc, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std, size, colour)
         shape = (n, planes, desc.ch, desc.cw) if size is None else (n, planes, desc.oh, desc.ow)
         dev = torch.device("cuda", self.device)
         if out is None:

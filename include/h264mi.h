@@ -130,8 +130,8 @@ H264SwDecRet H264SwDecNextPictureRGBA(H264SwDecInst decInst, H264SwDecPicture *p
 H264SwDecRet H264SwDecNextPictureCropped(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer, u8 *dst,
                                          u32 rgba);
 /* A picture as a planar tensor in device memory (tensor.hip): the window (x, y,
- * cw, ch -- luma pixels, all even) as (3, ch, cw) R G B planes (the values of
- * NextPictureRGBA) or one (1, ch, cw) luma plane, contiguous, of uint8 (the
+ * cw, ch -- luma pixels, all even) as (3, ch, cw) R G B planes (by default the
+ * values of NextPictureRGBA; other colour sets below) or one (1, ch, cw) luma plane, contiguous, of uint8 (the
  * sample) or fp16 / bf16 / fp32: fma((float)sample, scale[p], bias[p]) of plane
  * p as one fp32 fused multiply-add, then rounded to nearest-even to the 16-bit
  * types.  GRAY uses scale[0] and bias[0]; uint8 ignores both. */
@@ -139,6 +139,54 @@ enum { H264MI_TENSOR_RGB = 0, H264MI_TENSOR_GRAY = 1 };
 enum { H264MI_TENSOR_U8 = 0, H264MI_TENSOR_F16 = 1, H264MI_TENSOR_BF16 = 2, H264MI_TENSOR_F32 = 3,
        H264MI_TENSOR_I16 = 4 };     /* int16: the MB side-information field below only */
 typedef struct { int x, y, cw, ch, mode, dtype; float scale[3], bias[3]; } h264mi_tensor_desc;
+/* The colour set of an RGB tensor travels in `mode`: bits 0..7
+ * the layout above, bits 8..11 the colour id, bits 12..13 (read only with
+ * H264MI_TENSOR_COLOUR_STREAM) the set family to take where the stream names
+ * none; every other bit zero, and bits 8..13 zero with GRAY.  A set is six
+ * integers (ky, k0, crv, cgu, cgv, cbu); with u = U - 128, v = V - 128:
+ *   a0 = ky Y + k0
+ *   R = clamp((a0 + crv v) >> 10, 0, 255)
+ *   G = clamp((a0 - cgu u - cgv v) >> 10, 0, 255)
+ *   B = clamp((a0 + cbu u) >> 10, 0, 255)               (arithmetic shifts)
+ *   id  set                              ky  yoff   crv  cgu  cgv   cbu
+ *   0   reference (BT.601 limited,     1192   16   1634  400  832  2066
+ *       DecoderPost.js; the default)
+ *   1   BT.601 full range              1024    0   1436  352  731  1815
+ *   2   BT.709 limited range           1192   16   1836  218  546  2163
+ *   3   BT.709 full range              1024    0   1613  192  479  1900
+ * Set 0 is NextPictureRGBA's converter, which does not round: k0 = -ky yoff.
+ * Sets 1..3 round to nearest, k0 = 512 - ky yoff, and their coefficients are
+ * floor(1024 c + 1/2) of c = 255/219 (ky, limited) and f 2 (1 - Kr), f 2 Kb
+ * (1 - Kb) / Kg, f 2 Kr (1 - Kr) / Kg, f 2 (1 - Kb) with f = 255/224 (limited)
+ * or 1 (full), (Kr, Kb) = (0.299, 0.114) or (0.2126, 0.0722), Kg = 1 - Kr - Kb.
+ * Chroma is the 4:2:0 sample of the 2x2 block, replicated, as for set 0; the
+ * values stay gamma-encoded R'G'B'.
+ * H264MI_TENSOR_COLOUR_STREAM (the two H264SwDec calls below only; the engine-
+ * level exports know no stream and refuse it) takes the set from the VUI of
+ * the SPS the delivered picture was decoded under: matrix_coefficients 1 is
+ * BT.709, 5 and 6 are BT.601; no VUI, no colour description, 2 (unspecified)
+ * and every other value give the family of bits 12..13 -- BT.601, BT.709, or
+ * by size: BT.709 when the export window (before any resize) is at least 1280
+ * wide or more than 576 high.  The range is video_full_range_flag where the
+ * VUI carries a video signal type, else limited.  With STREAM, BT.601 limited
+ * range is set 0 (the reference's). */
+enum { H264MI_TENSOR_COLOUR_REFERENCE = 0, H264MI_TENSOR_COLOUR_BT601_FULL = 1, H264MI_TENSOR_COLOUR_BT709 = 2,
+       H264MI_TENSOR_COLOUR_BT709_FULL = 3, H264MI_TENSOR_COLOUR_STREAM = 15 };
+enum { H264MI_TENSOR_UNSPEC_BT601 = 0, H264MI_TENSOR_UNSPEC_BT709 = 1, H264MI_TENSOR_UNSPEC_SIZE = 2 };
+#define H264MI_TENSOR_COLOUR_SHIFT 8
+#define H264MI_TENSOR_UNSPEC_SHIFT 12
+#define H264MI_TENSOR_MODE(layout, colour, unspec) \
+    ((layout) | (colour) << H264MI_TENSOR_COLOUR_SHIFT | (unspec) << H264MI_TENSOR_UNSPEC_SHIFT)
+#define H264MI_TENSOR_LAYOUT(mode) ((mode) & 0xFF)
+#define H264MI_TENSOR_COLOUR(mode) (((mode) >> H264MI_TENSOR_COLOUR_SHIFT) & 15)
+#define H264MI_TENSOR_UNSPEC(mode) (((mode) >> H264MI_TENSOR_UNSPEC_SHIFT) & 3)
+/* The colour id, 0..3, an export with `mode` uses for a picture whose SPS has
+ * matrix_coefficients `matrix` (2: none given) and full-range flag `full`, over
+ * a window of cw x ch pixels: the id in `mode`, or STREAM resolved as above;
+ * -1 for a mode the H264SwDec tensor calls refuse.  A pure function. */
+int h264mi_tensor_colour_resolve(int mode, int matrix, int full, int cw, int ch);
+/* the six integers of set `id` into out; -1 for an id that is not 0..3 */
+int h264mi_tensor_colour_coeffs(int id, int out[6]);
 /* NextPicture, the picture exported to device memory instead of copied to the
  * host: d_dst (on the decoder's GPU, a multiple of the element size) receives
  * the tensor of `desc`, ordered on `hip_stream` as h264mi_engine_export_tensor
@@ -163,6 +211,11 @@ typedef struct { h264mi_tensor_desc t; int ow, oh, filter; } h264mi_tensor_resiz
  * desc->t.cw == 0 takes the active SPS's crop window.  Otherwise as above. */
 H264SwDecRet H264SwDecNextPictureTensorResized(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
                                                const h264mi_tensor_resize_desc *desc, void *d_dst, void *hip_stream);
+/* Both calls take colour ids 0..3 and H264MI_TENSOR_COLOUR_STREAM in the
+ * descriptor's mode, and refuse a bad mode (H264SWDEC_PARAM_ERR) before a
+ * picture is taken from the DPB.  The colour id, 0..3, of the last tensor
+ * either call delivered (GRAY: 0); -1 before the first one. */
+int H264SwDecLastTensorColour(H264SwDecInst decInst);
 /* Motion vectors and MB side information as a device tensor (mbinfo.hip, DESIGN
  * 3.5d; elsewhere: ffmpeg's export_mvs).  The field lives on the luma 4x4-block
  * grid of the MB-aligned picture, BW = 4 * w_mbs columns by BH = 4 * h_mbs
@@ -448,7 +501,9 @@ int  h264mi_engine_read_crop(h264mi_engine *e, int stream, int slot, int x, int 
  * row bytes are multiples of 16 a lane stores 16 bytes at a time.  Nothing
  * outside the planes * ch * cw elements of each picture is written.  Device
  * pointers, asynchronous on `hip_stream`.  -1 on a bad argument, nothing
- * launched. */
+ * launched.  This call and the three engine-level calls below take the colour
+ * ids 0..3 in desc->mode and refuse H264MI_TENSOR_COLOUR_STREAM: they know no
+ * stream. */
 int  h264mi_tensor_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width, int height,
                                 int cpitch, const h264mi_tensor_desc *desc, void *d_out, size_t out_stride,
                                 void *hip_stream);

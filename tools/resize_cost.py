@@ -5,7 +5,8 @@ writes profiles/resize_cost.json (or the path given).  Conventions of
 tools/tensor_cost.py.
 
 8 pictures 1920x1088 in the frame-slot layout, window 1920x1080, RGB: resized
-to 224x224 and to 384x640 (oh x ow) as fp16 and as uint8, against k_tensor's
+to 224x224 and to 384x640 (oh x ow) as fp16 and as uint8 (and to 224x224 as
+fp16 with colour set 2, BT.709 limited), against k_tensor's
 full-size fp16 export (h264mi_tensor_device_pitch) of the same slots in the
 same run.  The bar: a resized launch takes no longer than the comparator's
 median plus the comparator's own spread (max - min).  Consecutive launches
@@ -72,6 +73,13 @@ def kernel_legs(torch, L, nsets):
                 chk(L.h264mi_tensor_resize_device_pitch(d_in[i].data_ptr(), offs, NP, W, H, cpitch, C.byref(rdesc),
                                                         outs[i % NSETS].data_ptr(), stride, st))
             legs[f"resize_rgb_{str(dtype).split('.')[1]}_{oh}x{ow}"] = (f, NP * stride)
+    # fp16 -> 224x224 with colour set 2 (BT.709 limited): the COL instantiation
+    cdesc, planes, _ = tensor_desc((0, 0, CW, CH), "rgb", torch.float16, size=SIZES[0], colour="bt709")
+    couts = [torch.empty((NP, planes) + SIZES[0], dtype=torch.float16, device="cuda") for _ in range(NSETS)]
+    cstride = planes * SIZES[0][0] * SIZES[0][1] * 2
+    legs[f"resize_rgb_float16_{SIZES[0][0]}x{SIZES[0][1]}_bt709"] = (lambda i: chk(L.h264mi_tensor_resize_device_pitch(
+        d_in[i].data_ptr(), offs, NP, W, H, cpitch, C.byref(cdesc), couts[i % NSETS].data_ptr(), cstride, st)),
+        NP * cstride)
     us = {k: [] for k in legs}
     for k, (f, _) in legs.items():                      # warm-up: code objects, every shape
         for i in sets:
@@ -100,6 +108,9 @@ def kernel_legs(torch, L, nsets):
         out[k]["over_bar_us"] = round(out[k]["median_us"] - bar, 2)
         out[k]["meets_bar"] = bool(out[k]["median_us"] <= bar)
         out[k]["median_over_comparator_median"] = round(out[k]["median_us"] / b["median_us"], 3)
+    c, d = out[f"resize_rgb_float16_{SIZES[0][0]}x{SIZES[0][1]}_bt709"], out[f"resize_rgb_float16_{SIZES[0][0]}x{SIZES[0][1]}"]
+    c["default_median_us"], c["default_spread_us"] = d["median_us"], round(d["max_us"] - d["min_us"], 2)
+    c["within_default_spread"] = bool(c["median_us"] <= d["median_us"] + c["default_spread_us"])
     return out
 
 

@@ -6,8 +6,9 @@ tools/crop_cost.py.
 
 (a) kernel time per byte moved (read + written), 8 pictures 1920x1088 ->
     window 1920x1080 from the frame-slot layout, RGB planes as uint8, fp16,
-    bf16 and fp32, against k_crop_rgba (h264mi_crop_device_pitch, rgba) on
-    the same slots in the same run.  The bar is the comparator: a tensor
+    bf16 and fp32 (and uint8 and fp16 with colour set 2, BT.709 limited,
+    against the default leg of the same dtype), against k_crop_rgba
+    (h264mi_crop_device_pitch, rgba) on the same slots in the same run.  The bar is the comparator: a tensor
     kernel may cost more per byte moved by no more than the spread (max -
     min) of the comparator's samples; the interquartile range is recorded
     beside it.  Consecutive launches rotate through NSETS input and output
@@ -70,6 +71,17 @@ def kernel_leg(torch, L):
             chk(L.h264mi_tensor_device_pitch(d_in[i].data_ptr(), offs, NP, W, H, cpitch, C.byref(desc),
                                              outs[i].data_ptr(), stride, st))
         legs["tensor_rgb_" + str(dtype).split(".")[1]] = (f, NP * stride)
+    # the same export with colour set 2 (BT.709 limited): the COL instantiations
+    for dtype in (torch.uint8, torch.float16):
+        desc, planes, _ = tensor_desc((0, 0, CW, CH), "rgb", dtype, colour="bt709")
+        outs = [torch.empty((NP, planes, CH, CW), dtype=dtype, device="cuda") for _ in sets]
+        stride = planes * CH * CW * outs[0].element_size()
+        keep.append((desc, outs))
+
+        def f(i, desc=desc, outs=outs, stride=stride):
+            chk(L.h264mi_tensor_device_pitch(d_in[i].data_ptr(), offs, NP, W, H, cpitch, C.byref(desc),
+                                             outs[i].data_ptr(), stride, st))
+        legs["tensor_rgb_" + str(dtype).split(".")[1] + "_bt709"] = (f, NP * stride)
     us = {k: [] for k in legs}
     for k, (f, _) in legs.items():                      # warm-up: code objects, every shape
         for i in sets:
@@ -97,6 +109,14 @@ def kernel_leg(torch, L):
     moved_b = b["bytes_read"] + b["bytes_written"]
     spread = (b["max_us"] - b["min_us"]) * 1e6 / moved_b
     iqr = b["iqr_us"] * 1e6 / moved_b
+    # a colour leg against the default leg of its dtype: same bytes moved, the bar is the default's own spread
+    for a in [k for k in legs if k.endswith("_bt709")]:
+        d = out[a[:-len("_bt709")]]
+        dspread = (d["max_us"] - d["min_us"]) * 1e6 / (d["bytes_read"] + d["bytes_written"])
+        over = out[a]["ps_per_byte_moved"] - d["ps_per_byte_moved"]
+        out[a + "_vs_default"] = {"extra_ps_per_byte_moved": round(over, 3),
+                                  "default_spread_ps_per_byte_moved": round(dspread, 3),
+                                  "within_default_spread": bool(over <= dspread)}
     for a in [k for k in legs if k != "crop_rgba"]:
         over = out[a]["ps_per_byte_moved"] - b["ps_per_byte_moved"]
         out[a + "_vs_crop_rgba"] = {"extra_ps_per_byte_moved": round(over, 3),
