@@ -1,0 +1,121 @@
+/* The descriptor rules of the device-tensor exports (include/h264mi.h), stated
+ * once for the engine (hip/engine.hip) and the H264SwDec calls (host/api.c).
+ * Each descriptor's rules come in two parts, because api.c refuses the first
+ * before it looks for headers and the second before it takes a picture:
+ *   *_fixed_ok    what does not depend on the picture (element type, channels,
+ *                 planes, filter, output size);
+ *   *_window_ok   the window against a picture size (call it after *_fixed_ok).
+ * An export accepts a descriptor that passes both.  The mode of a tensor
+ * descriptor is not judged here: the engine-level calls refuse
+ * H264MI_TENSOR_COLOUR_STREAM, the H264SwDec calls resolve it. */
+#ifndef H264MI_EXPORT_DESC_H
+#define H264MI_EXPORT_DESC_H
+
+#include <stddef.h>
+#include <stdint.h>
+#include "../../../include/h264mi.h"
+
+#define H264MI_RESIZE_MAX_DIM 16384     /* ow, oh, cw, ch of a resized export (resize.hip's RESIZE_MAX_DIM) */
+
+#ifdef __cplusplus
+#define EXPORT_CONSTEXPR constexpr      /* engine.hip checks it against the kernels' tensor_elem_size */
+#else
+#define EXPORT_CONSTEXPR
+#endif
+
+static inline EXPORT_CONSTEXPR size_t export_elem_size(int dtype)
+{
+    return dtype == H264MI_TENSOR_U8 ? 1 : dtype == H264MI_TENSOR_F32 ? 4 : 2;
+}
+
+/* the element types of the MB side-information and residual exports: a float or int16 */
+static inline int export_dtype_field(int dtype)
+{
+    return dtype == H264MI_TENSOR_F16 || dtype == H264MI_TENSOR_BF16 || dtype == H264MI_TENSOR_F32 ||
+           dtype == H264MI_TENSOR_I16;
+}
+
+/* d_out, and the distance between two pictures, are multiples of the element size */
+static inline int export_aligned(const void *d_out, size_t out_stride, size_t es)
+{
+    return !(((size_t)(uintptr_t)d_out | out_stride) & (es - 1));
+}
+
+/* h264mi_tensor_desc: a pixel window is even and lies inside width x height */
+static inline int tensor_desc_fixed_ok(const h264mi_tensor_desc *t)
+{
+    return t->dtype >= H264MI_TENSOR_U8 && t->dtype <= H264MI_TENSOR_F32;
+}
+
+static inline int tensor_window_ok(const h264mi_tensor_desc *t, int width, int height)
+{
+    return t->x >= 0 && t->y >= 0 && t->cw > 0 && t->ch > 0 && !((t->x | t->y | t->cw | t->ch) & 1) &&
+           t->cw <= width - t->x && t->ch <= height - t->y;
+}
+
+/* h264mi_tensor_resize_desc: at most 32 source samples per output and axis */
+static inline int resize_desc_fixed_ok(const h264mi_tensor_resize_desc *d)
+{
+    return tensor_desc_fixed_ok(&d->t) && d->filter == H264MI_RESIZE_TRIANGLE && d->ow >= 1 && d->oh >= 1 &&
+           d->ow <= H264MI_RESIZE_MAX_DIM && d->oh <= H264MI_RESIZE_MAX_DIM;
+}
+
+static inline int resize_window_ok(const h264mi_tensor_resize_desc *d, int width, int height)
+{
+    return tensor_window_ok(&d->t, width, height) && d->t.cw <= H264MI_RESIZE_MAX_DIM &&
+           d->t.ch <= H264MI_RESIZE_MAX_DIM && d->t.cw <= 32 * d->ow && d->t.ch <= 32 * d->oh;
+}
+
+/* h264mi_mbinfo_desc: the window is in 4x4 blocks of a w_mbs x h_mbs picture */
+static inline int mbinfo_desc_fixed_ok(const h264mi_mbinfo_desc *d)
+{
+    if (d->nch < 1 || d->nch > H264MI_MBINFO_MAX_CH || !export_dtype_field(d->dtype)) return 0;
+    for (int c = 0; c < d->nch; c++)
+        if (d->ch[c] < 0 || d->ch[c] >= H264MI_MBINFO_NCHANNELS) return 0;
+    return 1;
+}
+
+static inline int mbinfo_window_ok(const h264mi_mbinfo_desc *d, int w_mbs, int h_mbs)
+{
+    return d->bx >= 0 && d->by >= 0 && d->bw >= 1 && d->bh >= 1 && d->bw <= 4 * w_mbs - d->bx &&
+           d->bh <= 4 * h_mbs - d->by;
+}
+
+/* h264mi_residual_desc: the window is in luma samples of the MB-aligned picture, even for UV */
+static inline int residual_desc_fixed_ok(const h264mi_residual_desc *d)
+{
+    return (d->planes == H264MI_RESID_Y || d->planes == H264MI_RESID_UV || d->planes == H264MI_RESID_YUV) &&
+           export_dtype_field(d->dtype);
+}
+
+static inline int residual_window_ok(const h264mi_residual_desc *d, int w_mbs, int h_mbs)
+{
+    return d->x >= 0 && d->y >= 0 && d->cw >= 1 && d->ch >= 1 && d->cw <= 16 * w_mbs - d->x &&
+           d->ch <= 16 * h_mbs - d->y && (d->planes != H264MI_RESID_UV || !((d->x | d->y | d->cw | d->ch) & 1));
+}
+
+/* An SPS's crop window in luma samples (the whole picture without cropping;
+ * the offsets are in the SPS's units of 2 samples) */
+typedef struct { int x, y, cw, ch; } export_window;
+
+static inline export_window export_crop_window(int w_mbs, int h_mbs, int crop, int crop_l, int crop_r, int crop_t,
+                                               int crop_b)
+{
+    export_window w = {0, 0, 16 * w_mbs, 16 * h_mbs};
+    if (crop) {
+        w.x = 2 * crop_l; w.y = 2 * crop_t;
+        w.cw -= 2 * (crop_l + crop_r); w.ch -= 2 * (crop_t + crop_b);
+    }
+    return w;
+}
+
+/* the 4x4 blocks that cover a window of luma samples, as (bx, by, bw, bh) */
+static inline export_window export_window_blocks(export_window w)
+{
+    export_window b = {w.x >> 2, w.y >> 2, 0, 0};
+    b.cw = ((w.x + w.cw + 3) >> 2) - b.x;
+    b.ch = ((w.y + w.ch + 3) >> 2) - b.y;
+    return b;
+}
+
+#endif

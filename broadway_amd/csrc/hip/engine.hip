@@ -14,9 +14,11 @@
 
 #include <stdio.h>
 #include <atomic>
+#include <vector>
 #include <stdlib.h>
 #include <string.h>
 #include "../../../include/h264mi.h"
+#include "../common/export_desc.h"
 #include "engine_int.h"
 
 #define HIPCHECK(x)                                                                    \
@@ -89,7 +91,7 @@ struct h264mi_engine {
     int tev_cap, tev_n;
     int tev_stride, tev_seq;  // record every tev_stride-th launch (h264mi_engine_set_timing_stride)
     uint8_t *d_rgba;          // h264mi_engine_read_rgba / _read_crop staging (w*h*4 B, allocated on first use)
-    hipEvent_t ev_exp_in, ev_exp_out;   // h264mi_engine_export_tensor: the caller's stream -> ours -> the caller's (created on first use)
+    hipEvent_t ev_exp_in, ev_exp_out;   // export_ordered, every export into the caller's memory: the caller's stream -> ours -> the caller's (created on first use)
     MbRec *d_keep;            // h264mi_engine_keep_records: per (stream, slot) the records of the last reconstruction into it (NULL: off),
                               // and one more batch that stays 0xFF ("no information")
     int keep_rec;             // the caller's own switch (d_keep is also held while d_keepc is)
@@ -1101,9 +1103,7 @@ static bool tensor_mode_ok(int mode)
 // h264mi_crop_device_pitch's)
 static bool tensor_desc_ok(const h264mi_tensor_desc *t, int width, int height)
 {
-    return t && t->x >= 0 && t->y >= 0 && t->cw > 0 && t->ch > 0 && !((t->x | t->y | t->cw | t->ch) & 1) &&
-           t->cw <= width - t->x && t->ch <= height - t->y && tensor_mode_ok(t->mode) &&
-           t->dtype >= H264MI_TENSOR_U8 && t->dtype <= H264MI_TENSOR_F32;
+    return t && tensor_mode_ok(t->mode) && tensor_desc_fixed_ok(t) && tensor_window_ok(t, width, height);
 }
 
 extern "C" int h264mi_tensor_colour_coeffs(int id, int out[6])
@@ -1117,9 +1117,88 @@ extern "C" int h264mi_tensor_colour_coeffs(int id, int out[6])
 // a resize descriptor h264mi_tensor_resize_device_pitch accepts
 static bool resize_desc_ok(const h264mi_tensor_resize_desc *d, int width, int height)
 {
-    return d && tensor_desc_ok(&d->t, width, height) && d->filter == H264MI_RESIZE_TRIANGLE && d->ow >= 1 &&
-           d->oh >= 1 && d->ow <= RESIZE_MAX_DIM && d->oh <= RESIZE_MAX_DIM && d->t.cw <= RESIZE_MAX_DIM &&
-           d->t.ch <= RESIZE_MAX_DIM && d->t.cw <= 32 * d->ow && d->t.ch <= 32 * d->oh;
+    return d && tensor_mode_ok(d->t.mode) && resize_desc_fixed_ok(d) && resize_window_ok(d, width, height);
+}
+
+// a field descriptor h264mi_mbinfo_device accepts on a w_mbs x h_mbs picture
+static bool mbinfo_desc_ok(const h264mi_mbinfo_desc *d, int w_mbs, int h_mbs)
+{
+    return d && mbinfo_desc_fixed_ok(d) && mbinfo_window_ok(d, w_mbs, h_mbs);
+}
+
+// a residual descriptor h264mi_residual_device accepts on a w_mbs x h_mbs picture
+static bool residual_desc_ok(const h264mi_residual_desc *d, int w_mbs, int h_mbs)
+{
+    return d && residual_desc_fixed_ok(d) && residual_window_ok(d, w_mbs, h_mbs);
+}
+
+#define EXPORT_MAX_PICS TENSOR_MAX_PICS
+static_assert(MBINFO_MAX_PICS == EXPORT_MAX_PICS && RESID_MAX_PICS == EXPORT_MAX_PICS,
+              "every export kernel takes the same number of pictures per launch");
+static_assert(H264MI_RESIZE_MAX_DIM == RESIZE_MAX_DIM, "common/export_desc.h and resize.hip name the same bound");
+static_assert(export_elem_size(H264MI_TENSOR_U8) == tensor_elem_size(TENSOR_U8) &&
+                  export_elem_size(H264MI_TENSOR_F16) == tensor_elem_size(TENSOR_F16) &&
+                  export_elem_size(H264MI_TENSOR_BF16) == tensor_elem_size(TENSOR_BF16) &&
+                  export_elem_size(H264MI_TENSOR_F32) == tensor_elem_size(TENSOR_F32) &&
+                  export_elem_size(H264MI_TENSOR_I16) == tensor_elem_size(TENSOR_I16),
+              "common/export_desc.h and tensor.hip give the element types the same sizes");
+
+// the kernels may store 16 bytes at a time: every row of row_bytes bytes of
+// every picture (out_stride apart) starts on a multiple of 16
+static bool export_v16(const void *d_out, size_t out_stride, size_t row_bytes)
+{
+    return !(((size_t)(uintptr_t)d_out | out_stride | row_bytes) & 15);
+}
+
+// The launches of a *_device entry point over npics pictures, at most
+// EXPORT_MAX_PICS each: a launch's offsets into a_off, zero-padded, and its
+// first picture's address into *a_out, then launch(k0, n) for the n pictures
+// from k0 on.
+template <class Launch>
+static int export_launches(int npics, const size_t *offsets, unsigned long long *a_off, uint8_t **a_out, void *d_out,
+                           size_t out_stride, Launch launch)
+{
+    for (int k0 = 0; k0 < npics; k0 += EXPORT_MAX_PICS) {
+        const int n = npics - k0 < EXPORT_MAX_PICS ? npics - k0 : EXPORT_MAX_PICS;
+        for (int k = 0; k < EXPORT_MAX_PICS; k++) a_off[k] = k < n ? offsets[k0 + k] : 0;
+        *a_out = (uint8_t *)d_out + (size_t)k0 * out_stride;
+        launch(k0, n);
+        HIPCHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+// Both tensor exports (r != NULL: resized, t = &r->t): one check and one fill
+// of what their kernels share, resize_args::t
+static int tensor_device(const void *d_in, const size_t *in_offsets, int npics, int width, int height, int cpitch,
+                         const h264mi_tensor_desc *t, const h264mi_tensor_resize_desc *r, void *d_out,
+                         size_t out_stride, hipStream_t stream)
+{
+    static_assert(H264MI_TENSOR_RGB == TENSOR_RGB && H264MI_TENSOR_GRAY == TENSOR_GRAY &&
+                      H264MI_TENSOR_U8 == TENSOR_U8 && H264MI_TENSOR_F16 == TENSOR_F16 &&
+                      H264MI_TENSOR_BF16 == TENSOR_BF16 && H264MI_TENSOR_F32 == TENSOR_F32 &&
+                      H264MI_TENSOR_COLOUR_BT709_FULL == TENSOR_COLOUR_SETS - 1,
+                  "include/h264mi.h and tensor.hip name the same modes, element types and colour sets");
+    if (!d_in || !in_offsets || !d_out || width <= 0 || height <= 0 || ((width | height) & 1) || npics < 1 ||
+        cpitch < width / 2 || (r ? !resize_desc_ok(r, width, height) : !tensor_desc_ok(t, width, height)))
+        return -1;
+    const size_t es = export_elem_size(t->dtype);
+    if (!export_aligned(d_out, out_stride, es)) return -1;
+    const bool v16 = export_v16(d_out, out_stride, (size_t)t->cw * es);
+    const int layout = H264MI_TENSOR_LAYOUT(t->mode), colour = H264MI_TENSOR_COLOUR(t->mode);
+    resize_args ra;
+    tensor_args &a = ra.t;
+    a.in = (const uint8_t *)d_in;
+    a.width = width; a.height = height; a.cpitch = cpitch;
+    a.x = t->x; a.y = t->y; a.cw = t->cw; a.ch = t->ch;
+    a.out_stride = out_stride;
+    for (int p = 0; p < 3; p++) { a.scale[p] = t->scale[p]; a.bias[p] = t->bias[p]; }
+    a.col = tensor_colour_sets[colour];     // (set 0 runs the kernels with the reference's literals)
+    if (r) { ra.ow = r->ow; ra.oh = r->oh; }
+    return export_launches(npics, in_offsets, a.in_off, &a.out, d_out, out_stride, [&](int, int n) {
+        if (r) resize_launch(layout, t->dtype, colour != 0, n, stream, ra);
+        else tensor_launch(layout, t->dtype, v16, colour != 0, n, stream, a);
+    });
 }
 
 // Pictures as planar tensors (tensor.hip): the window desc->(x, y, cw, ch) of
@@ -1132,34 +1211,7 @@ extern "C" int h264mi_tensor_device_pitch(const void *d_in, const size_t *in_off
                                           int cpitch, const h264mi_tensor_desc *desc, void *d_out, size_t out_stride,
                                           void *stream)
 {
-    static_assert(H264MI_TENSOR_RGB == TENSOR_RGB && H264MI_TENSOR_GRAY == TENSOR_GRAY &&
-                      H264MI_TENSOR_U8 == TENSOR_U8 && H264MI_TENSOR_F16 == TENSOR_F16 &&
-                      H264MI_TENSOR_BF16 == TENSOR_BF16 && H264MI_TENSOR_F32 == TENSOR_F32 &&
-                      H264MI_TENSOR_COLOUR_BT709_FULL == TENSOR_COLOUR_SETS - 1,
-                  "include/h264mi.h and tensor.hip name the same modes, element types and colour sets");
-    if (!d_in || !in_offsets || !d_out || width <= 0 || height <= 0 || ((width | height) & 1) || npics < 1 ||
-        cpitch < width / 2 || !tensor_desc_ok(desc, width, height))
-        return -1;
-    const size_t es = (size_t)tensor_elem_size(desc->dtype);
-    if (((size_t)(uintptr_t)d_out | out_stride) & (es - 1)) return -1;
-    const bool v16 = !(((size_t)(uintptr_t)d_out | out_stride | (size_t)desc->cw * es) & 15);
-    tensor_args a;
-    a.in = (const uint8_t *)d_in;
-    a.width = width; a.height = height; a.cpitch = cpitch;
-    a.x = desc->x; a.y = desc->y; a.cw = desc->cw; a.ch = desc->ch;
-    a.out_stride = out_stride;
-    for (int p = 0; p < 3; p++) { a.scale[p] = desc->scale[p]; a.bias[p] = desc->bias[p]; }
-    // (set 0 runs the kernels with the reference's literals)
-    const int colour = H264MI_TENSOR_COLOUR(desc->mode);
-    a.col = tensor_colour_sets[colour];
-    for (int k0 = 0; k0 < npics; k0 += TENSOR_MAX_PICS) {
-        const int n = npics - k0 < TENSOR_MAX_PICS ? npics - k0 : TENSOR_MAX_PICS;
-        for (int k = 0; k < TENSOR_MAX_PICS; k++) a.in_off[k] = k < n ? in_offsets[k0 + k] : 0;
-        a.out = (uint8_t *)d_out + (size_t)k0 * out_stride;
-        tensor_launch(H264MI_TENSOR_LAYOUT(desc->mode), desc->dtype, v16, colour != 0, n, (hipStream_t)stream, a);
-        HIPCHECK(hipGetLastError());
-    }
-    return 0;
+    return tensor_device(d_in, in_offsets, npics, width, height, cpitch, desc, NULL, d_out, out_stride, (hipStream_t)stream);
 }
 
 // The same pictures resized (resize.hip): the window filtered to desc->oh x
@@ -1172,68 +1224,49 @@ extern "C" int h264mi_tensor_resize_device_pitch(const void *d_in, const size_t 
                                                  int height, int cpitch, const h264mi_tensor_resize_desc *desc,
                                                  void *d_out, size_t out_stride, void *stream)
 {
-    if (!d_in || !in_offsets || !d_out || width <= 0 || height <= 0 || ((width | height) & 1) || npics < 1 ||
-        cpitch < width / 2 || !resize_desc_ok(desc, width, height))
-        return -1;
-    const h264mi_tensor_desc *t = &desc->t;
-    const size_t es = (size_t)tensor_elem_size(t->dtype);
-    if (((size_t)(uintptr_t)d_out | out_stride) & (es - 1)) return -1;
-    resize_args a;
-    a.t.in = (const uint8_t *)d_in;
-    a.t.width = width; a.t.height = height; a.t.cpitch = cpitch;
-    a.t.x = t->x; a.t.y = t->y; a.t.cw = t->cw; a.t.ch = t->ch;
-    a.t.out_stride = out_stride;
-    a.ow = desc->ow; a.oh = desc->oh;
-    for (int p = 0; p < 3; p++) { a.t.scale[p] = t->scale[p]; a.t.bias[p] = t->bias[p]; }
-    const int colour = H264MI_TENSOR_COLOUR(t->mode);
-    a.t.col = tensor_colour_sets[colour];
-    for (int k0 = 0; k0 < npics; k0 += TENSOR_MAX_PICS) {
-        const int n = npics - k0 < TENSOR_MAX_PICS ? npics - k0 : TENSOR_MAX_PICS;
-        for (int k = 0; k < TENSOR_MAX_PICS; k++) a.t.in_off[k] = k < n ? in_offsets[k0 + k] : 0;
-        a.t.out = (uint8_t *)d_out + (size_t)k0 * out_stride;
-        resize_launch(H264MI_TENSOR_LAYOUT(t->mode), t->dtype, colour != 0, n, (hipStream_t)stream, a);
-        HIPCHECK(hipGetLastError());
-    }
-    return 0;
+    return tensor_device(d_in, in_offsets, npics, width, height, cpitch, desc ? &desc->t : NULL, desc, d_out, out_stride,
+                         (hipStream_t)stream);
 }
 
-// The slots (streams[k], slots[k]), k < n, as tensors in the caller's device
-// memory, with no host synchronisation: the engine's stream waits for what
-// `stream` (NULL: the null stream; ours is non-blocking, so that too goes
-// through events) holds already -- d_out may have been recycled on it --, the
-// kernel runs on the engine's stream, behind every launch queued so far and
-// ahead of every later one, and `stream` waits for the kernel.
-// (rdesc != NULL: resized, desc = &rdesc->t)
-static int engine_export(h264mi_engine *e, int n, const int *streams, const int *slots, const h264mi_tensor_desc *desc,
-                         const h264mi_tensor_resize_desc *rdesc, void *d_out, size_t out_stride, void *stream)
+// An export of the slots (streams[k], slots[k]), k < n, into the caller's
+// device memory with no host synchronisation: the engine's stream waits for
+// what `stream` (NULL: the null stream; ours is non-blocking, so that too goes
+// through events) holds already -- d_out may have been recycled on it --,
+// launch() queues the kernels on the engine's stream, behind every launch
+// queued so far and ahead of every later one, and `stream` waits for them.
+// es: the element size d_out and out_stride are multiples of.
+template <class Launch>
+static int export_ordered(h264mi_engine *e, int n, const int *streams, const int *slots, void *d_out, size_t out_stride,
+                          size_t es, void *stream, Launch launch)
 {
-    if (!e || n < 1 || !streams || !slots || !d_out) return -1;
-    if (rdesc ? !resize_desc_ok(rdesc, e->w * 16, e->h * 16) : !tensor_desc_ok(desc, e->w * 16, e->h * 16)) return -1;
     for (int k = 0; k < n; k++)
         if (streams[k] < 0 || streams[k] >= e->nstreams || slots[k] < 0 || slots[k] >= e->nslots) return -1;
-    const size_t es = (size_t)tensor_elem_size(desc->dtype);
-    if (((size_t)(uintptr_t)d_out | out_stride) & (es - 1)) return -1;
+    if (!export_aligned(d_out, out_stride, es)) return -1;
     if (h264mi_pointer_device(d_out) != e->dev) return -1;
     HIPCHECK(hipSetDevice(e->dev));
     if (!e->ev_exp_in) HIPCHECK(hipEventCreateWithFlags(&e->ev_exp_in, hipEventDisableTiming));
     if (!e->ev_exp_out) HIPCHECK(hipEventCreateWithFlags(&e->ev_exp_out, hipEventDisableTiming));
     HIPCHECK(hipEventRecord(e->ev_exp_in, (hipStream_t)stream));
     HIPCHECK(hipStreamWaitEvent(e->st, e->ev_exp_in, 0));
-    int rc = 0;
-    for (int k0 = 0; k0 < n && !rc; k0 += TENSOR_MAX_PICS) {
-        size_t off[TENSOR_MAX_PICS];
-        const int m = n - k0 < TENSOR_MAX_PICS ? n - k0 : TENSOR_MAX_PICS;
-        for (int k = 0; k < m; k++) off[k] = e->frame_bytes * ((size_t)streams[k0 + k] * e->nslots + slots[k0 + k]);
-        uint8_t *o = (uint8_t *)d_out + (size_t)k0 * out_stride;
-        rc = rdesc ? h264mi_tensor_resize_device_pitch(e->d_frames, off, m, e->w * 16, e->h * 16, e->cpitch, rdesc, o,
-                                                       out_stride, e->st)
-                   : h264mi_tensor_device_pitch(e->d_frames, off, m, e->w * 16, e->h * 16, e->cpitch, desc, o,
-                                                out_stride, e->st);
-    }
+    const int rc = launch();
     // (also after a failed launch: whatever reached our stream stays ordered)
     HIPCHECK(hipEventRecord(e->ev_exp_out, e->st));
     HIPCHECK(hipStreamWaitEvent((hipStream_t)stream, e->ev_exp_out, 0));
     return rc;
+}
+
+// the frame slots as tensors (rdesc != NULL: resized, desc = &rdesc->t)
+static int engine_export(h264mi_engine *e, int n, const int *streams, const int *slots, const h264mi_tensor_desc *desc,
+                         const h264mi_tensor_resize_desc *rdesc, void *d_out, size_t out_stride, void *stream)
+{
+    if (!e || n < 1 || !streams || !slots || !d_out) return -1;
+    const int width = e->w * 16, height = e->h * 16;
+    if (rdesc ? !resize_desc_ok(rdesc, width, height) : !tensor_desc_ok(desc, width, height)) return -1;
+    return export_ordered(e, n, streams, slots, d_out, out_stride, export_elem_size(desc->dtype), stream, [&] {
+        std::vector<size_t> off((size_t)n);
+        for (int k = 0; k < n; k++) off[k] = e->frame_bytes * ((size_t)streams[k] * e->nslots + slots[k]);
+        return tensor_device(e->d_frames, off.data(), n, width, height, e->cpitch, desc, rdesc, d_out, out_stride, e->st);
+    });
 }
 
 extern "C" int h264mi_engine_export_tensor(h264mi_engine *e, int n, const int *streams, const int *slots,
@@ -1242,25 +1275,12 @@ extern "C" int h264mi_engine_export_tensor(h264mi_engine *e, int n, const int *s
     return engine_export(e, n, streams, slots, desc, NULL, d_out, out_stride, stream);
 }
 
-// the same, resized (h264mi_tensor_resize_device_pitch); the same pair of events
+// the same, resized (h264mi_tensor_resize_device_pitch)
 extern "C" int h264mi_engine_export_tensor_resized(h264mi_engine *e, int n, const int *streams, const int *slots,
                                                    const h264mi_tensor_resize_desc *desc, void *d_out,
                                                    size_t out_stride, void *stream)
 {
     return engine_export(e, n, streams, slots, desc ? &desc->t : NULL, desc, d_out, out_stride, stream);
-}
-
-// a field descriptor h264mi_mbinfo_device accepts on a w_mbs x h_mbs picture
-static bool mbinfo_desc_ok(const h264mi_mbinfo_desc *d, int w_mbs, int h_mbs)
-{
-    if (!d || d->bx < 0 || d->by < 0 || d->bw < 1 || d->bh < 1 || d->bw > 4 * w_mbs - d->bx || d->bh > 4 * h_mbs - d->by ||
-        d->nch < 1 || d->nch > H264MI_MBINFO_MAX_CH ||
-        (d->dtype != H264MI_TENSOR_F16 && d->dtype != H264MI_TENSOR_BF16 && d->dtype != H264MI_TENSOR_F32 &&
-         d->dtype != H264MI_TENSOR_I16))
-        return false;
-    for (int c = 0; c < d->nch; c++)
-        if (d->ch[c] < 0 || d->ch[c] >= H264MI_MBINFO_NCHANNELS) return false;
-    return true;
 }
 
 // Motion vectors and MB side information as planar fields (mbinfo.hip): the
@@ -1284,9 +1304,9 @@ extern "C" int h264mi_mbinfo_device(const void *d_recs, const size_t *rec_offset
         return -1;
     for (int k = 0; k < npics; k++)
         if (rec_offsets[k] % sizeof(MbRec)) return -1;
-    const size_t es = (size_t)tensor_elem_size(desc->dtype);
-    if (((size_t)(uintptr_t)d_out | out_stride) & (es - 1)) return -1;
-    const bool v16 = !(((size_t)(uintptr_t)d_out | out_stride | (size_t)desc->bw * es) & 15);
+    const size_t es = export_elem_size(desc->dtype);
+    if (!export_aligned(d_out, out_stride, es)) return -1;
+    const bool v16 = export_v16(d_out, out_stride, (size_t)desc->bw * es);
     mbinfo_args a;
     a.rec = (const uint8_t *)d_recs;
     a.w_mbs = w_mbs;
@@ -1297,14 +1317,8 @@ extern "C" int h264mi_mbinfo_device(const void *d_recs, const size_t *rec_offset
         a.scale[c] = c < desc->nch ? desc->scale[c] : 0.0f;
         a.bias[c] = c < desc->nch ? desc->bias[c] : 0.0f;
     }
-    for (int k0 = 0; k0 < npics; k0 += MBINFO_MAX_PICS) {
-        const int n = npics - k0 < MBINFO_MAX_PICS ? npics - k0 : MBINFO_MAX_PICS;
-        for (int k = 0; k < MBINFO_MAX_PICS; k++) a.off[k] = k < n ? rec_offsets[k0 + k] : 0;
-        a.out = (uint8_t *)d_out + (size_t)k0 * out_stride;
-        mbinfo_launch(desc->dtype, v16, n, (hipStream_t)stream, a);
-        HIPCHECK(hipGetLastError());
-    }
-    return 0;
+    return export_launches(npics, rec_offsets, a.off, &a.out, d_out, out_stride,
+                           [&](int, int n) { mbinfo_launch(desc->dtype, v16, n, (hipStream_t)stream, a); });
 }
 
 // Record retention: one batch per (stream, slot), 0xFF-filled ("no
@@ -1381,46 +1395,16 @@ extern "C" int h264mi_engine_forget_records(h264mi_engine *e, int stream, int sl
 }
 
 // The kept batches of the slots (streams[k], slots[k]) as fields in the
-// caller's memory: ordered between the caller's stream and ours as
-// engine_export orders a tensor export, with the same pair of events
+// caller's memory, ordered between the caller's stream and ours by export_ordered
 extern "C" int h264mi_engine_export_mbinfo(h264mi_engine *e, int n, const int *streams, const int *slots,
                                            const h264mi_mbinfo_desc *desc, void *d_out, size_t out_stride, void *stream)
 {
     if (!e || !e->d_keep || n < 1 || !streams || !slots || !d_out || !mbinfo_desc_ok(desc, e->w, e->h)) return -1;
-    for (int k = 0; k < n; k++)
-        if (streams[k] < 0 || streams[k] >= e->nstreams || slots[k] < 0 || slots[k] >= e->nslots) return -1;
-    const size_t es = (size_t)tensor_elem_size(desc->dtype);
-    if (((size_t)(uintptr_t)d_out | out_stride) & (es - 1)) return -1;
-    if (h264mi_pointer_device(d_out) != e->dev) return -1;
-    HIPCHECK(hipSetDevice(e->dev));
-    if (!e->ev_exp_in) HIPCHECK(hipEventCreateWithFlags(&e->ev_exp_in, hipEventDisableTiming));
-    if (!e->ev_exp_out) HIPCHECK(hipEventCreateWithFlags(&e->ev_exp_out, hipEventDisableTiming));
-    HIPCHECK(hipEventRecord(e->ev_exp_in, (hipStream_t)stream));
-    HIPCHECK(hipStreamWaitEvent(e->st, e->ev_exp_in, 0));
-    int rc = 0;
-    for (int k0 = 0; k0 < n && !rc; k0 += MBINFO_MAX_PICS) {
-        size_t off[MBINFO_MAX_PICS];
-        const int m = n - k0 < MBINFO_MAX_PICS ? n - k0 : MBINFO_MAX_PICS;
-        for (int k = 0; k < m; k++)
-            off[k] = sizeof(MbRec) * e->nmbs * ((size_t)streams[k0 + k] * e->nslots + slots[k0 + k]);
-        rc = h264mi_mbinfo_device(e->d_keep, off, m, e->w, e->h, desc, (uint8_t *)d_out + (size_t)k0 * out_stride,
-                                  out_stride, e->st);
-    }
-    // (also after a failed launch: whatever reached our stream stays ordered)
-    HIPCHECK(hipEventRecord(e->ev_exp_out, e->st));
-    HIPCHECK(hipStreamWaitEvent((hipStream_t)stream, e->ev_exp_out, 0));
-    return rc;
-}
-
-// a residual descriptor h264mi_residual_device accepts on a w_mbs x h_mbs picture
-static bool residual_desc_ok(const h264mi_residual_desc *d, int w_mbs, int h_mbs)
-{
-    if (!d || d->x < 0 || d->y < 0 || d->cw < 1 || d->ch < 1 || d->cw > 16 * w_mbs - d->x || d->ch > 16 * h_mbs - d->y ||
-        (d->planes != H264MI_RESID_Y && d->planes != H264MI_RESID_UV && d->planes != H264MI_RESID_YUV) ||
-        (d->dtype != H264MI_TENSOR_F16 && d->dtype != H264MI_TENSOR_BF16 && d->dtype != H264MI_TENSOR_F32 &&
-         d->dtype != H264MI_TENSOR_I16))
-        return false;
-    return d->planes != H264MI_RESID_UV || !((d->x | d->y | d->cw | d->ch) & 1);
+    return export_ordered(e, n, streams, slots, d_out, out_stride, export_elem_size(desc->dtype), stream, [&] {
+        std::vector<size_t> off((size_t)n);
+        for (int k = 0; k < n; k++) off[k] = sizeof(MbRec) * e->nmbs * ((size_t)streams[k] * e->nslots + slots[k]);
+        return h264mi_mbinfo_device(e->d_keep, off.data(), n, e->w, e->h, desc, d_out, out_stride, e->st);
+    });
 }
 
 // The decoded residual as planar tensors (residual.hip): the window desc->(x,
@@ -1442,10 +1426,9 @@ extern "C" int h264mi_residual_device(const void *d_recs, const size_t *rec_offs
         return -1;
     for (int k = 0; k < npics; k++)
         if (rec_offsets[k] % sizeof(MbRec)) return -1;
-    const size_t es = (size_t)tensor_elem_size(desc->dtype);
-    if (((size_t)(uintptr_t)d_out | out_stride) & (es - 1)) return -1;
-    const size_t ow = (size_t)(desc->planes == H264MI_RESID_UV ? desc->cw / 2 : desc->cw);
-    const bool v16 = !(((size_t)(uintptr_t)d_out | out_stride | ow * es) & 15);
+    const size_t es = export_elem_size(desc->dtype);
+    if (!export_aligned(d_out, out_stride, es)) return -1;
+    const bool v16 = export_v16(d_out, out_stride, (size_t)(desc->planes == H264MI_RESID_UV ? desc->cw / 2 : desc->cw) * es);
     residual_args a;
     a.rec = (const uint8_t *)d_recs;
     a.coef = (const int16_t *)d_coef;
@@ -1454,17 +1437,10 @@ extern "C" int h264mi_residual_device(const void *d_recs, const size_t *rec_offs
     a.x = desc->x; a.y = desc->y; a.cw = desc->cw; a.ch = desc->ch; a.planes = desc->planes;
     a.out_stride = out_stride;
     for (int c = 0; c < 3; c++) { a.scale[c] = desc->scale[c]; a.bias[c] = desc->bias[c]; }
-    for (int k0 = 0; k0 < npics; k0 += RESID_MAX_PICS) {
-        const int n = npics - k0 < RESID_MAX_PICS ? npics - k0 : RESID_MAX_PICS;
-        for (int k = 0; k < RESID_MAX_PICS; k++) {
-            a.off[k] = k < n ? rec_offsets[k0 + k] : 0;
-            a.cbase[k] = k < n ? coef_bases[k0 + k] : 0;
-        }
-        a.out = (uint8_t *)d_out + (size_t)k0 * out_stride;
+    return export_launches(npics, rec_offsets, a.off, &a.out, d_out, out_stride, [&](int k0, int n) {
+        for (int k = 0; k < RESID_MAX_PICS; k++) a.cbase[k] = k < n ? coef_bases[k0 + k] : 0;
         residual_launch(desc->dtype, v16, n, (hipStream_t)stream, a);
-        HIPCHECK(hipGetLastError());
-    }
-    return 0;
+    });
 }
 
 // The kept records and coefficients of the slots (streams[k], slots[k]) as
@@ -1478,34 +1454,18 @@ extern "C" int h264mi_engine_export_residual(h264mi_engine *e, int n, const int 
 {
     if (!e || !e->d_keepc || !e->d_keep || n < 1 || !streams || !slots || !d_out || !residual_desc_ok(desc, e->w, e->h))
         return -1;
-    for (int k = 0; k < n; k++)
-        if (streams[k] < 0 || streams[k] >= e->nstreams || slots[k] < 0 || slots[k] >= e->nslots) return -1;
-    const size_t es = (size_t)tensor_elem_size(desc->dtype);
-    if (((size_t)(uintptr_t)d_out | out_stride) & (es - 1)) return -1;
-    if (h264mi_pointer_device(d_out) != e->dev) return -1;
-    HIPCHECK(hipSetDevice(e->dev));
-    if (!e->ev_exp_in) HIPCHECK(hipEventCreateWithFlags(&e->ev_exp_in, hipEventDisableTiming));
-    if (!e->ev_exp_out) HIPCHECK(hipEventCreateWithFlags(&e->ev_exp_out, hipEventDisableTiming));
-    HIPCHECK(hipEventRecord(e->ev_exp_in, (hipStream_t)stream));
-    HIPCHECK(hipStreamWaitEvent(e->st, e->ev_exp_in, 0));
-    const size_t nb = (size_t)e->nslots * e->nstreams;
-    int rc = 0;
-    for (int k0 = 0; k0 < n && !rc; k0 += RESID_MAX_PICS) {
-        size_t off[RESID_MAX_PICS];
-        uint32_t cbase[RESID_MAX_PICS];
-        const int m = n - k0 < RESID_MAX_PICS ? n - k0 : RESID_MAX_PICS;
-        for (int k = 0; k < m; k++) {
-            const size_t b = (size_t)streams[k0 + k] * e->nslots + slots[k0 + k];
+    return export_ordered(e, n, streams, slots, d_out, out_stride, export_elem_size(desc->dtype), stream, [&] {
+        const size_t nb = (size_t)e->nslots * e->nstreams;
+        std::vector<size_t> off((size_t)n);
+        std::vector<uint32_t> cbase((size_t)n);
+        for (int k = 0; k < n; k++) {
+            const size_t b = (size_t)streams[k] * e->nslots + slots[k];
             off[k] = sizeof(MbRec) * e->nmbs * (e->keepc_ok[b] ? b : nb);
             cbase[k] = (uint32_t)(b * keepc_cap(e));
         }
-        rc = h264mi_residual_device(e->d_keep, off, e->d_keepc, cbase, nb * keepc_cap(e), m, e->w, e->h, desc,
-                                    (uint8_t *)d_out + (size_t)k0 * out_stride, out_stride, e->st);
-    }
-    // (also after a failed launch: whatever reached our stream stays ordered)
-    HIPCHECK(hipEventRecord(e->ev_exp_out, e->st));
-    HIPCHECK(hipStreamWaitEvent((hipStream_t)stream, e->ev_exp_out, 0));
-    return rc;
+        return h264mi_residual_device(e->d_keep, off.data(), e->d_keepc, cbase.data(), nb * keepc_cap(e), n, e->w, e->h,
+                                      desc, d_out, out_stride, e->st);
+    });
 }
 
 extern "C" void *h264mi_engine_frame_ptr(h264mi_engine *e, int stream, int slot)

@@ -14,6 +14,7 @@
  * created the API fails (H264SWDEC_INITFAIL / MEMFAIL) instead of falling
  * back. */
 #include "../../../include/h264mi.h"
+#include "../common/export_desc.h"
 #include "decoder.h"
 
 #include <stdio.h>
@@ -97,11 +98,12 @@ H264SwDecRet H264SwDecGetInfo(H264SwDecInst decInst, H264SwDecInfo *pDecInfo)
     pDecInfo->videoRange = (s->vui_present && s->video_full_range) ? 1 : 0;
     pDecInfo->matrixCoefficients = (s->vui_present && s->colour_desc_present) ? (u32)s->matrix_coeffs : 2;
     if (s->crop) {
+        const export_window w = sps_crop_window(s);
         pDecInfo->croppingFlag = 1;
-        pDecInfo->cropParams.cropLeftOffset = 2u * (u32)s->crop_l;
-        pDecInfo->cropParams.cropOutWidth = 16u * (u32)s->w_mbs - 2u * (u32)(s->crop_l + s->crop_r);
-        pDecInfo->cropParams.cropTopOffset = 2u * (u32)s->crop_t;
-        pDecInfo->cropParams.cropOutHeight = 16u * (u32)s->h_mbs - 2u * (u32)(s->crop_t + s->crop_b);
+        pDecInfo->cropParams.cropLeftOffset = (u32)w.x;
+        pDecInfo->cropParams.cropOutWidth = (u32)w.cw;
+        pDecInfo->cropParams.cropTopOffset = (u32)w.y;
+        pDecInfo->cropParams.cropOutHeight = (u32)w.ch;
     }
     u32 w = 1, h = 1;
     if (s->vui_present && s->aspect_present) {
@@ -252,44 +254,38 @@ H264SwDecRet H264SwDecNextPictureCropped(H264SwDecInst decInst, H264SwDecPicture
     return H264SWDEC_PIC_RDY;
 }
 
-/* NextPicture with the picture exported to device memory as a planar tensor
- * (include/h264mi.h); desc == NULL: RGB fp16, scale 1/255, over the active
- * SPS's crop window, which a desc with cw == 0 takes as well.  A backend
- * without export_tensor: H264SWDEC_PARAM_ERR, no host fallback. */
-H264SwDecRet H264SwDecNextPictureTensor(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
-                                        const h264mi_tensor_desc *desc, void *d_dst, void *hip_stream)
+/* H264SwDecNextPictureTensor (desc: an h264mi_tensor_desc) and, resized,
+ * ...TensorResized (an h264mi_tensor_resize_desc); a window with cw == 0 is the
+ * active SPS's crop window.  Everything the export can refuse is checked
+ * before a picture is taken from the DPB. */
+static H264SwDecRet next_picture_tensor(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
+                                        const void *desc, int resized, void *d_dst, void *hip_stream)
 {
-    if (decInst == NULL || pOutput == NULL || d_dst == NULL) return H264SWDEC_PARAM_ERR;
+    if (decInst == NULL || pOutput == NULL || d_dst == NULL || desc == NULL) return H264SWDEC_PARAM_ERR;
     DecContainer *c = (DecContainer *)decInst;
-    if (!c->dec.be.export_tensor) return H264SWDEC_PARAM_ERR;
-    h264mi_tensor_desc t;
-    if (desc) {
-        t = *desc;
-    } else {
-        memset(&t, 0, sizeof(t));
-        t.mode = H264MI_TENSOR_RGB;
-        t.dtype = H264MI_TENSOR_F16;
-        for (int p = 0; p < 3; p++) t.scale[p] = 1.0f / 255.0f;
-    }
-    if (h264mi_tensor_colour_resolve(t.mode, 2, 0, 2, 2) < 0 || t.dtype < H264MI_TENSOR_U8 || t.dtype > H264MI_TENSOR_F32)
+    if (!(resized ? c->dec.be.export_tensor_resized : c->dec.be.export_tensor)) return H264SWDEC_PARAM_ERR;
+    h264mi_tensor_resize_desc r;
+    memset(&r, 0, sizeof(r));
+    if (resized) r = *(const h264mi_tensor_resize_desc *)desc;
+    else r.t = *(const h264mi_tensor_desc *)desc;
+    h264mi_tensor_desc *t = &r.t;
+    if (h264mi_tensor_colour_resolve(t->mode, 2, 0, 2, 2) < 0 ||
+        !(resized ? resize_desc_fixed_ok(&r) : tensor_desc_fixed_ok(t)) ||
+        !export_aligned(d_dst, 0, export_elem_size(t->dtype)))
         return H264SWDEC_PARAM_ERR;
-    const size_t es = t.dtype == H264MI_TENSOR_U8 ? 1 : t.dtype == H264MI_TENSOR_F32 ? 4 : 2;
-    if ((size_t)(uintptr_t)d_dst & (es - 1)) return H264SWDEC_PARAM_ERR;
     if (flushBuffer) h264dec_flush(&c->dec);
     const Sps *s = h264dec_active_sps(&c->dec);
     if (!s) return H264SWDEC_OK;                    /* no headers yet: no picture either */
-    const int width = 16 * (int)s->w_mbs, height = 16 * (int)s->h_mbs;
-    if (t.cw == 0) {
-        const int cl = s->crop ? 2 * (int)s->crop_l : 0, ct = s->crop ? 2 * (int)s->crop_t : 0;
-        const int cr = s->crop ? 2 * (int)s->crop_r : 0, cb = s->crop ? 2 * (int)s->crop_b : 0;
-        t.x = cl; t.y = ct; t.cw = width - cl - cr; t.ch = height - ct - cb;
+    if (t->cw == 0) {
+        const export_window w = sps_crop_window(s);
+        t->x = w.x; t->y = w.y; t->cw = w.cw; t->ch = w.ch;
     }
-    if (t.x < 0 || t.y < 0 || t.cw <= 0 || t.ch <= 0 || ((t.x | t.y | t.cw | t.ch) & 1) || t.cw > width - t.x ||
-        t.ch > height - t.y)
-        return H264SWDEC_PARAM_ERR;
+    const int width = 16 * s->w_mbs, height = 16 * s->h_mbs;
+    if (!(resized ? resize_window_ok(&r, width, height) : tensor_window_ok(t, width, height))) return H264SWDEC_PARAM_ERR;
     uint32_t id, idr, em;
     int failed = 0;
-    const uint8_t *pic = h264dec_next_output_tensor(&c->dec, &id, &idr, &em, &t, d_dst, hip_stream, &failed);
+    /* (a resize descriptor starts with its h264mi_tensor_desc) */
+    const uint8_t *pic = h264dec_next_output_tensor(&c->dec, &id, &idr, &em, &r, resized, d_dst, hip_stream, &failed);
     if (failed) return H264SWDEC_PARAM_ERR;         /* (d_dst not on the decoder's GPU) */
     if (!pic) return H264SWDEC_OK;
     pOutput->pOutputPicture = (u32 *)(void *)pic;
@@ -299,45 +295,26 @@ H264SwDecRet H264SwDecNextPictureTensor(H264SwDecInst decInst, H264SwDecPicture 
     return H264SWDEC_PIC_RDY;
 }
 
-/* NextPictureTensor with the tensor resized on the GPU (include/h264mi.h);
- * desc->t.cw == 0: the active SPS's crop window.  Everything the export can
- * refuse is checked before a picture is taken from the DPB. */
+/* NextPicture with the picture exported to device memory as a planar tensor
+ * (include/h264mi.h); desc == NULL: RGB fp16, scale 1/255, over the active
+ * SPS's crop window.  A backend without export_tensor: H264SWDEC_PARAM_ERR, no
+ * host fallback. */
+H264SwDecRet H264SwDecNextPictureTensor(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
+                                        const h264mi_tensor_desc *desc, void *d_dst, void *hip_stream)
+{
+    h264mi_tensor_desc t;
+    memset(&t, 0, sizeof(t));
+    t.mode = H264MI_TENSOR_RGB;
+    t.dtype = H264MI_TENSOR_F16;
+    for (int p = 0; p < 3; p++) t.scale[p] = 1.0f / 255.0f;
+    return next_picture_tensor(decInst, pOutput, flushBuffer, desc ? desc : &t, 0, d_dst, hip_stream);
+}
+
+/* NextPictureTensor with the tensor resized on the GPU (include/h264mi.h) */
 H264SwDecRet H264SwDecNextPictureTensorResized(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
                                                const h264mi_tensor_resize_desc *desc, void *d_dst, void *hip_stream)
 {
-    if (decInst == NULL || pOutput == NULL || d_dst == NULL || desc == NULL) return H264SWDEC_PARAM_ERR;
-    DecContainer *c = (DecContainer *)decInst;
-    if (!c->dec.be.export_tensor_resized) return H264SWDEC_PARAM_ERR;
-    h264mi_tensor_resize_desc r = *desc;
-    h264mi_tensor_desc *t = &r.t;
-    if (h264mi_tensor_colour_resolve(t->mode, 2, 0, 2, 2) < 0 || t->dtype < H264MI_TENSOR_U8 ||
-        t->dtype > H264MI_TENSOR_F32 || r.filter != H264MI_RESIZE_TRIANGLE || r.ow < 1 || r.oh < 1 || r.ow > 16384 ||
-        r.oh > 16384)
-        return H264SWDEC_PARAM_ERR;
-    const size_t es = t->dtype == H264MI_TENSOR_U8 ? 1 : t->dtype == H264MI_TENSOR_F32 ? 4 : 2;
-    if ((size_t)(uintptr_t)d_dst & (es - 1)) return H264SWDEC_PARAM_ERR;
-    if (flushBuffer) h264dec_flush(&c->dec);
-    const Sps *s = h264dec_active_sps(&c->dec);
-    if (!s) return H264SWDEC_OK;                    /* no headers yet: no picture either */
-    const int width = 16 * (int)s->w_mbs, height = 16 * (int)s->h_mbs;
-    if (t->cw == 0) {
-        const int cl = s->crop ? 2 * (int)s->crop_l : 0, ct = s->crop ? 2 * (int)s->crop_t : 0;
-        const int cr = s->crop ? 2 * (int)s->crop_r : 0, cb = s->crop ? 2 * (int)s->crop_b : 0;
-        t->x = cl; t->y = ct; t->cw = width - cl - cr; t->ch = height - ct - cb;
-    }
-    if (t->x < 0 || t->y < 0 || t->cw <= 0 || t->ch <= 0 || ((t->x | t->y | t->cw | t->ch) & 1) ||
-        t->cw > width - t->x || t->ch > height - t->y || t->cw > 32 * r.ow || t->ch > 32 * r.oh)
-        return H264SWDEC_PARAM_ERR;
-    uint32_t id, idr, em;
-    int failed = 0;
-    const uint8_t *pic = h264dec_next_output_tensor_resized(&c->dec, &id, &idr, &em, &r, d_dst, hip_stream, &failed);
-    if (failed) return H264SWDEC_PARAM_ERR;         /* (d_dst not on the decoder's GPU) */
-    if (!pic) return H264SWDEC_OK;
-    pOutput->pOutputPicture = (u32 *)(void *)pic;
-    pOutput->picId = id;
-    pOutput->isIdrPicture = idr;
-    pOutput->nbrOfErrMBs = em;
-    return H264SWDEC_PIC_RDY;
+    return next_picture_tensor(decInst, pOutput, flushBuffer, desc, 1, d_dst, hip_stream);
 }
 
 /* the colour id of the last tensor either call above delivered; -1: none yet */
@@ -370,25 +347,14 @@ H264SwDecRet H264SwDecLastPictureMbInfo(H264SwDecInst decInst, const h264mi_mbin
     DecContainer *c = (DecContainer *)decInst;
     if (!c->dec.be.export_mbinfo || !c->dec.keep_mbinfo) return H264SWDEC_PARAM_ERR;
     h264mi_mbinfo_desc m = *desc;
-    if (m.nch < 1 || m.nch > H264MI_MBINFO_MAX_CH ||
-        (m.dtype != H264MI_TENSOR_F16 && m.dtype != H264MI_TENSOR_BF16 && m.dtype != H264MI_TENSOR_F32 &&
-         m.dtype != H264MI_TENSOR_I16))
-        return H264SWDEC_PARAM_ERR;
-    for (int k = 0; k < m.nch; k++)
-        if (m.ch[k] < 0 || m.ch[k] >= H264MI_MBINFO_NCHANNELS) return H264SWDEC_PARAM_ERR;
-    if ((size_t)(uintptr_t)d_dst & (m.dtype == H264MI_TENSOR_F32 ? 3u : 1u)) return H264SWDEC_PARAM_ERR;
+    if (!mbinfo_desc_fixed_ok(&m) || !export_aligned(d_dst, 0, export_elem_size(m.dtype))) return H264SWDEC_PARAM_ERR;
     const Sps *s = h264dec_active_sps(&c->dec);
     if (!s || !c->dec.last_out_slot1) return H264SWDEC_OK;      /* no picture delivered */
-    const int bw_all = 4 * (int)s->w_mbs, bh_all = 4 * (int)s->h_mbs;
     if (m.bw == 0) {
-        const int x = s->crop ? 2 * (int)s->crop_l : 0, y = s->crop ? 2 * (int)s->crop_t : 0;
-        const int cw = 4 * bw_all - x - (s->crop ? 2 * (int)s->crop_r : 0);
-        const int ch = 4 * bh_all - y - (s->crop ? 2 * (int)s->crop_b : 0);
-        m.bx = x >> 2; m.by = y >> 2;
-        m.bw = ((x + cw + 3) >> 2) - m.bx; m.bh = ((y + ch + 3) >> 2) - m.by;
+        const export_window b = export_window_blocks(sps_crop_window(s));
+        m.bx = b.x; m.by = b.y; m.bw = b.cw; m.bh = b.ch;
     }
-    if (m.bx < 0 || m.by < 0 || m.bw < 1 || m.bh < 1 || m.bw > bw_all - m.bx || m.bh > bh_all - m.by)
-        return H264SWDEC_PARAM_ERR;
+    if (!mbinfo_window_ok(&m, s->w_mbs, s->h_mbs)) return H264SWDEC_PARAM_ERR;
     if (c->dec.be.export_mbinfo(c->dec.be.ctx, c->dec.last_out_slot1 - 1, &m, d_dst, hip_stream))
         return H264SWDEC_PARAM_ERR;         /* (d_dst not on the decoder's GPU) */
     return H264SWDEC_PIC_RDY;
@@ -416,23 +382,14 @@ H264SwDecRet H264SwDecLastPictureResidual(H264SwDecInst decInst, const h264mi_re
     DecContainer *c = (DecContainer *)decInst;
     if (!c->dec.be.export_residual || !c->dec.keep_residual) return H264SWDEC_PARAM_ERR;
     h264mi_residual_desc m = *desc;
-    if ((m.planes != H264MI_RESID_Y && m.planes != H264MI_RESID_UV && m.planes != H264MI_RESID_YUV) ||
-        (m.dtype != H264MI_TENSOR_F16 && m.dtype != H264MI_TENSOR_BF16 && m.dtype != H264MI_TENSOR_F32 &&
-         m.dtype != H264MI_TENSOR_I16))
-        return H264SWDEC_PARAM_ERR;
-    if ((size_t)(uintptr_t)d_dst & (m.dtype == H264MI_TENSOR_F32 ? 3u : 1u)) return H264SWDEC_PARAM_ERR;
+    if (!residual_desc_fixed_ok(&m) || !export_aligned(d_dst, 0, export_elem_size(m.dtype))) return H264SWDEC_PARAM_ERR;
     const Sps *s = h264dec_active_sps(&c->dec);
     if (!s || !c->dec.last_out_slot1) return H264SWDEC_OK;      /* no picture delivered */
-    const int w = 16 * (int)s->w_mbs, h = 16 * (int)s->h_mbs;
     if (m.cw == 0 && m.ch == 0) {
-        m.x = s->crop ? 2 * (int)s->crop_l : 0;
-        m.y = s->crop ? 2 * (int)s->crop_t : 0;
-        m.cw = w - m.x - (s->crop ? 2 * (int)s->crop_r : 0);
-        m.ch = h - m.y - (s->crop ? 2 * (int)s->crop_b : 0);
+        const export_window w = sps_crop_window(s);
+        m.x = w.x; m.y = w.y; m.cw = w.cw; m.ch = w.ch;
     }
-    if (m.x < 0 || m.y < 0 || m.cw < 1 || m.ch < 1 || m.cw > w - m.x || m.ch > h - m.y ||
-        (m.planes == H264MI_RESID_UV && ((m.x | m.y | m.cw | m.ch) & 1)))
-        return H264SWDEC_PARAM_ERR;
+    if (!residual_window_ok(&m, s->w_mbs, s->h_mbs)) return H264SWDEC_PARAM_ERR;
     if (c->dec.be.export_residual(c->dec.be.ctx, c->dec.last_out_slot1 - 1, &m, d_dst, hip_stream))
         return H264SWDEC_PARAM_ERR;         /* (d_dst not on the decoder's GPU) */
     return H264SWDEC_PIC_RDY;

@@ -629,8 +629,7 @@ int h264mi_tensor_colour_resolve(int mode, int matrix, int full, int cw, int ch)
     return (bt709 ? H264MI_TENSOR_COLOUR_BT709 : H264MI_TENSOR_COLOUR_REFERENCE) + (full ? 1 : 0);
 }
 
-/* a tensor export (h264dec_next_output_tensor, resized: _tensor_resized);
- * failed: the backend refused it */
+/* a tensor export (h264dec_next_output_tensor); failed: the backend refused it */
 typedef struct TensorOut {
     const void *desc;
     void *d_dst, *hip_stream;
@@ -655,26 +654,13 @@ const uint8_t *h264dec_next_output_crop(H264Dec *d, uint32_t *pic_id, uint32_t *
     return next_output(d, pic_id, is_idr, err_mbs, NULL, dst, rgba, NULL);
 }
 
-/* (a resize descriptor starts with its h264mi_tensor_desc) */
-static int tensor_mode_ok(const void *desc)
-{
-    return h264mi_tensor_colour_resolve(((const h264mi_tensor_desc *)desc)->mode, 2, 0, 2, 2) >= 0;
-}
-
 const uint8_t *h264dec_next_output_tensor(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
-                                          const void *desc, void *d_dst, void *hip_stream, int *failed)
+                                          const void *desc, int resized, void *d_dst, void *hip_stream, int *failed)
 {
-    TensorOut t = {desc, d_dst, hip_stream, 0, 0};
-    const uint8_t *r = desc && d_dst && tensor_mode_ok(desc) ? next_output(d, pic_id, is_idr, err_mbs, NULL, NULL, 0, &t) : NULL;
-    if (failed) *failed = t.failed;
-    return r;
-}
-
-const uint8_t *h264dec_next_output_tensor_resized(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
-                                                  const void *desc, void *d_dst, void *hip_stream, int *failed)
-{
-    TensorOut t = {desc, d_dst, hip_stream, 0, 1};
-    const uint8_t *r = desc && d_dst && tensor_mode_ok(desc) ? next_output(d, pic_id, is_idr, err_mbs, NULL, NULL, 0, &t) : NULL;
+    TensorOut t = {desc, d_dst, hip_stream, 0, resized != 0};
+    /* (a resize descriptor starts with its h264mi_tensor_desc) */
+    const int mode_ok = desc && h264mi_tensor_colour_resolve(((const h264mi_tensor_desc *)desc)->mode, 2, 0, 2, 2) >= 0;
+    const uint8_t *r = d_dst && mode_ok ? next_output(d, pic_id, is_idr, err_mbs, NULL, NULL, 0, &t) : NULL;
     if (failed) *failed = t.failed;
     return r;
 }
@@ -718,10 +704,8 @@ static const uint8_t *next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr
         tensor->failed = rr < 0;
         if (rr >= 0) d->last_tensor_colour1 = colour + 1;
     } else if (crop) {
-        const int cl = sps->crop ? 2 * sps->crop_l : 0, ct = sps->crop ? 2 * sps->crop_t : 0;
-        const int cr = sps->crop ? 2 * sps->crop_r : 0, cb = sps->crop ? 2 * sps->crop_b : 0;
-        rr = d->be.read_crop(d->be.ctx, o->slot, cl, ct, 16 * sps->w_mbs - cl - cr, 16 * sps->h_mbs - ct - cb,
-                             crop_rgba, dst);
+        const export_window w = sps_crop_window(sps);
+        rr = d->be.read_crop(d->be.ctx, o->slot, w.x, w.y, w.cw, w.ch, crop_rgba, dst);
     } else {
         rr = rgba ? d->be.read_rgba(d->be.ctx, o->slot, dst) : d->be.read(d->be.ctx, o->slot, dst);
     }

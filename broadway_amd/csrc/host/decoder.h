@@ -10,6 +10,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include "../common/export_desc.h"
 #include "syntax.h"
 #include "dpb.h"
 #include "picbuild.h"
@@ -162,6 +163,12 @@ typedef struct H264Dec {
 
 double h264dec_now(void);
 
+/* the crop window of s in luma samples (the whole picture without cropping) */
+static inline export_window sps_crop_window(const Sps *s)
+{
+    return export_crop_window(s->w_mbs, s->h_mbs, s->crop, s->crop_l, s->crop_r, s->crop_t, s->crop_b);
+}
+
 int  h264dec_init(H264Dec *d, int no_output_reordering, H264Backend be);
 void h264dec_release(H264Dec *d);
 /* decode the next NAL unit found at buf[0..len); *read_bytes = consumed */
@@ -178,15 +185,12 @@ const uint8_t *h264dec_next_output_rgba(H264Dec *d, uint32_t *pic_id, uint32_t *
  * picture without one) into dst by the backend's read_crop (returns dst) */
 const uint8_t *h264dec_next_output_crop(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
                                         uint8_t *dst, int rgba);
-/* the same, the picture exported by the backend's export_tensor (returns
- * d_dst, a device pointer); *failed = 1 when the export of the picture taken
- * from the DPB failed */
+/* the same, the picture exported by the backend's export_tensor (desc: an
+ * h264mi_tensor_desc) or, with resized != 0, export_tensor_resized (an
+ * h264mi_tensor_resize_desc); returns d_dst, a device pointer; *failed = 1
+ * when the export of the picture taken from the DPB failed */
 const uint8_t *h264dec_next_output_tensor(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
-                                          const void *desc, void *d_dst, void *hip_stream, int *failed);
-/* the same through the backend's export_tensor_resized (desc: an
- * h264mi_tensor_resize_desc) */
-const uint8_t *h264dec_next_output_tensor_resized(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
-                                                  const void *desc, void *d_dst, void *hip_stream, int *failed);
+                                          const void *desc, int resized, void *d_dst, void *hip_stream, int *failed);
 int  h264dec_valid_param_sets(const H264Dec *d);
 /* conceal the current picture's missing MBs (conceal.c); returns their
  * number or -1 */

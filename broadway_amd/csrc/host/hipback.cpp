@@ -323,79 +323,34 @@ static bool wait_launched(SharedEng *sh, unsigned long long mine)
 }
 
 // Weak like the crop and tensor entry points below: a backend built against
-// the CPU stand-in of the engine leaves keep_records and export_mbinfo NULL.
+// the CPU stand-in of the engine leaves keep_records and keep_coefs NULL.
 extern "C" int h264mi_engine_keep_records(h264mi_engine *e, int on) __attribute__((weak));
 extern "C" int h264mi_engine_forget_records(h264mi_engine *e, int stream, int slot) __attribute__((weak));
-extern "C" int h264mi_engine_export_mbinfo(h264mi_engine *e, int n, const int *streams, const int *slots,
-                                           const h264mi_mbinfo_desc *desc, void *d_out, size_t out_stride,
-                                           void *hip_stream) __attribute__((weak));
+extern "C" int h264mi_engine_keep_coefs(h264mi_engine *e, int on) __attribute__((weak));
 
-// c->keep onto the instance's engine.  A shared engine's retention is only
-// ever switched on: its other instances may be using it.
-static int hb_keep_apply(HipBackendCtx *c)
+// The decoder's switch `on` (c->keep, c->keepc) onto the instance's engine
+// through h264mi_engine_keep_records / _keep_coefs.  A shared engine's
+// retention is only ever switched on: its other instances may be using it.
+static int hb_keep_apply(HipBackendCtx *c, int (*engine_keep)(h264mi_engine *, int), bool on)
 {
-    if (!c->sh) return h264mi_engine_keep_records(c->e, c->keep);
-    if (!c->keep) return 0;
+    if (!c->sh) return engine_keep(c->e, on);
+    if (!on) return 0;
     std::lock_guard<std::mutex> l(c->sh->mu);
-    return h264mi_engine_keep_records(c->e, 1);
+    return engine_keep(c->e, 1);
 }
 
 static int hb_keep_records(void *vctx, int on)
 {
     HipBackendCtx *c = (HipBackendCtx *)vctx;
     c->keep = on != 0;
-    return c->e ? hb_keep_apply(c) : 0;
-}
-
-// the kept records of slot as a field (desc: a checked h264mi_mbinfo_desc) at
-// d_dst; ordered like hb_export, nothing waits
-static int hb_export_mbinfo(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
-{
-    HipBackendCtx *c = (HipBackendCtx *)vctx;
-    if (!c->e || slot < 0 || slot >= c->nslots) return -1;
-    const int lane = c->lane;
-    std::unique_lock<std::mutex> l;
-    if (c->sh) l = std::unique_lock<std::mutex>(c->sh->mu);
-    if (h264mi_engine_export_mbinfo(c->e, 1, &lane, &slot, (const h264mi_mbinfo_desc *)desc, d_dst, 0, hip_stream))
-        return -1;
-    if (c->sh) HIPCHECK(hipEventRecord(c->ev_last, engine_stream(c->e)));
-    c->enq++;
-    return 0;
-}
-
-// The same pair for the coefficients and the residual export.
-extern "C" int h264mi_engine_keep_coefs(h264mi_engine *e, int on) __attribute__((weak));
-extern "C" int h264mi_engine_export_residual(h264mi_engine *e, int n, const int *streams, const int *slots,
-                                             const h264mi_residual_desc *desc, void *d_out, size_t out_stride,
-                                             void *hip_stream) __attribute__((weak));
-
-static int hb_keepc_apply(HipBackendCtx *c)
-{
-    if (!c->sh) return h264mi_engine_keep_coefs(c->e, c->keepc);
-    if (!c->keepc) return 0;
-    std::lock_guard<std::mutex> l(c->sh->mu);
-    return h264mi_engine_keep_coefs(c->e, 1);
+    return c->e ? hb_keep_apply(c, h264mi_engine_keep_records, c->keep) : 0;
 }
 
 static int hb_keep_coefs(void *vctx, int on)
 {
     HipBackendCtx *c = (HipBackendCtx *)vctx;
     c->keepc = on != 0;
-    return c->e ? hb_keepc_apply(c) : 0;
-}
-
-static int hb_export_residual(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
-{
-    HipBackendCtx *c = (HipBackendCtx *)vctx;
-    if (!c->e || slot < 0 || slot >= c->nslots) return -1;
-    const int lane = c->lane;
-    std::unique_lock<std::mutex> l;
-    if (c->sh) l = std::unique_lock<std::mutex>(c->sh->mu);
-    if (h264mi_engine_export_residual(c->e, 1, &lane, &slot, (const h264mi_residual_desc *)desc, d_dst, 0, hip_stream))
-        return -1;
-    if (c->sh) HIPCHECK(hipEventRecord(c->ev_last, engine_stream(c->e)));
-    c->enq++;
-    return 0;
+    return c->e ? hb_keep_apply(c, h264mi_engine_keep_coefs, c->keepc) : 0;
 }
 
 static int hb_configure(void *vctx, int w_mbs, int h_mbs, int nslots)
@@ -419,8 +374,8 @@ static int hb_configure(void *vctx, int w_mbs, int h_mbs, int nslots)
         c->lane = 0;
         c->e = engine_get(c->device, w_mbs, h_mbs, 1, nslots);
     }
-    if (c->e && c->keep && hb_keep_apply(c)) return -1;
-    if (c->e && c->keepc && hb_keepc_apply(c)) return -1;
+    if (c->e && c->keep && hb_keep_apply(c, h264mi_engine_keep_records, true)) return -1;
+    if (c->e && c->keepc && hb_keep_apply(c, h264mi_engine_keep_coefs, true)) return -1;
     return c->e && c->pref ? 0 : -1;
 }
 
@@ -603,43 +558,60 @@ static int hb_read_crop(void *vctx, int slot, int x, int y, int cw, int ch, int 
 }
 
 // Weak like the crop entry points: a backend built against the CPU stand-in of
-// the engine leaves export_tensor NULL (H264SwDecNextPictureTensor then fails).
+// the engine leaves the exports NULL (H264SwDecNextPictureTensor then fails).
 extern "C" int h264mi_engine_export_tensor(h264mi_engine *e, int n, const int *streams, const int *slots,
                                            const h264mi_tensor_desc *desc, void *d_out, size_t out_stride,
                                            void *hip_stream) __attribute__((weak));
-
 extern "C" int h264mi_engine_export_tensor_resized(h264mi_engine *e, int n, const int *streams, const int *slots,
                                                    const h264mi_tensor_resize_desc *desc, void *d_out,
                                                    size_t out_stride, void *hip_stream) __attribute__((weak));
+extern "C" int h264mi_engine_export_mbinfo(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                           const h264mi_mbinfo_desc *desc, void *d_out, size_t out_stride,
+                                           void *hip_stream) __attribute__((weak));
+extern "C" int h264mi_engine_export_residual(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                             const h264mi_residual_desc *desc, void *d_out, size_t out_stride,
+                                             void *hip_stream) __attribute__((weak));
 
-// nothing waits here: the decoder synced before (the slot's flags are on the
-// host), and the export orders itself on the engine's and the caller's stream;
-// resized: desc is an h264mi_tensor_resize_desc
-static int hb_export(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream, bool resized)
+// The four exports of slot (desc: a checked descriptor of the engine call's
+// kind) to d_dst.  Nothing waits here: the decoder synced before (the slot's
+// flags are on the host), and the export orders itself on the engine's and the
+// caller's stream.
+template <class Desc>
+static int hb_export(void *vctx, int slot,
+                     int (*engine_export)(h264mi_engine *, int, const int *, const int *, const Desc *, void *, size_t, void *),
+                     const void *desc, void *d_dst, void *hip_stream)
 {
     HipBackendCtx *c = (HipBackendCtx *)vctx;
-    if (slot < 0 || slot >= c->nslots) return -1;
+    if (!c->e || slot < 0 || slot >= c->nslots) return -1;
     const int lane = c->lane;
     std::unique_lock<std::mutex> l;
     if (c->sh) l = std::unique_lock<std::mutex>(c->sh->mu);
-    if (resized ? h264mi_engine_export_tensor_resized(c->e, 1, &lane, &slot, (const h264mi_tensor_resize_desc *)desc,
-                                                      d_dst, 0, hip_stream)
-                : h264mi_engine_export_tensor(c->e, 1, &lane, &slot, (const h264mi_tensor_desc *)desc, d_dst, 0,
-                                              hip_stream))
-        return -1;
+    if (engine_export(c->e, 1, &lane, &slot, (const Desc *)desc, d_dst, 0, hip_stream)) return -1;
     if (c->sh) HIPCHECK(hipEventRecord(c->ev_last, engine_stream(c->e)));
     c->enq++;
-    return slot_flagged(c, slot, false);
+    return 0;
 }
 
 static int hb_export_tensor(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
 {
-    return hb_export(vctx, slot, desc, d_dst, hip_stream, false);
+    if (hb_export(vctx, slot, h264mi_engine_export_tensor, desc, d_dst, hip_stream)) return -1;
+    return slot_flagged((HipBackendCtx *)vctx, slot, false);
 }
 
 static int hb_export_tensor_resized(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
 {
-    return hb_export(vctx, slot, desc, d_dst, hip_stream, true);
+    if (hb_export(vctx, slot, h264mi_engine_export_tensor_resized, desc, d_dst, hip_stream)) return -1;
+    return slot_flagged((HipBackendCtx *)vctx, slot, false);
+}
+
+static int hb_export_mbinfo(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
+{
+    return hb_export(vctx, slot, h264mi_engine_export_mbinfo, desc, d_dst, hip_stream);
+}
+
+static int hb_export_residual(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
+{
+    return hb_export(vctx, slot, h264mi_engine_export_residual, desc, d_dst, hip_stream);
 }
 
 // Pinned host blocks (decoder output frames) kept after free for the next

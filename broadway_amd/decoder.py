@@ -192,15 +192,11 @@ class Decoder:
             self.pic_decode_number += 1
             while True:
                 if self._tensor is not None:
-                    import torch
                     desc, planes, dtype = self._tensor
                     w, h = self._out_size()
-                    dev = torch.device("cuda", self._device)
-                    with torch.cuda.device(dev):
-                        out = torch.empty((planes, h, w), dtype=dtype, device=dev)
+                    out, st = self._device_empty((planes, h, w), dtype)
                     nxt = L.H264SwDecNextPictureTensorResized if self._resized else L.H264SwDecNextPictureTensor
-                    ret = nxt(self._inst, C.byref(self._pic), 0, C.byref(desc), out.data_ptr(),
-                              torch.cuda.current_stream(dev).cuda_stream)
+                    ret = nxt(self._inst, C.byref(self._pic), 0, C.byref(desc), out.data_ptr(), st)
                     if ret == _lib.H264SWDEC_PARAM_ERR:
                         raise RuntimeError("tensor: the backend cannot export device tensors "
                                            "(there is no host fallback)")
@@ -245,20 +241,29 @@ class Decoder:
             return i.cropParams.cropOutWidth, i.cropParams.cropOutHeight
         return i.picWidth, i.picHeight
 
+    def _device_empty(self, shape, dtype):
+        """(a new tensor on the decoder's GPU, torch's current stream there as a HIP handle)."""
+        import torch
+        dev = torch.device("cuda", self._device)
+        with torch.cuda.device(dev):
+            return torch.empty(shape, dtype=dtype, device=dev), torch.cuda.current_stream(dev).cuda_stream
+
+    def _crop_window(self):
+        """(x, y, cw, ch) of the active SPS's crop window (the whole picture without one)."""
+        i = self._info
+        if not i.croppingFlag:
+            return 0, 0, i.picWidth, i.picHeight
+        return (i.cropParams.cropLeftOffset, i.cropParams.cropTopOffset, i.cropParams.cropOutWidth,
+                i.cropParams.cropOutHeight)
+
     def _export_mbinfo(self):
         """The delivered picture's field over the blocks covering the crop
         window (the window H264SwDecLastPictureMbInfo takes for bw == 0)."""
-        import torch
         desc, nch, dtype = self._mbinfo
-        i = self._info
-        x, y, cw, ch = ((i.cropParams.cropLeftOffset, i.cropParams.cropTopOffset, i.cropParams.cropOutWidth,
-                         i.cropParams.cropOutHeight) if i.croppingFlag else (0, 0, i.picWidth, i.picHeight))
+        x, y, cw, ch = self._crop_window()
         bw, bh = ((x + cw + 3) >> 2) - (x >> 2), ((y + ch + 3) >> 2) - (y >> 2)
-        dev = torch.device("cuda", self._device)
-        with torch.cuda.device(dev):
-            out = torch.empty((nch, bh, bw), dtype=dtype, device=dev)
-        ret = self._L.H264SwDecLastPictureMbInfo(self._inst, C.byref(desc), out.data_ptr(),
-                                                 torch.cuda.current_stream(dev).cuda_stream)
+        out, st = self._device_empty((nch, bh, bw), dtype)
+        ret = self._L.H264SwDecLastPictureMbInfo(self._inst, C.byref(desc), out.data_ptr(), st)
         if ret != _lib.H264SWDEC_PIC_RDY:
             raise RuntimeError(f"mbinfo: the backend cannot export the MB records ({ret}; there is no host fallback)")
         return out
@@ -266,17 +271,11 @@ class Decoder:
     def _export_residual(self):
         """The delivered picture's residual over the crop window (the window
         H264SwDecLastPictureResidual takes for cw == ch == 0)."""
-        import torch
         desc, npl, dtype = self._residual
-        i = self._info
-        cw, ch = ((i.cropParams.cropOutWidth, i.cropParams.cropOutHeight) if i.croppingFlag
-                  else (i.picWidth, i.picHeight))
+        _, _, cw, ch = self._crop_window()
         hs = 1 if desc.planes == _lib.RESID_PLANES["uv"] else 0
-        dev = torch.device("cuda", self._device)
-        with torch.cuda.device(dev):
-            out = torch.empty((npl, ch >> hs, cw >> hs), dtype=dtype, device=dev)
-        ret = self._L.H264SwDecLastPictureResidual(self._inst, C.byref(desc), out.data_ptr(),
-                                                   torch.cuda.current_stream(dev).cuda_stream)
+        out, st = self._device_empty((npl, ch >> hs, cw >> hs), dtype)
+        ret = self._L.H264SwDecLastPictureResidual(self._inst, C.byref(desc), out.data_ptr(), st)
         if ret != _lib.H264SWDEC_PIC_RDY:
             raise RuntimeError(f"residual: the backend cannot export the residual ({ret}; there is no host fallback)")
         return out

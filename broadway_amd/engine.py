@@ -378,6 +378,31 @@ class Engine:
             raise RuntimeError("h264mi_engine_read_crop failed")
         return out
 
+    @staticmethod
+    def _pictures(streams: Sequence[int], slots: Sequence[int]):
+        """(n, streams, slots) of an export's pictures, the two as C int arrays."""
+        n = len(streams)
+        if n < 1 or len(slots) != n:
+            raise ValueError("streams and slots name the same, non-zero number of pictures")
+        return n, (C.c_int * n)(*streams), (C.c_int * n)(*slots)
+
+    def _out(self, shape, dtype, out, stream):
+        """(out, HIP stream handle) of an export: ``out``, checked, or a new
+        ``torch.empty``; ``stream`` or torch's current stream of the device."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = torch.empty(shape, dtype=dtype, device=dev)
+        elif tuple(out.shape) != shape or out.dtype != dtype or out.device != dev or not out.is_contiguous():
+            raise ValueError(f"out: a contiguous {dtype} tensor of shape {shape} on {dev} "
+                             f"(got {out.dtype} {tuple(out.shape)} on {out.device})")
+        cur = torch.cuda.current_stream(dev)
+        st = stream if stream is not None else cur
+        if st != cur:
+            out.record_stream(st)       # (the caching allocator: the block is in use on `stream` too)
+        return out, st.cuda_stream
+
     def to_tensor(self, streams: Sequence[int], slots: Sequence[int], window=None, mode: str = "rgb", dtype=None,
                   scale=None, bias=None, mean=None, std=None, out=None, stream=None, size=None, colour=None):
         """The slots (streams[k], slots[k]) as one ``(n, planes, ch, cw)``
@@ -406,30 +431,17 @@ class Engine:
         tensor of the result's shape, dtype and device to fill instead of a
         new ``torch.empty``.  The result is an ordinary torch tensor, so DLPack
         consumers (``torch.utils.dlpack`` / ``__dlpack__``) need nothing further."""
-        import torch
-        n = len(streams)
-        if n < 1 or len(slots) != n:
-            raise ValueError("streams and slots name the same, non-zero number of pictures")
+        n, c_streams, c_slots = self._pictures(streams, slots)
         if window is None:
             window = (0, 0, self.w_mbs * 16, self.h_mbs * 16)
         desc, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std, size, colour)
         shape = (n, planes, desc.ch, desc.cw) if size is None else (n, planes, desc.oh, desc.ow)
-        dev = torch.device("cuda", self.device)
-        if out is None:
-            if min(shape) < 1:
-                raise ValueError(f"window {tuple(window)}")
-            with torch.cuda.device(self.device):
-                out = torch.empty(shape, dtype=dtype, device=dev)
-        elif tuple(out.shape) != shape or out.dtype != dtype or out.device != dev or not out.is_contiguous():
-            raise ValueError(f"out: a contiguous {dtype} tensor of shape {shape} on {dev} "
-                             f"(got {out.dtype} {tuple(out.shape)} on {out.device})")
-        cur = torch.cuda.current_stream(dev)
-        st = stream if stream is not None else cur
-        if st != cur:
-            out.record_stream(st)       # (the caching allocator: the block is in use on `stream` too)
+        if out is None and min(shape) < 1:
+            raise ValueError(f"window {tuple(window)}")
+        out, st = self._out(shape, dtype, out, stream)
         export = self._L.h264mi_engine_export_tensor if size is None else self._L.h264mi_engine_export_tensor_resized
-        if export(self._h, n, (C.c_int * n)(*streams), (C.c_int * n)(*slots), C.byref(desc), out.data_ptr(),
-                  planes * shape[2] * shape[3] * out.element_size(), st.cuda_stream) != 0:
+        if export(self._h, n, c_streams, c_slots, C.byref(desc), out.data_ptr(),
+                  planes * shape[2] * shape[3] * out.element_size(), st) != 0:
             raise RuntimeError(f"{export.__name__} failed (stream, slot, window or size out of range?)")
         return out
 
@@ -456,28 +468,14 @@ class Engine:
         (``mbinfo_desc``; a slot nothing was decoded into reads as "no
         information").  Needs ``keep_records()`` before the decodes.  ``out``
         and ``stream`` as for ``to_tensor``; the host is never synchronised."""
-        import torch
-        n = len(streams)
-        if n < 1 or len(slots) != n:
-            raise ValueError("streams and slots name the same, non-zero number of pictures")
+        n, c_streams, c_slots = self._pictures(streams, slots)
         if window is None:
             window = (0, 0, self.w_mbs * 4, self.h_mbs * 4)
         desc, nch, dtype = mbinfo_desc(channels, window, dtype, scale, bias)
         shape = (n, nch, desc.bh, desc.bw)
-        dev = torch.device("cuda", self.device)
-        if out is None:
-            with torch.cuda.device(self.device):
-                out = torch.empty(shape, dtype=dtype, device=dev)
-        elif tuple(out.shape) != shape or out.dtype != dtype or out.device != dev or not out.is_contiguous():
-            raise ValueError(f"out: a contiguous {dtype} tensor of shape {shape} on {dev} "
-                             f"(got {out.dtype} {tuple(out.shape)} on {out.device})")
-        cur = torch.cuda.current_stream(dev)
-        st = stream if stream is not None else cur
-        if st != cur:
-            out.record_stream(st)       # (the caching allocator: the block is in use on `stream` too)
-        if self._L.h264mi_engine_export_mbinfo(self._h, n, (C.c_int * n)(*streams), (C.c_int * n)(*slots),
-                                               C.byref(desc), out.data_ptr(),
-                                               nch * desc.bh * desc.bw * out.element_size(), st.cuda_stream) != 0:
+        out, st = self._out(shape, dtype, out, stream)
+        if self._L.h264mi_engine_export_mbinfo(self._h, n, c_streams, c_slots, C.byref(desc), out.data_ptr(),
+                                               nch * desc.bh * desc.bw * out.element_size(), st) != 0:
             raise RuntimeError("h264mi_engine_export_mbinfo failed (keep_records off, or stream, slot or window "
                                "out of range?)")
         return out
@@ -502,29 +500,15 @@ class Engine:
         a slot nothing was decoded into reads as zeros).  Needs
         ``keep_coefs()`` before the decodes.  ``out`` and ``stream`` as for
         ``to_tensor``; the host is never synchronised."""
-        import torch
-        n = len(streams)
-        if n < 1 or len(slots) != n:
-            raise ValueError("streams and slots name the same, non-zero number of pictures")
+        n, c_streams, c_slots = self._pictures(streams, slots)
         if window is None:
             window = (0, 0, self.w_mbs * 16, self.h_mbs * 16)
         desc, npl, dtype = residual_desc(planes, window, dtype, scale, bias)
         hs = 1 if planes == "uv" else 0
         shape = (n, npl, desc.ch >> hs, desc.cw >> hs)
-        dev = torch.device("cuda", self.device)
-        if out is None:
-            with torch.cuda.device(self.device):
-                out = torch.empty(shape, dtype=dtype, device=dev)
-        elif tuple(out.shape) != shape or out.dtype != dtype or out.device != dev or not out.is_contiguous():
-            raise ValueError(f"out: a contiguous {dtype} tensor of shape {shape} on {dev} "
-                             f"(got {out.dtype} {tuple(out.shape)} on {out.device})")
-        cur = torch.cuda.current_stream(dev)
-        st = stream if stream is not None else cur
-        if st != cur:
-            out.record_stream(st)       # (the caching allocator: the block is in use on `stream` too)
-        if self._L.h264mi_engine_export_residual(self._h, n, (C.c_int * n)(*streams), (C.c_int * n)(*slots),
-                                                 C.byref(desc), out.data_ptr(),
-                                                 npl * shape[2] * shape[3] * out.element_size(), st.cuda_stream) != 0:
+        out, st = self._out(shape, dtype, out, stream)
+        if self._L.h264mi_engine_export_residual(self._h, n, c_streams, c_slots, C.byref(desc), out.data_ptr(),
+                                                 npl * shape[2] * shape[3] * out.element_size(), st) != 0:
             raise RuntimeError("h264mi_engine_export_residual failed (keep_coefs off, or stream, slot or window "
                                "out of range?)")
         return out
