@@ -101,6 +101,16 @@ class ResidualDesc(C.Structure):
                [("scale", C.c_float * 3), ("bias", C.c_float * 3)]
 
 
+class AccMvDesc(C.Structure):
+    """h264mi_accmv_desc (include/h264mi.h)."""
+    _fields_ = [(n, C.c_int) for n in ("x", "y", "cw", "ch", "nch", "dtype")] + \
+               [("id", C.c_int * 8), ("scale", C.c_float * 8), ("bias", C.c_float * 8)]
+
+
+# channel ids of AccMvDesc.id, by name
+ACCMV_CHANNELS = {"adx": 0, "ady": 1, "jx": 2, "jy": 3, "anchored": 4}
+ACCMV_MAX_CH = 8
+
 # ResidualDesc.planes, by name
 RESID_PLANES = {"y": 0, "uv": 1, "yuv": 2}
 
@@ -277,6 +287,20 @@ def mi() -> C.CDLL:
         L.H264SwDecKeepResidual.restype = i32
         L.H264SwDecLastPictureResidual.argtypes = [vp, rs, vp, vp]
         L.H264SwDecLastPictureResidual.restype = i32
+    if hasattr(L, "h264mi_accmv_device"):                   # (optional, as above)
+        ad = C.POINTER(AccMvDesc)
+        L.h264mi_accmv_step_device.argtypes = [vp, i32, i32, C.POINTER(vp), i32, i32, vp, vp]
+        L.h264mi_accmv_step_device.restype = i32
+        L.h264mi_accmv_device.argtypes = [vp, C.POINTER(sz), i32, i32, i32, ad, vp, sz, vp]
+        L.h264mi_accmv_device.restype = i32
+        L.h264mi_engine_keep_accmv.argtypes = [vp, i32]
+        L.h264mi_engine_keep_accmv.restype = i32
+        L.h264mi_engine_export_accmv.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), ad, vp, sz, vp]
+        L.h264mi_engine_export_accmv.restype = i32
+        L.H264SwDecKeepAccMotion.argtypes = [vp, u32]
+        L.H264SwDecKeepAccMotion.restype = i32
+        L.H264SwDecLastPictureAccMotion.argtypes = [vp, ad, vp, vp]
+        L.H264SwDecLastPictureAccMotion.restype = i32
     L.h264mi_engine_sync.argtypes = [vp]
     L.h264mi_engine_sync.restype = i32
     L.h264mi_engine_kernel.argtypes = [vp]

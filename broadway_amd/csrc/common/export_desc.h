@@ -94,6 +94,27 @@ static inline int residual_window_ok(const h264mi_residual_desc *d, int w_mbs, i
            d->ch <= 16 * h_mbs - d->y && (d->planes != H264MI_RESID_UV || !((d->x | d->y | d->cw | d->ch) & 1));
 }
 
+/* h264mi_accmv_desc: an origin map holds 15-bit coordinates, and the window is
+ * in luma samples of the MB-aligned picture (residual_window_ok's rules for Y) */
+static inline int accmv_size_ok(int w_mbs, int h_mbs)
+{
+    return w_mbs >= 1 && h_mbs >= 1 && w_mbs <= H264MI_ACCMV_MAX_DIM / 16 && h_mbs <= H264MI_ACCMV_MAX_DIM / 16;
+}
+
+static inline int accmv_desc_fixed_ok(const h264mi_accmv_desc *d)
+{
+    if (d->nch < 1 || d->nch > H264MI_ACCMV_MAX_CH || !export_dtype_field(d->dtype)) return 0;
+    for (int c = 0; c < d->nch; c++)
+        if (d->id[c] < 0 || d->id[c] >= H264MI_ACCMV_NCHANNELS) return 0;
+    return 1;
+}
+
+static inline int accmv_window_ok(const h264mi_accmv_desc *d, int w_mbs, int h_mbs)
+{
+    return accmv_size_ok(w_mbs, h_mbs) && d->x >= 0 && d->y >= 0 && d->cw >= 1 && d->ch >= 1 &&
+           d->cw <= 16 * w_mbs - d->x && d->ch <= 16 * h_mbs - d->y;
+}
+
 /* An SPS's crop window in luma samples (the whole picture without cropping;
  * the offsets are in the SPS's units of 2 samples) */
 typedef struct { int x, y, cw, ch; } export_window;

@@ -9,6 +9,7 @@
 #include "resize.hip"
 #include "mbinfo.hip"
 #include "residual.hip"
+#include "accmv.hip"
 #include "conceal.hip"
 #include <hip/hip_ext.h>
 
@@ -97,6 +98,9 @@ struct h264mi_engine {
     int keep_rec;             // the caller's own switch (d_keep is also held while d_keepc is)
     int16_t *d_keepc;         // h264mi_engine_keep_coefs: per (stream, slot) that reconstruction's coefficient blocks (NULL: off)
     uint8_t *keepc_ok;        // per (stream, slot): d_keepc holds the blocks d_keep's records index (host)
+    uint32_t *d_acc;          // h264mi_engine_keep_accmv: per (stream, slot) the origin map of the last reconstruction into it (NULL: off)
+    unsigned long long *acc_key;  // per stream: serial of its current key picture (host; 0: none yet)
+    unsigned long long *acc_ser;  // per (stream, slot): the key serial its map was written under (host; 0: no map)
     int steps;                // pictures per stream per launch (h264mi_engine_set_steps)
     unsigned long long *d_prog;   // per picture row of a launch, per row wave: {MBs stored, epoch} (frame-pipelined launches)
     unsigned *d_done;             // per picture row of a launch: epoch once the row is stored
@@ -301,6 +305,9 @@ extern "C" void h264mi_engine_destroy(h264mi_engine *e)
     (void)hipFree(e->d_keep);
     (void)hipFree(e->d_keepc);
     free(e->keepc_ok);
+    (void)hipFree(e->d_acc);
+    free(e->acc_key);
+    free(e->acc_ser);
     (void)hipFree(e->d_frames); (void)hipFree(e->d_prof); (void)hipFree(e->d_rec); (void)hipFree(e->d_coef);
     (void)hipFree(e->d_pics); (void)hipFree(e->d_gjunk);
     (void)hipHostFree(e->h_rec); (void)hipHostFree(e->h_coef); (void)hipHostFree(e->h_pics);
@@ -584,6 +591,50 @@ static int keep_batch(h264mi_engine *e, int npics, const int *stream, const int 
     return 0;
 }
 
+// origin-map retention (h264mi_engine_keep_accmv): one k_accmv_step launch per
+// ACCMV_STEP_PICS pictures of the uploaded batch, behind the launch that
+// reconstructs them and ahead of the next upload, reading d_rec in place.
+// Picture i's host records recs[i] say whether it is a key picture (no MBT_INTER
+// / MBT_SKIP record): that bumps its stream's key serial.  A slot's map counts
+// iff it was written under the stream's current serial; the slot being written
+// counts as none (a picture does not reference its own slot).
+static size_t acc_words(const h264mi_engine *e) { return (size_t)e->nmbs * 256; }
+static int accmv_clear(h264mi_engine *e, size_t first, size_t n);
+
+static int accmv_batch(h264mi_engine *e, int npics, const int *stream, const int *cur_slot, const void *const *recs)
+{
+    accmv_step_args a;
+    a.rec = (const uint8_t *)e->d_rec;
+    a.w_mbs = e->w; a.W = 16 * e->w; a.H = 16 * e->h; a.nslots = e->nslots;
+    for (int k0 = 0; k0 < npics; k0 += ACCMV_STEP_PICS) {
+        const int n = npics - k0 < ACCMV_STEP_PICS ? npics - k0 : ACCMV_STEP_PICS;
+        memset(a.ref, 0, sizeof(a.ref));
+        for (int k = 0; k < ACCMV_STEP_PICS; k++) {
+            const int i = k0 + (k < n ? k : 0);
+            const size_t b = (size_t)stream[i] * e->nslots;
+            a.rec_off[k] = (unsigned long long)i * e->nmbs * sizeof(MbRec);
+            a.out[k] = e->d_acc + (b + cur_slot[i]) * acc_words(e);
+            a.mode[k] = ACCMV_STEP;
+            if (k >= n) continue;
+            const MbRec *r = (const MbRec *)recs[i];
+            bool key = true;
+            for (int m = 0; m < e->nmbs && key; m++) key = r[m].type > MBT_SKIP;
+            if (key) {
+                e->acc_key[stream[i]]++;
+                a.mode[k] = ACCMV_KEY;
+            } else {
+                for (int s = 0; s < e->nslots; s++)
+                    if (s != cur_slot[i] && e->acc_key[stream[i]] && e->acc_ser[b + s] == e->acc_key[stream[i]])
+                        a.ref[k][s] = e->d_acc + (b + s) * acc_words(e);
+            }
+            e->acc_ser[b + cur_slot[i]] = e->acc_key[stream[i]];
+        }
+        accmv_step_launch(n, e->st, a);
+        HIPCHECK(hipGetLastError());
+    }
+    return 0;
+}
+
 // coefficient retention (h264mi_engine_keep_coefs): a kept batch holds the
 // worst case of every MB -- 16 luma, 8 chroma AC, 1 luma DC and 2 chroma DC
 // blocks (I_PCM's 12 fit)
@@ -662,6 +713,7 @@ int engine_decode_host(h264mi_engine *e, int npics, const int *stream, const int
     for (int i = 0; i < npics && !heavy && intra_heavy < 0; i++) heavy = (e->h_pics[i].flags & PD_INTRA_HEAVY) != 0;
     e->launch_intra = heavy;
     if (launch_batch(e, npics, 1, e->d_rec, e->d_coef, e->d_pics, NULL, NULL, NULL)) return -1;
+    if (e->d_acc && accmv_batch(e, npics, stream, cur_slot, recs)) return -1;
     if (e->d_keep && keep_batch(e, npics, stream, cur_slot)) return -1;
     return e->d_keepc ? keep_coef_batch(e, npics, stream, cur_slot, ncoef) : 0;
 }
@@ -699,6 +751,7 @@ int engine_decode_direct(h264mi_engine *e, int stream, int cur_slot, const void 
     HIPCHECK(hipEventRecord(e->ev_staged, e->st));
     e->launch_intra = intra_heavy >= 0 ? intra_heavy : (pd.flags & PD_INTRA_HEAVY) != 0;
     if (launch_batch(e, 1, 1, e->d_rec, e->d_coef, e->d_pics, NULL, NULL, NULL)) return -1;
+    if (e->d_acc && accmv_batch(e, 1, &stream, &cur_slot, &rec)) return -1;
     if (e->d_keep && keep_batch(e, 1, &stream, &cur_slot)) return -1;
     return e->d_keepc ? keep_coef_batch(e, 1, &stream, &cur_slot, &ncoef) : 0;
 }
@@ -1387,10 +1440,17 @@ extern "C" int h264mi_engine_keep_coefs(h264mi_engine *e, int on)
 
 extern "C" int h264mi_engine_forget_records(h264mi_engine *e, int stream, int slot)
 {
-    if (!e || !e->d_keep || stream < 0 || stream >= e->nstreams || slot < 0 || slot >= e->nslots) return -1;
+    if (!e || (!e->d_keep && !e->d_acc) || stream < 0 || stream >= e->nstreams || slot < 0 || slot >= e->nslots)
+        return -1;
     HIPCHECK(hipSetDevice(e->dev));
     if (e->keepc_ok) e->keepc_ok[(size_t)stream * e->nslots + slot] = 0;
-    HIPCHECK(hipMemsetAsync(e->d_keep + ((size_t)stream * e->nslots + slot) * e->nmbs, 0xFF, sizeof(MbRec) * e->nmbs, e->st));
+    if (e->d_keep)
+        HIPCHECK(hipMemsetAsync(e->d_keep + ((size_t)stream * e->nslots + slot) * e->nmbs, 0xFF, sizeof(MbRec) * e->nmbs, e->st));
+    if (e->d_acc) {
+        // the slot's map says nothing about its picture: none as a reference, (x, y, 0) when exported
+        e->acc_ser[(size_t)stream * e->nslots + slot] = 0;
+        return accmv_clear(e, (size_t)stream * e->nslots + slot, 1);
+    }
     return 0;
 }
 
@@ -1465,6 +1525,133 @@ extern "C" int h264mi_engine_export_residual(h264mi_engine *e, int n, const int 
         }
         return h264mi_residual_device(e->d_keep, off.data(), e->d_keepc, cbase.data(), nb * keepc_cap(e), n, e->w, e->h,
                                       desc, d_out, out_stride, e->st);
+    });
+}
+
+// an export descriptor h264mi_accmv_device accepts on a w_mbs x h_mbs picture
+static bool accmv_desc_ok(const h264mi_accmv_desc *d, int w_mbs, int h_mbs)
+{
+    return d && accmv_desc_fixed_ok(d) && accmv_window_ok(d, w_mbs, h_mbs);
+}
+
+// One step of the accumulated motion (accmv.hip k_accmv_step): the origin map
+// of the picture whose records start at d_recs, from the maps d_ref_maps[s] of
+// the slots it references (NULL: none) or, with key != 0, the identity.  Device
+// pointers, asynchronous on `stream`.  -1 (nothing launched) on a bad argument.
+extern "C" int h264mi_accmv_step_device(const void *d_recs, int w_mbs, int h_mbs, const void *const *d_ref_maps,
+                                        int nslots, int key, void *d_map_out, void *stream)
+{
+    static_assert(H264MI_ACCMV_MAX_SLOTS == ACCMV_MAX_SLOTS && H264MI_ACCMV_MAX_CH == ACCMV_MAX_CH &&
+                      H264MI_ACCMV_NCHANNELS == ACC_NCHANNELS && H264MI_ACCMV_ADX == ACC_ADX &&
+                      H264MI_ACCMV_ADY == ACC_ADY && H264MI_ACCMV_JX == ACC_JX && H264MI_ACCMV_JY == ACC_JY &&
+                      H264MI_ACCMV_ANCHORED == ACC_ANCHORED && ACCMV_MAX_PICS == EXPORT_MAX_PICS,
+                  "include/h264mi.h and accmv.hip name the same channels and bounds");
+    if (!d_recs || !d_map_out || !accmv_size_ok(w_mbs, h_mbs) || nslots < 0 || nslots > ACCMV_MAX_SLOTS ||
+        (nslots && !d_ref_maps) || (((size_t)(uintptr_t)d_recs | (size_t)(uintptr_t)d_map_out) & 15))
+        return -1;
+    for (int s = 0; s < nslots; s++)
+        if (d_ref_maps[s] == d_map_out || ((size_t)(uintptr_t)d_ref_maps[s] & 3)) return -1;
+    accmv_step_args a;
+    memset(&a, 0, sizeof(a));
+    a.rec = (const uint8_t *)d_recs;
+    a.w_mbs = w_mbs; a.W = 16 * w_mbs; a.H = 16 * h_mbs; a.nslots = nslots;
+    a.out[0] = (uint32_t *)d_map_out;
+    for (int s = 0; s < nslots; s++) a.ref[0][s] = (const uint32_t *)d_ref_maps[s];
+    a.mode[0] = key ? ACCMV_KEY : ACCMV_STEP;
+    accmv_step_launch(1, (hipStream_t)stream, a);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// Origin maps as planar channels (accmv.hip k_accmv): the window desc->(x, y,
+// cw, ch) of the npics maps (16 * w_mbs words a row) that start map_offsets[k]
+// bytes after d_maps, as contiguous (nch, ch, cw) elements of desc->dtype at
+// d_out + k * out_stride; device pointers, asynchronous on `stream`;
+// ACCMV_MAX_PICS pictures per launch.  -1 (nothing launched) on a bad argument.
+extern "C" int h264mi_accmv_device(const void *d_maps, const size_t *map_offsets, int npics, int w_mbs, int h_mbs,
+                                   const h264mi_accmv_desc *desc, void *d_out, size_t out_stride, void *stream)
+{
+    if (!d_maps || !map_offsets || !d_out || npics < 1 || ((size_t)(uintptr_t)d_maps & 3) ||
+        !accmv_desc_ok(desc, w_mbs, h_mbs))
+        return -1;
+    for (int k = 0; k < npics; k++)
+        if (map_offsets[k] & 3) return -1;
+    const size_t es = export_elem_size(desc->dtype);
+    if (!export_aligned(d_out, out_stride, es)) return -1;
+    const bool v16 = export_v16(d_out, out_stride, (size_t)desc->cw * es);
+    accmv_args a;
+    a.maps = (const uint8_t *)d_maps;
+    a.W = 16 * w_mbs;
+    a.x = desc->x; a.y = desc->y; a.cw = desc->cw; a.ch = desc->ch; a.nch = desc->nch;
+    a.out_stride = out_stride;
+    for (int c = 0; c < ACCMV_MAX_CH; c++) {
+        a.id[c] = c < desc->nch ? (uint8_t)desc->id[c] : 0;
+        a.scale[c] = c < desc->nch ? desc->scale[c] : 0.0f;
+        a.bias[c] = c < desc->nch ? desc->bias[c] : 0.0f;
+    }
+    return export_launches(npics, map_offsets, a.off, &a.out, d_out, out_stride,
+                           [&](int, int n) { accmv_launch(desc->dtype, v16, n, (hipStream_t)stream, a); });
+}
+
+// the maps of slots [first, first + n) of the engine's pool as (x, y, 0), on its stream
+static int accmv_clear(h264mi_engine *e, size_t first, size_t n)
+{
+    accmv_step_args a;
+    memset(&a, 0, sizeof(a));
+    a.w_mbs = e->w; a.W = 16 * e->w; a.H = 16 * e->h;
+    for (size_t k0 = 0; k0 < n; k0 += ACCMV_STEP_PICS) {
+        const int m = n - k0 < ACCMV_STEP_PICS ? (int)(n - k0) : ACCMV_STEP_PICS;
+        for (int k = 0; k < ACCMV_STEP_PICS; k++) {
+            a.out[k] = e->d_acc + (first + k0 + (k < m ? k : 0)) * acc_words(e);
+            a.mode[k] = ACCMV_CLEAR;
+        }
+        accmv_step_launch(m, e->st, a);
+        HIPCHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+// Origin-map retention: one map per (stream, slot), (x, y, 0) until a
+// reconstruction into the slot steps into it (accmv_batch); every serial starts
+// at 0, so switching on starts from nothing.  Off waits for the engine's stream
+// (exports run on it) and frees.
+extern "C" int h264mi_engine_keep_accmv(h264mi_engine *e, int on)
+{
+    if (!e) return -1;
+    if ((on != 0) == (e->d_acc != NULL)) return 0;
+    HIPCHECK(hipSetDevice(e->dev));
+    if (on) {
+        if (!accmv_size_ok(e->w, e->h) || e->nslots > ACCMV_MAX_SLOTS) return -1;
+        const size_t nb = (size_t)e->nslots * e->nstreams;
+        e->acc_key = (unsigned long long *)calloc((size_t)e->nstreams, sizeof(unsigned long long));
+        e->acc_ser = (unsigned long long *)calloc(nb, sizeof(unsigned long long));
+        if (!e->acc_key || !e->acc_ser || hipMalloc(&e->d_acc, nb * acc_words(e) * 4) != hipSuccess ||
+            accmv_clear(e, 0, nb)) {
+            (void)hipStreamSynchronize(e->st);
+            (void)hipFree(e->d_acc);
+            free(e->acc_key); free(e->acc_ser);
+            e->d_acc = NULL; e->acc_key = e->acc_ser = NULL;
+            return -1;
+        }
+        return 0;
+    }
+    HIPCHECK(hipStreamSynchronize(e->st));
+    (void)hipFree(e->d_acc);
+    free(e->acc_key); free(e->acc_ser);
+    e->d_acc = NULL; e->acc_key = e->acc_ser = NULL;
+    return 0;
+}
+
+// The kept maps of the slots (streams[k], slots[k]) as tensors in the caller's
+// memory, ordered between the caller's stream and ours by export_ordered
+extern "C" int h264mi_engine_export_accmv(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                          const h264mi_accmv_desc *desc, void *d_out, size_t out_stride, void *stream)
+{
+    if (!e || !e->d_acc || n < 1 || !streams || !slots || !d_out || !accmv_desc_ok(desc, e->w, e->h)) return -1;
+    return export_ordered(e, n, streams, slots, d_out, out_stride, export_elem_size(desc->dtype), stream, [&] {
+        std::vector<size_t> off((size_t)n);
+        for (int k = 0; k < n; k++) off[k] = acc_words(e) * 4 * ((size_t)streams[k] * e->nslots + slots[k]);
+        return h264mi_accmv_device(e->d_acc, off.data(), n, e->w, e->h, desc, d_out, out_stride, e->st);
     });
 }
 
@@ -1595,7 +1782,8 @@ int engine_reuse(h264mi_engine *e)
     e->err_bits = 0;          // the previous owner's device / checker flags
     e->steps = 1;
     e->last_kernel = NULL;
-    if (h264mi_engine_keep_coefs(e, 0) || h264mi_engine_keep_records(e, 0)) return -1;      // the previous owner's retention
+    if (h264mi_engine_keep_coefs(e, 0) || h264mi_engine_keep_records(e, 0) || h264mi_engine_keep_accmv(e, 0))
+        return -1;                                                                          // the previous owner's retention
     // the epoch keeps counting: the mailboxes hold tags of earlier launches only
     HIPCHECK(hipMemsetAsync(e->d_frames, 0, e->frame_bytes * e->nslots * e->nstreams, e->st));
     return 0;

@@ -395,6 +395,41 @@ H264SwDecRet H264SwDecLastPictureResidual(H264SwDecInst decInst, const h264mi_re
     return H264SWDEC_PIC_RDY;
 }
 
+/* Origin-map retention for H264SwDecLastPictureAccMotion (include/h264mi.h) */
+H264SwDecRet H264SwDecKeepAccMotion(H264SwDecInst decInst, u32 on)
+{
+    if (decInst == NULL) return H264SWDEC_PARAM_ERR;
+    DecContainer *c = (DecContainer *)decInst;
+    if (!c->dec.be.keep_accmv || !c->dec.be.export_accmv) return H264SWDEC_PARAM_ERR;
+    if (c->dec.be.keep_accmv(c->dec.be.ctx, on != 0)) return H264SWDEC_PARAM_ERR;
+    c->dec.keep_accmv = on != 0;
+    return H264SWDEC_OK;
+}
+
+/* The accumulated motion of the picture the last H264SwDecNextPicture* call
+ * delivered (include/h264mi.h); desc->cw == desc->ch == 0: the active SPS's
+ * crop window.  The DPB is not touched.  Everything the export can refuse is
+ * checked before anything is queued. */
+H264SwDecRet H264SwDecLastPictureAccMotion(H264SwDecInst decInst, const h264mi_accmv_desc *desc, void *d_dst,
+                                           void *hip_stream)
+{
+    if (decInst == NULL || desc == NULL || d_dst == NULL) return H264SWDEC_PARAM_ERR;
+    DecContainer *c = (DecContainer *)decInst;
+    if (!c->dec.be.export_accmv || !c->dec.keep_accmv) return H264SWDEC_PARAM_ERR;
+    h264mi_accmv_desc m = *desc;
+    if (!accmv_desc_fixed_ok(&m) || !export_aligned(d_dst, 0, export_elem_size(m.dtype))) return H264SWDEC_PARAM_ERR;
+    const Sps *s = h264dec_active_sps(&c->dec);
+    if (!s || !c->dec.last_out_slot1) return H264SWDEC_OK;      /* no picture delivered */
+    if (m.cw == 0 && m.ch == 0) {
+        const export_window w = sps_crop_window(s);
+        m.x = w.x; m.y = w.y; m.cw = w.cw; m.ch = w.ch;
+    }
+    if (!accmv_window_ok(&m, s->w_mbs, s->h_mbs)) return H264SWDEC_PARAM_ERR;
+    if (c->dec.be.export_accmv(c->dec.be.ctx, c->dec.last_out_slot1 - 1, &m, d_dst, hip_stream))
+        return H264SWDEC_PARAM_ERR;         /* (d_dst not on the decoder's GPU) */
+    return H264SWDEC_PIC_RDY;
+}
+
 H264SwDecRet H264SwDecGetTiming(H264SwDecInst decInst, double *parse_s, double *submit_s, double *wait_s,
                                 double *copy_s, u32 *pictures)
 {

@@ -66,6 +66,10 @@ typedef struct H264Backend {
      * checked h264mi_residual_desc) */
     int  (*keep_coefs)(void *ctx, int on);
     int  (*export_residual)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
+    /* optional: the same for each picture's origin map (accumulated motion),
+     * and slot's kept map as the tensor of desc (a checked h264mi_accmv_desc) */
+    int  (*keep_accmv)(void *ctx, int on);
+    int  (*export_accmv)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
     /* optional: host memory for the output frames (pinned by the HIP
      * backend, so each picture's D2H copy runs at DMA speed); NULL: malloc */
     void *(*host_alloc)(void *ctx, size_t bytes);
@@ -147,6 +151,7 @@ typedef struct H264Dec {
      * since the last H264SwDecDecode) */
     int      keep_mbinfo;
     int      keep_residual;     /* the same for the coefficients (H264SwDecKeepResidual) */
+    int      keep_accmv;        /* the same for the origin maps (H264SwDecKeepAccMotion) */
     int      last_out_slot1;
     /* the colour id of the last tensor delivered (include/h264mi.h), plus one (0: none yet) */
     int      last_tensor_colour1;

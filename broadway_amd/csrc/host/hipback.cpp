@@ -195,6 +195,7 @@ struct HipBackendCtx {
     unsigned enq, synced;   // work items queued on the engine's stream / of those, waited for by hb_sync
     bool keep;              // keep_records: asked for by the decoder, applied to every engine configured from then on
     bool keepc;             // keep_coefs: the same
+    bool keepa;             // keep_accmv: the same
 };
 
 extern "C" int h264mi_set_share(int lanes)
@@ -327,6 +328,7 @@ static bool wait_launched(SharedEng *sh, unsigned long long mine)
 extern "C" int h264mi_engine_keep_records(h264mi_engine *e, int on) __attribute__((weak));
 extern "C" int h264mi_engine_forget_records(h264mi_engine *e, int stream, int slot) __attribute__((weak));
 extern "C" int h264mi_engine_keep_coefs(h264mi_engine *e, int on) __attribute__((weak));
+extern "C" int h264mi_engine_keep_accmv(h264mi_engine *e, int on) __attribute__((weak));
 
 // The decoder's switch `on` (c->keep, c->keepc) onto the instance's engine
 // through h264mi_engine_keep_records / _keep_coefs.  A shared engine's
@@ -353,6 +355,13 @@ static int hb_keep_coefs(void *vctx, int on)
     return c->e ? hb_keep_apply(c, h264mi_engine_keep_coefs, c->keepc) : 0;
 }
 
+static int hb_keep_accmv(void *vctx, int on)
+{
+    HipBackendCtx *c = (HipBackendCtx *)vctx;
+    c->keepa = on != 0;
+    return c->e ? hb_keep_apply(c, h264mi_engine_keep_accmv, c->keepa) : 0;
+}
+
 static int hb_configure(void *vctx, int w_mbs, int h_mbs, int nslots)
 {
     HipBackendCtx *c = (HipBackendCtx *)vctx;
@@ -376,6 +385,7 @@ static int hb_configure(void *vctx, int w_mbs, int h_mbs, int nslots)
     }
     if (c->e && c->keep && hb_keep_apply(c, h264mi_engine_keep_records, true)) return -1;
     if (c->e && c->keepc && hb_keep_apply(c, h264mi_engine_keep_coefs, true)) return -1;
+    if (c->e && c->keepa && hb_keep_apply(c, h264mi_engine_keep_accmv, true)) return -1;
     return c->e && c->pref ? 0 : -1;
 }
 
@@ -571,8 +581,11 @@ extern "C" int h264mi_engine_export_mbinfo(h264mi_engine *e, int n, const int *s
 extern "C" int h264mi_engine_export_residual(h264mi_engine *e, int n, const int *streams, const int *slots,
                                              const h264mi_residual_desc *desc, void *d_out, size_t out_stride,
                                              void *hip_stream) __attribute__((weak));
+extern "C" int h264mi_engine_export_accmv(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                          const h264mi_accmv_desc *desc, void *d_out, size_t out_stride,
+                                          void *hip_stream) __attribute__((weak));
 
-// The four exports of slot (desc: a checked descriptor of the engine call's
+// The five exports of slot (desc: a checked descriptor of the engine call's
 // kind) to d_dst.  Nothing waits here: the decoder synced before (the slot's
 // flags are on the host), and the export orders itself on the engine's and the
 // caller's stream.
@@ -612,6 +625,11 @@ static int hb_export_mbinfo(void *vctx, int slot, const void *desc, void *d_dst,
 static int hb_export_residual(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
 {
     return hb_export(vctx, slot, h264mi_engine_export_residual, desc, d_dst, hip_stream);
+}
+
+static int hb_export_accmv(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
+{
+    return hb_export(vctx, slot, h264mi_engine_export_accmv, desc, d_dst, hip_stream);
 }
 
 // Pinned host blocks (decoder output frames) kept after free for the next
@@ -689,11 +707,11 @@ static int hb_copy(void *vctx, int dst, int src)
         HIPCHECK(hipMemcpyAsync(h264mi_engine_frame_ptr(c->e, c->lane, dst), h264mi_engine_frame_ptr(c->e, c->lane, src),
                                 engine_slot_bytes(c->e), hipMemcpyDeviceToDevice, engine_stream(c->e)));
         // the copy is no reconstruction: dst's kept records say nothing about it
-        if ((c->keep || c->keepc) && h264mi_engine_forget_records && h264mi_engine_forget_records(c->e, c->lane, dst)) return -1;
+        if ((c->keep || c->keepc || c->keepa) && h264mi_engine_forget_records && h264mi_engine_forget_records(c->e, c->lane, dst)) return -1;
         HIPCHECK(hipEventRecord(c->ev_last, engine_stream(c->e)));
         return 0;
     }
-    if ((c->keep || c->keepc) && h264mi_engine_forget_records && h264mi_engine_forget_records(c->e, 0, dst)) return -1;
+    if ((c->keep || c->keepc || c->keepa) && h264mi_engine_forget_records && h264mi_engine_forget_records(c->e, 0, dst)) return -1;
     if (h264mi_engine_sync(c->e)) return -1;
     HIPCHECK(hipMemcpy(h264mi_engine_frame_ptr(c->e, 0, dst), h264mi_engine_frame_ptr(c->e, 0, src),
                        engine_slot_bytes(c->e), hipMemcpyDeviceToDevice));
@@ -755,6 +773,9 @@ extern "C" H264Backend h264mi_hip_backend_create(int device)
     const bool resid = mbinfo && h264mi_engine_keep_coefs && h264mi_engine_export_residual;
     be.keep_coefs = resid ? hb_keep_coefs : NULL;
     be.export_residual = resid ? hb_export_residual : NULL;
+    const bool accmv = h264mi_engine_keep_accmv && h264mi_engine_export_accmv && h264mi_engine_forget_records;
+    be.keep_accmv = accmv ? hb_keep_accmv : NULL;
+    be.export_accmv = accmv ? hb_export_accmv : NULL;
     be.host_alloc = hb_host_alloc;
     be.host_free = hb_host_free;
     be.records_wait = hb_records_wait;

@@ -68,6 +68,17 @@ of the wasm glue of Decoder/src/Decoder.c:44-162:
   torch's current stream; the arguments of ``Engine.to_residual`` (default:
   planes "y", int16).
 
+* ``accmv: true`` or ``accmv: {"channels": ..., "dtype": ..., "scale": ...,
+  "bias": ...}`` (an extension for device consumers; needs torch; combines
+  with every output mode above and with ``mbinfo`` and ``residual``): the
+  decoder keeps each picture's origin map on the GPU -- every luma sample
+  traced back, through the pictures it was predicted from, to its position in
+  the key picture of its GOP --, and before every ``onPictureDecoded`` call
+  ``decoder.accmv`` is a new ``(C, ch, cw)`` torch tensor on the decoder's GPU
+  -- the delivered picture's accumulated motion over the SPS crop window,
+  built by ``H264SwDecLastPictureAccMotion`` on torch's current stream; the
+  arguments of ``Engine.to_accmv`` (default: channels ("adx", "ady"), int16).
+
 Unlike the reference module (a single global instance) every ``Decoder`` has
 its own H264SwDec instance, so several streams can be decoded side by side.
 Reconstruction always runs on the GPU through libh264mi.so; ``sliceMode``
@@ -131,6 +142,16 @@ class Decoder:
             from .engine import residual_desc        # (imports torch)
             self._residual = residual_desc(opts.pop("planes", "y"), None, **opts)
             self._device = int(os.environ.get("H264MI_DEVICE") or 0)
+        self._accmv = self.options.get("accmv") or None
+        self.accmv = None
+        if self._accmv is not None:
+            opts = {} if self._accmv is True else dict(self._accmv)
+            unknown = set(opts) - {"channels", "dtype", "scale", "bias"}
+            if unknown:
+                raise ValueError(f"accmv: unknown keys {sorted(unknown)}")
+            from .engine import accmv_desc           # (imports torch)
+            self._accmv = accmv_desc(opts.pop("channels", ("adx", "ady")), None, **opts)
+            self._device = int(os.environ.get("H264MI_DEVICE") or 0)
         self._L = _lib.mi()
         inst = C.c_void_p()
         ret = self._L.H264SwDecInit(C.byref(inst), 0)
@@ -145,6 +166,10 @@ class Decoder:
                                            self._L.H264SwDecKeepResidual(inst, 1) != _lib.H264SWDEC_OK):
             self.close()
             raise RuntimeError("residual: the backend cannot keep coefficients (there is no host fallback)")
+        if self._accmv is not None and (not hasattr(self._L, "H264SwDecKeepAccMotion") or
+                                        self._L.H264SwDecKeepAccMotion(inst, 1) != _lib.H264SWDEC_OK):
+            self.close()
+            raise RuntimeError("accmv: the backend cannot keep origin maps (there is no host fallback)")
         self._buf = (C.c_uint8 * STREAM_BUFFER_SIZE)()
         self._info = _lib.H264SwDecInfo()
         self._pic = _lib.H264SwDecPicture()
@@ -280,7 +305,20 @@ class Decoder:
             raise RuntimeError(f"residual: the backend cannot export the residual ({ret}; there is no host fallback)")
         return out
 
+    def _export_accmv(self):
+        """The delivered picture's accumulated motion over the crop window (the
+        window H264SwDecLastPictureAccMotion takes for cw == ch == 0)."""
+        desc, nch, dtype = self._accmv
+        _, _, cw, ch = self._crop_window()
+        out, st = self._device_empty((nch, ch, cw), dtype)
+        ret = self._L.H264SwDecLastPictureAccMotion(self._inst, C.byref(desc), out.data_ptr(), st)
+        if ret != _lib.H264SWDEC_PIC_RDY:
+            raise RuntimeError(f"accmv: the backend cannot export the origin map ({ret}; there is no host fallback)")
+        return out
+
     def _emit(self, pic, rgba=None) -> None:
+        if self._accmv is not None:
+            self.accmv = self._export_accmv()
         if self._residual is not None:
             self.residual = self._export_residual()
         if self._mbinfo is not None:

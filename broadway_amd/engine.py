@@ -209,6 +209,54 @@ def residual_desc(planes="y", window=None, dtype=None, scale=None, bias=None):
     return d, np_, dtype
 
 
+def accmv_desc(channels=("adx", "ady"), window=None, dtype=None, scale=None, bias=None):
+    """(``_lib.AccMvDesc``, number of channels, torch dtype) of an export of
+    the accumulated motion (Engine.to_accmv, Decoder's ``accmv`` option;
+    include/h264mi.h defines the field): ``channels`` names the planes, in
+    order, repeats allowed (1..8 of "adx", "ady", "jx", "jy", "anchored");
+    window = (x, y, cw, ch) in luma samples of the MB-aligned picture, or None
+    for the decoder's SPS crop window (cw = ch = 0 in the descriptor).
+    ``dtype``: torch.int16 (the default; the integer itself) or float16 /
+    bfloat16 / float32, ``fma(v, scale[c], bias[c])`` of channel position c;
+    scale and bias are scalars or one value per channel, default 1 and 0."""
+    import torch
+    if isinstance(channels, str):
+        channels = (channels,)
+    channels = tuple(channels)
+    if not 1 <= len(channels) <= _lib.ACCMV_MAX_CH:
+        raise ValueError(f"channels: 1..{_lib.ACCMV_MAX_CH} names")
+    bad = [c for c in channels if c not in _lib.ACCMV_CHANNELS]
+    if bad:
+        raise ValueError(f"channels {bad}: each one of {sorted(_lib.ACCMV_CHANNELS)}")
+    dtype = torch.int16 if dtype is None else dtype
+    dts = {torch.int16: _lib.TENSOR_I16, torch.float16: _lib.TENSOR_F16, torch.bfloat16: _lib.TENSOR_BF16,
+           torch.float32: _lib.TENSOR_F32}
+    if dtype not in dts:
+        raise ValueError(f"dtype {dtype}: one of torch.int16, float16, bfloat16, float32")
+
+    def per_channel(v, default, what):
+        if v is None:
+            return (default,) * len(channels)
+        v = tuple(float(f) for f in v) if hasattr(v, "__len__") else (float(v),) * len(channels)
+        if len(v) != len(channels):
+            raise ValueError(f"{what}: a scalar or one value per channel")
+        return v
+
+    d = _lib.AccMvDesc()
+    if window is not None:
+        try:
+            d.x, d.y, d.cw, d.ch = (int(v) for v in window)
+        except (TypeError, ValueError):
+            raise ValueError(f"window {window!r}: (x, y, cw, ch)") from None
+        if d.x < 0 or d.y < 0 or d.cw < 1 or d.ch < 1:
+            raise ValueError(f"window {tuple(window)}: x, y >= 0 and cw, ch >= 1 (luma samples)")
+    d.nch, d.dtype = len(channels), dts[dtype]
+    d.id[:len(channels)] = [_lib.ACCMV_CHANNELS[c] for c in channels]
+    d.scale[:len(channels)] = per_channel(scale, 1.0, "scale")
+    d.bias[:len(channels)] = per_channel(bias, 0.0, "bias")
+    return d, len(channels), dtype
+
+
 @dataclass
 class CapturedPicture:
     rec: int            # host address of w*h MbRec
@@ -454,9 +502,11 @@ class Engine:
             raise RuntimeError("h264mi_engine_keep_records failed")
 
     def forget_records(self, stream: int, slot: int) -> None:
-        """Mark the slot's kept records as "no information"."""
+        """Mark the slot's kept records as "no information" and, with
+        ``keep_accmv`` on, reset its origin map."""
         if self._L.h264mi_engine_forget_records(self._h, stream, slot) != 0:
-            raise RuntimeError("h264mi_engine_forget_records failed (keep_records off, or a bad stream or slot)")
+            raise RuntimeError("h264mi_engine_forget_records failed (keep_records and keep_accmv off, or a bad "
+                               "stream or slot)")
 
     def to_mbinfo(self, streams: Sequence[int], slots: Sequence[int], channels=("mvx", "mvy"), window=None,
                   dtype=None, scale=None, bias=None, out=None, stream=None):
@@ -510,6 +560,40 @@ class Engine:
         if self._L.h264mi_engine_export_residual(self._h, n, c_streams, c_slots, C.byref(desc), out.data_ptr(),
                                                  npl * shape[2] * shape[3] * out.element_size(), st) != 0:
             raise RuntimeError("h264mi_engine_export_residual failed (keep_coefs off, or stream, slot or window "
+                               "out of range?)")
+        return out
+
+    def keep_accmv(self, on: bool = True) -> None:
+        """Keep each picture's origin map -- every luma sample traced back to
+        its position in the key picture of its GOP -- on the device, per
+        (stream, slot), from the next ``decode`` on (to_accmv reads them): 1024
+        bytes per MB and slot, 8.36 MB per 1080p slot, and one gather launch
+        per picture.  ``on=False`` waits for the engine and frees them.
+        ``decode_device*`` launches retain nothing."""
+        if not hasattr(self._L, "h264mi_engine_keep_accmv") or \
+                self._L.h264mi_engine_keep_accmv(self._h, int(bool(on))) != 0:
+            raise RuntimeError("h264mi_engine_keep_accmv failed")
+
+    def to_accmv(self, streams: Sequence[int], slots: Sequence[int], channels=("adx", "ady"), window=None,
+                 dtype=None, scale=None, bias=None, out=None, stream=None):
+        """The accumulated motion of the pictures last decoded into the slots
+        (streams[k], slots[k]) as one ``(n, C, ch, cw)`` torch tensor on
+        ``cuda:{self.device}``, one element per luma sample of ``window`` = (x,
+        y, cw, ch) (None: the whole MB-aligned picture) and per name in
+        ``channels`` (``accmv_desc``; a slot nothing was decoded into reads as
+        (x, y, 0): no displacement, not anchored).  Needs ``keep_accmv()``
+        before the decodes.  ``out`` and ``stream`` as for ``to_tensor``; the
+        host is never synchronised."""
+        n, c_streams, c_slots = self._pictures(streams, slots)
+        if window is None:
+            window = (0, 0, self.w_mbs * 16, self.h_mbs * 16)
+        desc, nch, dtype = accmv_desc(channels, window, dtype, scale, bias)
+        shape = (n, nch, desc.ch, desc.cw)
+        out, st = self._out(shape, dtype, out, stream)
+        if not hasattr(self._L, "h264mi_engine_export_accmv") or \
+                self._L.h264mi_engine_export_accmv(self._h, n, c_streams, c_slots, C.byref(desc), out.data_ptr(),
+                                                   nch * desc.ch * desc.cw * out.element_size(), st) != 0:
+            raise RuntimeError("h264mi_engine_export_accmv failed (keep_accmv off, or stream, slot or window "
                                "out of range?)")
         return out
 

@@ -321,6 +321,65 @@ H264SwDecRet H264SwDecKeepResidual(H264SwDecInst decInst, u32 on);
  * backend cannot export. */
 H264SwDecRet H264SwDecLastPictureResidual(H264SwDecInst decInst, const h264mi_residual_desc *desc, void *d_dst,
                                           void *hip_stream);
+/* Accumulated motion as a device tensor (accmv.hip): every luma
+ * sample traced back, hop by hop, through the pictures it was predicted from to
+ * its position in the key picture of its GOP -- what compressed-domain models
+ * (CoViAR and its descendants) train on instead of the per-picture field above.
+ * Everything lives on the luma sample grid of the MB-aligned picture, W = 16 *
+ * w_mbs by H = 16 * h_mbs, both at most H264MI_ACCMV_MAX_DIM.
+ * An origin map is one 32-bit word per sample, row-major, W words per row:
+ * bits 0..14 JX, bit 15 zero, bits 16..30 JY, bit 31 ANCHORED.
+ * One step makes picture t's map from its record batch r, per DPB slot of its
+ * stream either an origin map or none, and a key flag.  Sample (x, y) belongs
+ * to record (y >> 4) * w_mbs + (x >> 4) and to its z-scan block b of ((x >> 2)
+ * & 3, (y >> 2) & 3) (h264mi_mbinfo_desc's b):
+ *   key set: (JX, JY, ANCHORED) = (x, y, 1) for every sample; r is not read.
+ *   r.type MBT_INTER or MBT_SKIP: d = ((mv[b][0] + 2) >> 2, (mv[b][1] + 2) >> 2),
+ *     an arithmetic shift in 32 bits (integer-pel, round half up); q = (clamp(x
+ *     + d.x, 0, W - 1), clamp(y + d.y, 0, H - 1)), the clamp of the reference
+ *     fetch; s = r.ref[b >> 2].  If slot s has a map, the sample is that map's
+ *     word at q, whole.  If it has none, or s >= nslots, it is (q.x, q.y, 0) and
+ *     nothing is read for it.
+ *   every other type (MBT_I4x4, MBT_I16, MBT_IPCM, 255): (x, y, 0); mv and ref
+ *     are not looked at.
+ * So ANCHORED = 1 means every hop back to the key picture was inter prediction
+ * and (JX, JY) is where the sample sat in the key picture; ANCHORED = 0 means
+ * the chain started at an intra MB, a slot without a map or an older key, and
+ * the coordinates are those of that start.
+ * An export is one integer v per sample of the window (x, y, cw, ch), in luma
+ * samples anywhere inside W x H, and per channel id[0 .. nch), 1 <= nch <=
+ * H264MI_ACCMV_MAX_CH, any order, repeats allowed:
+ *   ADX  JX - x (the sign of MVX: one unclamped hop from a key picture gives
+ *        (MVX + 2) >> 2)        ADY  JY - y
+ *   JX, JY                      ANCHORED  0 or 1
+ * Elements: H264MI_TENSOR_I16 (v) or F16 / BF16 / F32, fma((float)v, scale[c],
+ * bias[c]) of channel position c, converted as for h264mi_tensor_desc; U8 is
+ * refused. */
+enum { H264MI_ACCMV_ADX = 0, H264MI_ACCMV_ADY = 1, H264MI_ACCMV_JX = 2, H264MI_ACCMV_JY = 3,
+       H264MI_ACCMV_ANCHORED = 4, H264MI_ACCMV_NCHANNELS = 5 };
+#define H264MI_ACCMV_MAX_CH 8
+#define H264MI_ACCMV_MAX_DIM 32768
+#define H264MI_ACCMV_MAX_SLOTS 32      /* slots a step takes maps for */
+typedef struct {
+    int x, y, cw, ch, nch, dtype;
+    int id[8];
+    float scale[8], bias[8];
+} h264mi_accmv_desc;
+/* Keep the origin map of every picture, per frame slot, on the device (on != 0;
+ * 0 frees them), from the next picture on: 1024 bytes per MB and slot (8.36 MB
+ * per 1080p slot) and one gather launch per picture.  It survives a change of
+ * picture size, and on a shared engine it is only ever switched on.
+ * H264SWDEC_PARAM_ERR when the backend cannot keep them. */
+H264SwDecRet H264SwDecKeepAccMotion(H264SwDecInst decInst, u32 on);
+/* The accumulated motion of the picture most recently delivered by any
+ * H264SwDecNextPicture* call of the instance, as (nch, ch, cw) elements at d_dst
+ * (on the decoder's GPU, a multiple of the element size), ordered on
+ * `hip_stream` as h264mi_engine_export_accmv orders it.  The DPB is not touched.
+ * Valid until the next H264SwDecDecode.  desc->cw == 0 and desc->ch == 0: the
+ * active SPS's crop window.  The return codes are H264SwDecLastPictureMbInfo's
+ * (H264SWDEC_PARAM_ERR also without H264SwDecKeepAccMotion). */
+H264SwDecRet H264SwDecLastPictureAccMotion(H264SwDecInst decInst, const h264mi_accmv_desc *desc, void *d_dst,
+                                           void *hip_stream);
 /* Extension (no reference counterpart): where an instance's time went, in
  * seconds since H264SwDecInit -- host parse (NAL extraction, headers, CAVLC /
  * MB layer, DPB, concealment), record upload + kernel launch, waiting for the
@@ -551,8 +610,9 @@ int  h264mi_mbinfo_device(const void *d_recs, const size_t *rec_offsets, int npi
  * 0, or -1 on a bad argument / HIP error. */
 int  h264mi_engine_keep_records(h264mi_engine *e, int on);
 /* refills the slot's batch with 0xFF bytes, behind the work queued on the
- * engine (its picture did not come from a reconstruction); -1 when retention
- * is off or on a bad stream or slot */
+ * engine (its picture did not come from a reconstruction), and with
+ * h264mi_engine_keep_accmv on resets its origin map; -1 when both retentions
+ * are off or on a bad stream or slot */
 int  h264mi_engine_forget_records(h264mi_engine *e, int stream, int slot);
 /* the kept batches of the slots (streams[k], slots[k]), k < n, as fields in the
  * caller's memory, ordered as h264mi_engine_export_tensor orders its export (no
@@ -598,6 +658,48 @@ int  h264mi_engine_keep_coefs(h264mi_engine *e, int on);
 int  h264mi_engine_export_residual(h264mi_engine *e, int n, const int *streams, const int *slots,
                                    const h264mi_residual_desc *desc, void *d_out, size_t out_stride,
                                    void *hip_stream);
+/* one step of the accumulated motion (h264mi_accmv_desc above): the origin map
+ * of the picture whose w_mbs * h_mbs MbRec start at d_recs (16-byte aligned),
+ * W * H words at d_map_out, from the maps d_ref_maps[s], s < nslots <=
+ * H264MI_ACCMV_MAX_SLOTS (a host array of device pointers; NULL: slot s has
+ * none; d_ref_maps itself may be NULL when nslots is 0), or with key != 0 the
+ * identity.  No map may be d_map_out.  Nothing outside d_map_out's W * H words
+ * is written and nothing outside the maps' is read.  Stateless; asynchronous on
+ * `hip_stream`.  -1 on a bad argument or a picture beyond H264MI_ACCMV_MAX_DIM,
+ * nothing launched.  For callers that hold their records on the device. */
+int  h264mi_accmv_step_device(const void *d_recs, int w_mbs, int h_mbs, const void *const *d_ref_maps, int nslots,
+                              int key, void *d_map_out, void *hip_stream);
+/* the channels of desc over npics origin maps, map k starting map_offsets[k]
+ * bytes (a host array of multiples of 4; any order, repeats allowed) after
+ * d_maps: picture k's (nch, ch, cw) elements, contiguous, at d_out + k *
+ * out_stride, under the alignment rules of h264mi_mbinfo_device; nothing else
+ * is written.  Stateless; asynchronous on `hip_stream`.  -1 on a bad argument,
+ * nothing launched. */
+int  h264mi_accmv_device(const void *d_maps, const size_t *map_offsets, int npics, int w_mbs, int h_mbs,
+                         const h264mi_accmv_desc *desc, void *d_out, size_t out_stride, void *hip_stream);
+/* origin-map retention: on != 0 allocates one map per (stream, slot), 1024
+ * bytes per MB (8.36 MB per 1080p slot: 1.14 GB for eight streams of 17 slots),
+ * each (x, y, 0); from then on h264mi_engine_decode and the H264SwDec* path
+ * queue one step per picture behind its reconstruction, on the engine's stream,
+ * reading the uploaded records in place.  A picture without a single MBT_INTER
+ * / MBT_SKIP record is a key picture: it starts its stream's next GOP and steps
+ * with the key flag.  Any other picture steps from the maps of its stream's
+ * slots that were written since that key picture (the slot it is decoded into
+ * excepted); a map from before it counts as none, though it stays exportable.
+ * A slot's map is that of the last reconstruction into it;
+ * h264mi_engine_forget_records resets it to (x, y, 0).  The decode_device*
+ * launches retain nothing.  0 (the default: nothing is allocated or queued)
+ * waits for the engine's stream and frees the maps.  -1 on a bad argument, a
+ * picture beyond H264MI_ACCMV_MAX_DIM, more than H264MI_ACCMV_MAX_SLOTS slots or
+ * a HIP error. */
+int  h264mi_engine_keep_accmv(h264mi_engine *e, int on);
+/* the kept maps of the slots (streams[k], slots[k]), k < n, as tensors in the
+ * caller's memory, ordered as h264mi_engine_export_mbinfo orders its export (no
+ * host synchronisation; a later decode into one of the slots waits for the
+ * export).  -1 when retention is off, on a bad stream, slot or desc, or when
+ * d_out is not on the engine's device. */
+int  h264mi_engine_export_accmv(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                const h264mi_accmv_desc *desc, void *d_out, size_t out_stride, void *hip_stream);
 int  h264mi_engine_sync(h264mi_engine *e);
 /* number of (launch, picture) slots flagged since the last call: residual
  * range errors (reference transform.c:181) or a bounded wait that expired;
