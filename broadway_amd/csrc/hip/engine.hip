@@ -110,6 +110,18 @@ struct h264mi_engine {
     uint32_t err_bits;        // OR of every picture's device flags since the last h264mi_engine_error_bits
 };
 
+// k_wgpp's instances, in the order of wgpp_variants (wgpp_variants.h): this
+// table is what instantiates them.  lds: the dynamic LDS of a launch on a
+// picture w MBs wide (cols: a DEP_COLS launch's progress cache beside it)
+struct WgppLaunch {
+    const void *fn;
+    size_t (*lds)(int w, bool cols);
+};
+#define WGPP_LAUNCH_ROW(NMC, PROF, RPW, CHK, DEPM) \
+    {reinterpret_cast<const void *>(&k_wgpp<NMC, PROF, true, RPW, CHK, DEPM>), &WgppLds<NMC, RPW>::bytes},
+static const WgppLaunch wgpp_launch[WGPP_NVARIANTS] = {WGPP_VARIANTS(WGPP_LAUNCH_ROW)};
+#undef WGPP_LAUNCH_ROW
+
 // per-picture buffers of one launch (deblocking records, residuals, row
 // mailboxes, error flags), for `cap` pictures
 static void free_pic_buffers(h264mi_engine *e)
@@ -174,52 +186,8 @@ static void engine_config(h264mi_engine *e)
     // the static LDS of its rows (regions, MC scratch, a RINGG-slot ring)
     // within the CU's 160 KB
     // k_wgpp's LDS is dynamic (WgppLds): allow every variant the CU's 160 KB
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<3, false, true, 1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<3, true, true, 1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<3, false, true, 2>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<3, true, true, 2>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<3, false, true, 3>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<3, true, true, 3>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<2, false, true, 1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<6, true, true, 1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<6, false, true, 1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<6, false, true, 1, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<2, false, true, 2>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<2, true, true, 1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<3, false, true, 1, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<2, false, true, 1, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<3, false, true, 2, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<2, false, true, 2, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<3, false, true, 3, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<2, false, true, 1, false, DEP_ROWS>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<2, false, true, 1, true, DEP_ROWS>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<2, true, true, 1, false, DEP_ROWS>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<2, false, true, 1, false, DEP_COLS>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<2, false, true, 1, true, DEP_COLS>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_wgpp<2, true, true, 1, false, DEP_COLS>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    for (const WgppLaunch &k : wgpp_launch)
+        (void)hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     const size_t row_lds = sizeof(PPLds) + (size_t)(e->mc_waves == 2 ? 2 : e->mc_waves == 6 ? 6 : 3) * sizeof(McScratch) + sizeof(MbRing<RINGG>);
     e->rpw_max = e->mc_waves == 2 ? 2 : 3;
     while (e->rpw_max > 1 && (size_t)(e->rpw_max - 1) * e->w * 256 + (size_t)e->rpw_max * row_lds > 156 * 1024)
@@ -427,7 +395,7 @@ static int launch_batch(h264mi_engine *e, int S, int P, const MbRec *d_rec, cons
     }
     a.epoch = e->epoch;
     // (a launch of more pictures than the stamp buffer holds runs unstamped)
-    a.prof = e->d_prof && (size_t)npics * ((size_t)e->h * 16 + (size_t)e->nmbs * PROF_MB) <= e->prof_cap ? e->d_prof : nullptr;
+    a.prof = e->d_prof && (size_t)npics * ((size_t)e->h * PROF_ROW + (size_t)e->nmbs * PROF_MB) <= e->prof_cap ? e->d_prof : nullptr;
     a.prof_mode = e->d_prof && getenv("H264MI_PROF_MODE") ? atoi(getenv("H264MI_PROF_MODE")) : 0;
     // study knobs: MC lead over the row's deblocking (MBs; 0 / unset = the
     // ring depth), before the chain has begun (LEAD0, at least 4) and after
@@ -492,7 +460,6 @@ static int launch_batch(h264mi_engine *e, int S, int P, const MbRec *d_rec, cons
         rec_tev = true;
     }
     const bool rec = e->timing || rec_tev;
-    e->last_kernel = "k_wgpp";
     // frame-pipelined launches: the DEP_ROWS / DEP_COLS instances (single-row,
     // 2 MC waves).  The mode is the caller's hint for this launch or the
     // engine's default; whole rows need every slot below 32 (a bit mask)
@@ -506,69 +473,30 @@ static int launch_batch(h264mi_engine *e, int S, int P, const MbRec *d_rec, cons
     const int nmc = dep3 ? 2 : launch_nmc(e, rpw, P, npics);
     e->last_nmc = nmc;
     e->launch_intra = -1;                     // a hint covers one launch
-    const size_t lmbx = nmc == 2 && (!a.prof || rpw == 1) ? (rpw == 2 ? WgppLds<2, 2>::bytes(e->w)
-                                                                      : WgppLds<2, 1>::bytes(e->w, dep3 && dmode == DEP_COLS))
-                        : rpw == 3 ? WgppLds<3, 3>::bytes(e->w) : rpw == 2 ? WgppLds<3, 2>::bytes(e->w)
-                        : nmc == 6 ? WgppLds<6, 1>::bytes(e->w) : WgppLds<3, 1>::bytes(e->w);
-    if (dep3) {
-        e->last_kernel = e->check ? "k_wgpp_check" : a.prof ? "k_wgpp_prof" : "k_wgpp";
-#define DEP_LAUNCH(M)                                                                                          \
-        do {                                                                                                   \
-            if (a.prof && !e->check)                                                                           \
-                hipExtLaunchKernelGGL((k_wgpp<2, true, true, 1, false, M>), grid, dim3(256), lmbx, e->st,      \
-                                      rec ? t0 : nullptr, rec ? t2 : nullptr, 0, a);                          \
-            else if (e->check)                                                                                 \
-                hipExtLaunchKernelGGL((k_wgpp<2, false, true, 1, true, M>), grid, dim3(256), lmbx, e->st,      \
-                                      rec ? t0 : nullptr, rec ? t2 : nullptr, 0, a);                          \
-            else                                                                                               \
-                hipExtLaunchKernelGGL((k_wgpp<2, false, true, 1, false, M>), grid, dim3(256), lmbx, e->st,     \
-                                      rec ? t0 : nullptr, rec ? t2 : nullptr, 0, a);                          \
-        } while (0)
-        if (dmode == DEP_COLS) DEP_LAUNCH(DEP_COLS);
-        else DEP_LAUNCH(DEP_ROWS);
-#undef DEP_LAUNCH
-    } else if (a.prof) {
-        if (rec) (void)hipEventRecord(t0, e->st);
-        if (rpw == 3) hipLaunchKernelGGL((k_wgpp<3, true, true, 3>), grid, dim3(960), lmbx, e->st, a);
-        else if (rpw == 2) hipLaunchKernelGGL((k_wgpp<3, true, true, 2>), grid, dim3(640), lmbx, e->st, a);
-        else if (nmc == 2) hipLaunchKernelGGL((k_wgpp<2, true, true, 1>), grid, dim3(256), lmbx, e->st, a);
-        else if (nmc == 6) hipLaunchKernelGGL((k_wgpp<6, true, true, 1>), grid, dim3(512), lmbx, e->st, a);
-        else hipLaunchKernelGGL((k_wgpp<3, true, true, 1>), grid, dim3(320), lmbx, e->st, a);
-        if (rec) (void)hipEventRecord(t2, e->st);
-    } else if (e->check) {
-        // dependency checker (H264MI_CHECK=1): every hand-off verified at
-        // its consumer, violations in the pictures' error words
-        e->last_kernel = "k_wgpp_check";
-        if (rec) (void)hipEventRecord(t0, e->st);
-        if (rpw == 3) hipLaunchKernelGGL((k_wgpp<3, false, true, 3, true>), grid, dim3(960), lmbx, e->st, a);
-        else if (rpw == 2 && nmc == 2) hipLaunchKernelGGL((k_wgpp<2, false, true, 2, true>), grid, dim3(512), lmbx, e->st, a);
-        else if (rpw == 2) hipLaunchKernelGGL((k_wgpp<3, false, true, 2, true>), grid, dim3(640), lmbx, e->st, a);
-        else if (nmc == 2) hipLaunchKernelGGL((k_wgpp<2, false, true, 1, true>), grid, dim3(256), lmbx, e->st, a);
-        else if (nmc == 6) hipLaunchKernelGGL((k_wgpp<6, false, true, 1, true>), grid, dim3(512), lmbx, e->st, a);
-        else hipLaunchKernelGGL((k_wgpp<3, false, true, 1, true>), grid, dim3(320), lmbx, e->st, a);
-        if (rec) (void)hipEventRecord(t2, e->st);
-    } else if (nmc == 2) {
-        // sizing study (H264MI_MC_WAVES=2): two MC waves per row workgroup
-        if (rpw == 2)
-            hipExtLaunchKernelGGL((k_wgpp<2, false, true, 2>), grid, dim3(512), lmbx, e->st, rec ? t0 : nullptr,
-                                  rec ? t2 : nullptr, 0, a);
-        else
-            hipExtLaunchKernelGGL((k_wgpp<2, false, true, 1>), grid, dim3(256), lmbx, e->st, rec ? t0 : nullptr,
-                                  rec ? t2 : nullptr, 0, a);
-    } else if (nmc == 6) {
-        hipExtLaunchKernelGGL((k_wgpp<6, false, true, 1>), grid, dim3(512), lmbx, e->st, rec ? t0 : nullptr,
-                              rec ? t2 : nullptr, 0, a);
-    } else if (rpw == 3) {
+    // the instance for this shape (wgpp_variants.h), its LDS and block size
+    const WgppChoice ch = wgpp_select(nmc, rpw, a.prof != nullptr, e->check != 0, dep3, dmode);
+    if (ch.variant < 0) {
+        fprintf(stderr, "h264mi: no k_wgpp instance for %d MC waves, %d rows per workgroup, %d steps\n", nmc, rpw, P);
+        return -1;
+    }
+    const WgppVariant &v = wgpp_variants[ch.variant];
+    const WgppLaunch &k = wgpp_launch[ch.variant];
+    const size_t lmbx = k.lds(e->w, v.depm == DEP_COLS);
+    const dim3 block(wgpp_block_size(v.nmc, v.rpw));
+    void *args[] = {&a};
+    e->last_kernel = ch.name;
+    if (ch.ev_on_packet) {
         // the timing events ride on the kernel's own dispatch packet
-        // (hipExtLaunchKernelGGL): no marker packets between launches
-        hipExtLaunchKernelGGL((k_wgpp<3, false, true, 3>), grid, dim3(960), lmbx, e->st, rec ? t0 : nullptr,
-                              rec ? t2 : nullptr, 0, a);
-    } else if (rpw == 2) {
-        hipExtLaunchKernelGGL((k_wgpp<3, false, true, 2>), grid, dim3(640), lmbx, e->st, rec ? t0 : nullptr,
-                              rec ? t2 : nullptr, 0, a);
+        // (hipExtLaunchKernel): no marker packets between launches
+        (void)hipExtLaunchKernel(k.fn, grid, block, args, lmbx, e->st, rec ? t0 : nullptr, rec ? t2 : nullptr, 0);
     } else {
-        hipExtLaunchKernelGGL((k_wgpp<3, false, true, 1>), grid, dim3(320), lmbx, e->st, rec ? t0 : nullptr,
-                              rec ? t2 : nullptr, 0, a);
+        // the profiling instances, and the dependency checker's
+        // (H264MI_CHECK=1: every hand-off verified at its consumer,
+        // violations in the pictures' error words), outside frame-pipelined
+        // launches: the events recorded around the launch
+        if (rec) (void)hipEventRecord(t0, e->st);
+        (void)hipLaunchKernel(k.fn, grid, block, args, lmbx, e->st);
+        if (rec) (void)hipEventRecord(t2, e->st);
     }
     HIPCHECK(hipGetLastError());
     e->rows_launched += rows;
@@ -667,6 +595,47 @@ extern "C" int h264mi_engine_decode(h264mi_engine *e, int npics, const int *stre
     return engine_decode_host(e, npics, stream, cur_slot, recs, coefs, ncoef, -1);
 }
 
+// the three steps the two upload paths below share
+// room for `total` coefficient blocks in the device pool and its pinned staging
+static int reserve_coefs(h264mi_engine *e, size_t total)
+{
+    if (total + 16 <= e->coef_cap) return 0;
+    HIPCHECK(hipStreamSynchronize(e->st));
+    (void)hipFree(e->d_coef);
+    (void)hipHostFree(e->h_coef);
+    e->coef_cap = e->h_coef_cap = total + total / 2 + 1024;
+    HIPCHECK(hipMalloc(&e->d_coef, e->coef_cap * 32));
+    HIPCHECK(hipHostMalloc(&e->h_coef, e->h_coef_cap * 32, hipHostMallocDefault));
+    return 0;
+}
+
+// batch picture i's descriptor in the pinned staging: its records at
+// d_rec + i * nmbs, its coefficient blocks from cbase on; the flags from a
+// scan of its records (intra-heavy: more than half its MBs intra; no
+// deblocking: no MB filters an inner edge)
+static void fill_pic_desc(h264mi_engine *e, int i, int stream, int cur_slot, const void *rec, size_t cbase)
+{
+    PicDesc &pd = e->h_pics[i];
+    pd.rec_base = (uint32_t)(i * e->nmbs);
+    pd.frame_base = (uint32_t)(stream * e->nslots);
+    pd.cur_slot = (uint32_t)cur_slot;
+    const MbRec *r = (const MbRec *)rec;
+    int n = 0, db = 0;
+    for (int m = 0; m < e->nmbs; m++) { n += r[m].type >= MBT_I4x4; db |= r[m].avail & DB_INNER; }
+    pd.flags = (2 * n > e->nmbs ? PD_INTRA_HEAVY : 0) | (db ? 0 : PD_NO_DEBLOCK);
+    pd.coef_base = (uint32_t)cbase;
+    pd.rsv[0] = pd.rsv[1] = pd.rsv[2] = 0;
+}
+
+// what is kept of the uploaded batch, queued behind its launch
+static int retain_batch(h264mi_engine *e, int npics, const int *stream, const int *cur_slot, const void *const *recs,
+                        const uint32_t *ncoef)
+{
+    if (e->d_acc && accmv_batch(e, npics, stream, cur_slot, recs)) return -1;
+    if (e->d_keep && keep_batch(e, npics, stream, cur_slot)) return -1;
+    return e->d_keepc ? keep_coef_batch(e, npics, stream, cur_slot, ncoef) : 0;
+}
+
 int engine_decode_host(h264mi_engine *e, int npics, const int *stream, const int *cur_slot,
                        const void *const *recs, const int16_t *const *coefs, const uint32_t *ncoef,
                        int intra_heavy)
@@ -677,31 +646,13 @@ int engine_decode_host(h264mi_engine *e, int npics, const int *stream, const int
     HIPCHECK(hipEventSynchronize(e->ev_staged));
     size_t total = 0;
     for (int i = 0; i < npics; i++) total += ncoef[i];
-    if (total + 16 > e->coef_cap) {
-        HIPCHECK(hipStreamSynchronize(e->st));
-        (void)hipFree(e->d_coef);
-        (void)hipHostFree(e->h_coef);
-        e->coef_cap = e->h_coef_cap = total + total / 2 + 1024;
-        HIPCHECK(hipMalloc(&e->d_coef, e->coef_cap * 32));
-        HIPCHECK(hipHostMalloc(&e->h_coef, e->h_coef_cap * 32, hipHostMallocDefault));
-    }
+    if (reserve_coefs(e, total)) return -1;
     size_t cbase = 0;
     for (int i = 0; i < npics; i++) {
         if (stream[i] < 0 || stream[i] >= e->nstreams || cur_slot[i] < 0 || cur_slot[i] >= e->nslots) return -1;
         memcpy(e->h_rec + (size_t)i * e->nmbs, recs[i], sizeof(MbRec) * e->nmbs);
         if (ncoef[i]) memcpy(e->h_coef + cbase * 16, coefs[i], (size_t)ncoef[i] * 32);
-        PicDesc &pd = e->h_pics[i];
-        pd.rec_base = (uint32_t)(i * e->nmbs);
-        pd.frame_base = (uint32_t)(stream[i] * e->nslots);
-        pd.cur_slot = (uint32_t)cur_slot[i];
-        {
-            const MbRec *r = (const MbRec *)recs[i];
-            int n = 0, db = 0;
-            for (int m = 0; m < e->nmbs; m++) { n += r[m].type >= MBT_I4x4; db |= r[m].avail & DB_INNER; }
-            pd.flags = (2 * n > e->nmbs ? PD_INTRA_HEAVY : 0) | (db ? 0 : PD_NO_DEBLOCK);
-        }
-        pd.coef_base = (uint32_t)cbase;
-        pd.rsv[0] = pd.rsv[1] = pd.rsv[2] = 0;
+        fill_pic_desc(e, i, stream[i], cur_slot[i], recs[i], cbase);
         cbase += ncoef[i];
     }
     HIPCHECK(hipMemcpyAsync(e->d_rec, e->h_rec, sizeof(MbRec) * e->nmbs * npics, hipMemcpyHostToDevice, e->st));
@@ -713,11 +664,11 @@ int engine_decode_host(h264mi_engine *e, int npics, const int *stream, const int
     for (int i = 0; i < npics && !heavy && intra_heavy < 0; i++) heavy = (e->h_pics[i].flags & PD_INTRA_HEAVY) != 0;
     e->launch_intra = heavy;
     if (launch_batch(e, npics, 1, e->d_rec, e->d_coef, e->d_pics, NULL, NULL, NULL)) return -1;
-    if (e->d_acc && accmv_batch(e, npics, stream, cur_slot, recs)) return -1;
-    if (e->d_keep && keep_batch(e, npics, stream, cur_slot)) return -1;
-    return e->d_keepc ? keep_coef_batch(e, npics, stream, cur_slot, ncoef) : 0;
+    return retain_batch(e, npics, stream, cur_slot, recs, ncoef);
 }
 
+// one picture whose records and coefficients are already pinned: uploaded
+// from where they are, no staging copy
 int engine_decode_direct(h264mi_engine *e, int stream, int cur_slot, const void *rec, const int16_t *coef,
                          uint32_t ncoef, int intra_heavy)
 {
@@ -725,35 +676,15 @@ int engine_decode_direct(h264mi_engine *e, int stream, int cur_slot, const void 
     HIPCHECK(hipSetDevice(e->dev));
     // the descriptor staging is reused: wait until the previous upload consumed it
     HIPCHECK(hipEventSynchronize(e->ev_staged));
-    if ((size_t)ncoef + 16 > e->coef_cap) {
-        HIPCHECK(hipStreamSynchronize(e->st));
-        (void)hipFree(e->d_coef);
-        (void)hipHostFree(e->h_coef);
-        e->coef_cap = e->h_coef_cap = ncoef + ncoef / 2 + 1024;
-        HIPCHECK(hipMalloc(&e->d_coef, e->coef_cap * 32));
-        HIPCHECK(hipHostMalloc(&e->h_coef, e->h_coef_cap * 32, hipHostMallocDefault));
-    }
-    PicDesc &pd = e->h_pics[0];
-    pd.rec_base = 0;
-    pd.frame_base = (uint32_t)(stream * e->nslots);
-    pd.cur_slot = (uint32_t)cur_slot;
-    {
-        const MbRec *r = (const MbRec *)rec;
-        int n = 0, db = 0;
-        for (int m = 0; m < e->nmbs; m++) { n += r[m].type >= MBT_I4x4; db |= r[m].avail & DB_INNER; }
-        pd.flags = (2 * n > e->nmbs ? PD_INTRA_HEAVY : 0) | (db ? 0 : PD_NO_DEBLOCK);
-    }
-    pd.coef_base = 0;
-    pd.rsv[0] = pd.rsv[1] = pd.rsv[2] = 0;
+    if (reserve_coefs(e, ncoef)) return -1;
+    fill_pic_desc(e, 0, stream, cur_slot, rec, 0);
     HIPCHECK(hipMemcpyAsync(e->d_rec, rec, sizeof(MbRec) * e->nmbs, hipMemcpyHostToDevice, e->st));
     if (ncoef) HIPCHECK(hipMemcpyAsync(e->d_coef, coef, (size_t)ncoef * 32, hipMemcpyHostToDevice, e->st));
     HIPCHECK(hipMemcpyAsync(e->d_pics, e->h_pics, sizeof(PicDesc), hipMemcpyHostToDevice, e->st));
     HIPCHECK(hipEventRecord(e->ev_staged, e->st));
-    e->launch_intra = intra_heavy >= 0 ? intra_heavy : (pd.flags & PD_INTRA_HEAVY) != 0;
+    e->launch_intra = intra_heavy >= 0 ? intra_heavy : (e->h_pics[0].flags & PD_INTRA_HEAVY) != 0;
     if (launch_batch(e, 1, 1, e->d_rec, e->d_coef, e->d_pics, NULL, NULL, NULL)) return -1;
-    if (e->d_acc && accmv_batch(e, 1, &stream, &cur_slot, &rec)) return -1;
-    if (e->d_keep && keep_batch(e, 1, &stream, &cur_slot)) return -1;
-    return e->d_keepc ? keep_coef_batch(e, 1, &stream, &cur_slot, &ncoef) : 0;
+    return retain_batch(e, 1, &stream, &cur_slot, &rec, &ncoef);
 }
 
 int engine_records_wait(h264mi_engine *e)
@@ -835,11 +766,14 @@ extern "C" int h264mi_engine_decode_device_steps_next(h264mi_engine *e, int S, i
 // the main single-row kernel (rpw 1), and its kernel attributes
 extern "C" int h264mi_kernel_occupancy(int *blocks_per_cu, int *lds_bytes, int *vgprs, int *sgprs)
 {
+    constexpr int vi = wgpp_find(3, false, 1, false, DEP_NONE);
+    static_assert(vi >= 0, "the main single-row instance is in WGPP_VARIANTS");
+    const WgppLaunch &k = wgpp_launch[vi];
     hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_wgpp<3, false, true, 1>)) != hipSuccess) return -1;
+    if (hipFuncGetAttributes(&fa, k.fn) != hipSuccess) return -1;
     int n = 0;
-    const size_t lds = WgppLds<3, 1>::bytes(120);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_wgpp<3, false, true, 1>, 320, lds) != hipSuccess) return -1;
+    const size_t lds = k.lds(120, false);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k.fn, wgpp_block_size(wgpp_variants[vi].nmc, wgpp_variants[vi].rpw), lds) != hipSuccess) return -1;
     if (blocks_per_cu) *blocks_per_cu = n;
     if (lds_bytes) *lds_bytes = (int)(fa.sharedSizeBytes + lds);
     if (vgprs) *vgprs = fa.numRegs;
@@ -853,7 +787,7 @@ static int prof_alloc(h264mi_engine *e)
 {
     (void)hipFree(e->d_prof);
     e->d_prof = NULL;
-    e->prof_cap = (size_t)e->pipe_cap * e->h * 16 + (size_t)e->pipe_cap * e->nmbs * PROF_MB;
+    e->prof_cap = (size_t)e->pipe_cap * e->h * PROF_ROW + (size_t)e->pipe_cap * e->nmbs * PROF_MB;
     HIPCHECK(hipMalloc(&e->d_prof, sizeof(unsigned long long) * e->prof_cap));
     HIPCHECK(hipMemset(e->d_prof, 0, sizeof(unsigned long long) * e->prof_cap));
     return 0;

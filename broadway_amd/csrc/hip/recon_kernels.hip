@@ -20,10 +20,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../../include/h264mi_records.h"
+#include "wgpp_variants.h"
 
 #define WAVE 64
 // profiling build: u64 stamps per MB (row waves [0..2], MC [3], intra [4..5])
 #define PROF_MB 8
+// and u64 per (picture, MB row) record, which come first in the buffer
+#define PROF_ROW 16
 
 struct ReconArgs {
     uint8_t *frames;          // frame pool (I420 per slot, chroma rows cpitch apart: H264MI_CPITCH)
@@ -1696,10 +1699,10 @@ __device__ void row_pp(const ReconArgs &a, int p, int r, PPLds &L, const int w, 
     unsigned long long tc0 = 0, tc1, tva = 0, tvd = 0;
 #define PPT(i) do { if (prof) { tc1 = clock64(); pt[i] += tc1 - tc0; tc0 = tc1; } } while (0)
     if (prof && w == 0 && lane == 0) {
-        a.prof[((size_t)r * a.npics + p) * 16] = wall_clock64();
+        a.prof[((size_t)r * a.npics + p) * PROF_ROW] = wall_clock64();
         // placement: HW_REG_HW_ID (CU / SH / SE of this wave) and HW_REG_XCC_ID
-        a.prof[((size_t)r * a.npics + p) * 16 + 10] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);
-        a.prof[((size_t)r * a.npics + p) * 16 + 11] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 20);
+        a.prof[((size_t)r * a.npics + p) * PROF_ROW + 10] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);
+        a.prof[((size_t)r * a.npics + p) * PROF_ROW + 11] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 20);
     }
 
     for (int c = w; c < W; c += 2) {
@@ -1715,7 +1718,7 @@ __device__ void row_pp(const ReconArgs &a, int p, int r, PPLds &L, const int w, 
         // may start); [1] V(c) start (after the hdone wait and halo copy) in
         // bits 0..31, V(c) end in bits 32..63; [2] entry c published in bits
         // 0..31, H(c) end (hdone = c + 1) in bits 32..63
-        unsigned long long *pmb = prof ? a.prof + (size_t)a.npics * H * 16 + ((size_t)(p * H + r) * W + c) * PROF_MB : nullptr;
+        unsigned long long *pmb = prof ? a.prof + (size_t)a.npics * H * PROF_ROW + ((size_t)(p * H + r) * W + c) * PROF_MB : nullptr;
         const cu32p rw = recw + c * 24;
         const uint32_t h0 = rw[0];
         // MB c+1's record dword 0 (avail), for the hand-off patch (a VMEM load:
@@ -1976,7 +1979,7 @@ __device__ void row_pp(const ReconArgs &a, int p, int r, PPLds &L, const int w, 
         if (lane == 0) st_gran(prog_me, (uint32_t)W, tag);
     }
     if (prof) {
-        unsigned long long *o = a.prof + ((size_t)r * a.npics + p) * 16;
+        unsigned long long *o = a.prof + ((size_t)r * a.npics + p) * PROF_ROW;
         if (lane == 0 && ((W - 1) & 1) == w) o[1] = wall_clock64();
         if (w == 1) {
             if (lane == 0) {
@@ -2235,9 +2238,8 @@ __device__ __forceinline__ int mc_finish(const ReconArgs &a, int p, uint32_t v0,
 // waves have seen is kept in the workgroup's LDS (values only grow, so any
 // value a wave stores is a valid lower bound), so most MBs need no load.
 #define PC_ROWS 136         // MB rows of a producer the LDS progress cache holds (2160p: 135)
-// k_wgpp's dependency modes (template DEPM): none (one step per launch), whole
-// rows, or (MB row, MB column) cells
-enum { DEP_NONE = 0, DEP_ROWS = 1, DEP_COLS = 2 };
+// k_wgpp's dependency modes (template DEPM; wgpp_variants.h): none (one step
+// per launch), whole rows, or (MB row, MB column) cells
 struct DepState {
     int n;                 // in-launch producers: steps j - 1 .. j - n (0: none)
     uint32_t slots;        // DEP_COLS: their target slots, 8 bits each (step j - 1 - k at bits 8k)
@@ -2680,7 +2682,7 @@ __device__ __forceinline__ void mc_row(const ReconArgs &a, int p, int r, int c0,
         if (PROF) { drain_vm(); t_ld = wall_clock64(); }
         const int type = mc_finish(a, p, v0, lane, ld, Mw, R.px[slot], Mw.res, R.db[slot]);
         if (PROF && type < MBT_I4x4 && lane == 0) {
-            unsigned long long *pm = a.prof + (size_t)a.npics * a.h * 16 + ((size_t)(p * a.h + r) * a.w + c) * PROF_MB;
+            unsigned long long *pm = a.prof + (size_t)a.npics * a.h * PROF_ROW + ((size_t)(p * a.h + r) * a.w + c) * PROF_MB;
             pm[4] = (t0 & 0xFFFFFFFFull) | (t_ld << 32);
             pm[5] = wall_clock64() & 0xFFFFFFFFull;
         }
@@ -2692,7 +2694,7 @@ __device__ __forceinline__ void mc_row(const ReconArgs &a, int p, int r, int c0,
             mc_intra<UPL, MEL, RK, CHK, PROF, NMC == 6>((g_MbRec *)(a.rec + pd.rec_base + r * a.w + c), mbx_up, (g_u32 *)(a.err + p), a.w, c, a.epoch,
                               r > 0, lane, (lds_McScratch *)&Mw, (__attribute__((address_space(3))) MbRing<RK> *)&R,
                               (lds_cu32 *)i4tab,
-                              PROF ? (unsigned long long *)(a.prof + (size_t)a.npics * a.h * 16 + ((size_t)(p * a.h + r) * a.w + c) * PROF_MB + 4)
+                              PROF ? (unsigned long long *)(a.prof + (size_t)a.npics * a.h * PROF_ROW + ((size_t)(p * a.h + r) * a.w + c) * PROF_MB + 4)
                                    : NMC == 6 && r + 1 < a.h ? mbx_me + c * 32 : nullptr);
         }
         wave_sync();
@@ -2706,7 +2708,7 @@ __device__ __forceinline__ void mc_row(const ReconArgs &a, int p, int r, int c0,
         }
         // PROF stamp [3]: MC start in bits 0..31, flag set (slot final) in bits 32..63 (100 MHz)
         if (PROF && lane == 0)
-            a.prof[(size_t)a.npics * a.h * 16 + ((size_t)(p * a.h + r) * a.w + c) * PROF_MB + 3] = (t0 & 0xFFFFFFFFull) | (wall_clock64() << 32);
+            a.prof[(size_t)a.npics * a.h * PROF_ROW + ((size_t)(p * a.h + r) * a.w + c) * PROF_MB + 3] = (t0 & 0xFFFFFFFFull) | (wall_clock64() << 32);
         if (lane == 0) {
             if (CHK) *(uint16_t *)&R.db[slot][CHK_TAG_OFF] = (uint16_t)(c ^ (a.chk_inject == 1 && c == 5 ? 1 : 0));
             lds_st(&R.lprog[slot], (c << 4) | 10);
@@ -2720,7 +2722,7 @@ __device__ __forceinline__ void mc_row(const ReconArgs &a, int p, int r, int c0,
         if (DEPM == DEP_ROWS && c < a.w && D.n) dep_wait_rows<CHK>(a, p, v0, lane, D);
         // PROF stamp [6] of the next MB: its in-launch dependency wait (100 MHz ticks)
         if (PROF && DEPM != DEP_NONE && c < a.w && lane == 0)
-            a.prof[(size_t)a.npics * a.h * 16 + ((size_t)(p * a.h + r) * a.w + c) * PROF_MB + 6] = wall_clock64() - tdw;
+            a.prof[(size_t)a.npics * a.h * PROF_ROW + ((size_t)(p * a.h + r) * a.w + c) * PROF_MB + 6] = wall_clock64() - tdw;
         if (DEPM == DEP_COLS && CHK && c < a.w && D.n) chk_ref_rows(a, p, r * a.w + c, v0, lane, D);
         if (DEPM == DEP_ROWS && CHK && c < a.w && D.n) chk_ref_rows_rows(a, p, r * a.w + c, v0, lane, D);
         const unsigned long long tis = PROF ? wall_clock64() : 0;
@@ -2729,12 +2731,12 @@ __device__ __forceinline__ void mc_row(const ReconArgs &a, int p, int r, int c0,
         // PROF stamp [7] of the next MB: its loads' issue began (bits 0..31) / ended (32..63)
         if (PROF && c < a.w && lane == 0) {
             const unsigned long long te = wall_clock64();
-            a.prof[(size_t)a.npics * a.h * 16 + ((size_t)(p * a.h + r) * a.w + c) * PROF_MB + 7] =
+            a.prof[(size_t)a.npics * a.h * PROF_ROW + ((size_t)(p * a.h + r) * a.w + c) * PROF_MB + 7] =
                 (tis & 0xFFFFFFFFull) | (te << 32);
             // [6] with one step per launch (no dependency wait): issue phases, 16 bits each
             // (100 MHz ticks from the issue start): address set-up, luma loads, chroma loads
             if (DEPM == DEP_NONE)
-                a.prof[(size_t)a.npics * a.h * 16 + ((size_t)(p * a.h + r) * a.w + c) * PROF_MB + 6] =
+                a.prof[(size_t)a.npics * a.h * PROF_ROW + ((size_t)(p * a.h + r) * a.w + c) * PROF_MB + 6] =
                     (unsigned long long)((tsd[0] - (uint32_t)tis) & 0xFFFF) | ((unsigned long long)((tsd[1] - (uint32_t)tis) & 0xFFFF) << 16) |
                     ((unsigned long long)((tsd[2] - (uint32_t)tis) & 0xFFFF) << 32);
         }
@@ -2787,9 +2789,11 @@ struct WgppLds {
 
 // DEPM: frame-pipelined launches (two or more steps per stream), DEP_ROWS or
 // DEP_COLS (dep_wait_rows / dep_wait_cols); separate instances, so that
-// single-step launches carry none of it
+// single-step launches carry none of it.
+// The instances that exist are the rows of WGPP_VARIANTS (wgpp_variants.h);
+// engine.hip's launch table instantiates exactly those.
 template <int NMC, bool PROF, bool PREP, int RPW, bool CHK = false, int DEPM = DEP_NONE>
-__global__ __launch_bounds__(64 * (NMC + 2) * RPW)
+__global__ __launch_bounds__(wgpp_block_size(NMC, RPW))
 __attribute__((amdgpu_waves_per_eu(NMC == 3 && RPW == 1 ? WGPP_WAVES_PER_EU : NMC >= 3 || RPW > 1 ? 4 : WGPP2_WAVES_PER_EU))) void k_wgpp(ReconArgs a)
 {
     using Lay = WgppLds<NMC, RPW>;
@@ -2821,21 +2825,21 @@ __attribute__((amdgpu_waves_per_eu(NMC == 3 && RPW == 1 ? WGPP_WAVES_PER_EU : NM
         if (threadIdx.x < RK) { R[q].flag[threadIdx.x] = 0; R[q].lprog[threadIdx.x] = -1; R[q].cprog[threadIdx.x] = -1; }
         if (threadIdx.x == 0) { R[q].consumed = 0; R[q].claim = NMC + xmc; L[q].hdone = 0; L[q].copied = 0; L[q].pdone = 0; L[q].fin = 0; }
     }
-    for (int e = threadIdx.x; e < I4TAB_N; e += 64 * (NMC + 2) * RPW)
+    for (int e = threadIdx.x; e < I4TAB_N; e += wgpp_block_size(NMC, RPW))
         L[0].i4tab[e] = i4_entry((e >> 4) % 9, e & 3, (e >> 2) & 3, e >= 9 * 16);
     // frame-pipelined launches: the producers' progress cache (dep_wait)
     lds_u2 *const pc = (lds_u2 *)(__attribute__((address_space(3))) unsigned char *)(wg_lds + Lay::offX);
     if (DEPM == DEP_COLS)
-        for (int e = threadIdx.x; e < 3 * PC_ROWS; e += 64 * (NMC + 2) * RPW) pc[e] = 0ull;
+        for (int e = threadIdx.x; e < 3 * PC_ROWS; e += wgpp_block_size(NMC, RPW)) pc[e] = 0ull;
     if (RPW > 1)        // granule tags from an earlier workgroup on this CU must not match
-        for (int e = threadIdx.x; e < (RPW - 1) * a.w * 32; e += 64 * (NMC + 2) * RPW) lmbx[e] = 0;
+        for (int e = threadIdx.x; e < (RPW - 1) * a.w * 32; e += wgpp_block_size(NMC, RPW)) lmbx[e] = 0;
     __syncthreads();
     const int wid0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int q = RPW == 1 ? 0 : wid0 / (NMC + 2), wid = wid0 - q * (NMC + 2);
     const int r = g * RPW + q;
     if (r >= a.h) return;
     if (PROF && RPW == 1 && wid0 >= 1 && lane == 0)    // placement of waves 1..4 (wave 0: row_pp)
-        a.prof[((size_t)r * a.npics + p) * 16 + 11 + wid0] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);
+        a.prof[((size_t)r * a.npics + p) * PROF_ROW + 11 + wid0] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);
     const size_t W32 = (size_t)a.w * 32;
     // mailboxes: the group's first row reads the row above from L2, its last
     // row publishes there; inner boundaries use lmbx[(q - 1) * W32 ..]
@@ -2916,30 +2920,3 @@ __attribute__((amdgpu_waves_per_eu(NMC == 3 && RPW == 1 ? WGPP_WAVES_PER_EU : NM
     else if (mel) mc_row<NMC, PROF, true, true, RK, CHK, DEPM>(a, p, r, wid - 2, lane, Mw, R[q], L[0].i4tab, up, me, pc);
     else mc_row<NMC, PROF, true, false, RK, CHK, DEPM>(a, p, r, wid - 2, lane, Mw, R[q], L[0].i4tab, up, me, pc);
 }
-template __global__ void k_wgpp<3, false, true, 1>(ReconArgs);
-template __global__ void k_wgpp<3, true, true, 1>(ReconArgs);
-template __global__ void k_wgpp<3, false, true, 2>(ReconArgs);
-template __global__ void k_wgpp<3, true, true, 2>(ReconArgs);
-template __global__ void k_wgpp<3, false, true, 3>(ReconArgs);
-template __global__ void k_wgpp<2, false, true, 2>(ReconArgs);
-template __global__ void k_wgpp<2, true, true, 1>(ReconArgs);
-template __global__ void k_wgpp<3, true, true, 3>(ReconArgs);
-// intra-heavy single-step launches whose rows all fit two workgroups per CU:
-// six MC waves per row (engine launch_nmc)
-template __global__ void k_wgpp<6, false, true, 1>(ReconArgs);
-template __global__ void k_wgpp<6, true, true, 1>(ReconArgs);
-// dependency-checker instantiations (H264MI_CHECK=1)
-template __global__ void k_wgpp<3, false, true, 1, true>(ReconArgs);
-template __global__ void k_wgpp<2, false, true, 1, true>(ReconArgs);
-template __global__ void k_wgpp<3, false, true, 2, true>(ReconArgs);
-template __global__ void k_wgpp<2, false, true, 2, true>(ReconArgs);
-template __global__ void k_wgpp<3, false, true, 3, true>(ReconArgs);
-template __global__ void k_wgpp<6, false, true, 1, true>(ReconArgs);
-// frame-pipelined launches (single-row, 2 MC waves: launch_batch), by
-// dependency mode; the profiling builds for tools/prof_steps.py
-template __global__ void k_wgpp<2, false, true, 1, false, DEP_ROWS>(ReconArgs);
-template __global__ void k_wgpp<2, false, true, 1, true, DEP_ROWS>(ReconArgs);
-template __global__ void k_wgpp<2, true, true, 1, false, DEP_ROWS>(ReconArgs);
-template __global__ void k_wgpp<2, false, true, 1, false, DEP_COLS>(ReconArgs);
-template __global__ void k_wgpp<2, false, true, 1, true, DEP_COLS>(ReconArgs);
-template __global__ void k_wgpp<2, true, true, 1, false, DEP_COLS>(ReconArgs);

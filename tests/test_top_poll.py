@@ -10,7 +10,12 @@ picture of every launch is compared byte for byte with the oracle's decode
 Shapes: one MB column (the c > 0 / hdone branch never runs), one MB per row
 wave, three columns, and an odd width at which the two row waves' last MBs
 differ.  Each run decodes four streams of one size whose deblocking mix
-makes the top edge filtered for all, for none and for some MBs of a row."""
+makes the top edge filtered for all, for none and for some MBs of a row.
+
+Flavours: the plain instances, the dependency checker's (H264MI_CHECK=1) and,
+at the two larger sizes, the profiling ones (h264mi_engine_profile), which
+nothing else in the suite launches."""
+import ctypes as C
 import functools
 
 import pytest
@@ -61,23 +66,34 @@ SHAPES = {
     "pipe1_mc3": (1, None, {"H264MI_MC_WAVES": "3"}, False, 3),
     "pipe1_ionly_mc6": (1, None, {}, True, 6),
     "pipe1_rpw2": (1, None, {"H264MI_RPW": "2"}, False, None),
+    "pipe1_rpw3": (1, None, {"H264MI_RPW": "3"}, False, 3),
+    # (profiling: two rows per workgroup run the 3-wave build; the engine still reports 2)
+    "pipe1_mc2_rpw2": (1, None, {"H264MI_MC_WAVES": "2", "H264MI_RPW": "2"}, False, 2),
     "pipe3_rows": (3, "rows", {}, False, 2),
     "pipe3_cols": (3, "cols", {}, False, 2),
 }
 
 
-@pytest.mark.parametrize("check", [False, True], ids=["plain", "check"])
-@pytest.mark.parametrize("shape", sorted(SHAPES))
-@pytest.mark.parametrize("wh", SIZES, ids=lambda wh: f"{wh[0]}x{wh[1]}")
-def test_top_halo_poll_vs_oracle(wh, shape, check, monkeypatch):
+# profiling at the sizes whose five rows leave a partial last group at 2 and 3
+# rows per workgroup, and more than one MB per row wave
+PROF_SIZES = [(3, 5), (13, 9)]
+CASES = [(wh, shape, flavour) for wh in SIZES for shape in sorted(SHAPES) for flavour in ("plain", "check", "prof")
+         if flavour != "prof" or wh in PROF_SIZES]
+
+
+@pytest.mark.parametrize("wh,shape,flavour", CASES, ids=[f"{wh[0]}x{wh[1]}-{shape}-{fl}" for wh, shape, fl in CASES])
+def test_top_halo_poll_vs_oracle(wh, shape, flavour, monkeypatch):
     """Nine pictures of four streams (top edge filtered for all / none / some
     MBs of a row), one or three pictures of each per launch, so that several
     launches reuse the mailboxes under new epochs; rows or (row, column)
     dependencies between the pictures of a launch; 2, 3 and 6 MC waves per row
-    workgroup, two rows per workgroup (the LDS mailbox); each also through
-    the dependency-checker instances (H264MI_CHECK=1)."""
+    workgroup, two and three rows per workgroup (the LDS mailboxes); each also
+    through the dependency-checker instances (H264MI_CHECK=1) and, switched on
+    once the run is set up, the profiling instances, whose row-start stamp of
+    row 0 of picture 0 shows that one ran."""
     import bench
     pipe, mode, env, ionly, nmc = SHAPES[shape]
+    check, prof = flavour == "check", flavour == "prof"
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     if mode:
@@ -94,6 +110,8 @@ def test_top_halo_poll_vs_oracle(wh, shape, check, monkeypatch):
     assert n == NFRAMES
     run = bench.DeviceRun(_lib.mi(), caps, 0, n, pipe)
     try:
+        if prof:
+            assert run.eng._L.h264mi_engine_profile(run.eng._h, 1, None, 0) == 0
         assert run.P == pipe
         assert len(run.launches) >= 3
         for i, launch in enumerate(run.launches):
@@ -110,6 +128,11 @@ def test_top_halo_poll_vs_oracle(wh, shape, check, monkeypatch):
         if check:
             assert run.eng.kernel_name() == "k_wgpp_check"
             assert run.eng.error_bits() == 0
+        elif prof:
+            assert run.eng.kernel_name() == ("k_wgpp_prof" if pipe > 1 else "k_wgpp")
+            rec = (C.c_uint64 * 16)()
+            assert run.eng._L.h264mi_engine_profile(run.eng._h, 1, rec, len(rec)) == 0
+            assert rec[0] != 0
         else:
             assert run.eng.kernel_name() == "k_wgpp"
         assert run.eng.errors() == 0
