@@ -21,6 +21,7 @@
 #include <stdint.h>
 #include "../../../include/h264mi_records.h"
 #include "wgpp_variants.h"
+#include "deblock_lanes.h"
 
 #define WAVE 64
 // profiling build: u64 stamps per MB (row waves [0..2], MC [3], intra [4..5])
@@ -997,8 +998,8 @@ __device__ __forceinline__ void intra_tile(int mbtype, int avail, int pred, uint
 
 __device__ __forceinline__ int absd(int a, int b) { return (int)__builtin_amdgcn_sad_u8((unsigned)a, (unsigned)b, 0u); }
 
-// one sample line across edge k (p3..q3 = v[4k..4k+7]); chroma lines only
-// use p1..q1.  filterSamples / bS<4 / bS==4 of deblocking.c:1543-1736.  The
+// one sample line across an edge (p3..q3); chroma lines only use p1..q1.
+// filterSamples / bS<4 / bS==4 of deblocking.c:1543-1736.  The
 // bS==4 arithmetic runs only when some lane of the wave has bS==4 on this
 // edge (wave-uniform branch); everything else is select-based.
 // keep a value computed where it stands: the filter updates below are cheap
@@ -1018,18 +1019,22 @@ __device__ __forceinline__ int mad_m2(int x, int c)
     return r;
 }
 
-// One edge of one line (8.7.2.3 / 8.7.2.4).  Per-lane constants: alpha,
-// beta; beta_ap = beta for luma, 0 for chroma (so a_p / a_q are false and
-// the p1 / q1 updates off); tcs = tc0 by bS in bytes 1..3 (+1 for chroma,
+// One edge of one line (8.7.2.3 / 8.7.2.4), v = p3..q3.  Per-lane constants:
+// alpha, beta; beta_ap = beta for luma, 0 for chroma (so a_p / a_q are false
+// and the p1 / q1 updates off); tcs = tc0 by bS in bytes 1..3 (+1 for chroma,
 // where tc = tc0 + 1), byte 0 = 0.  MBEDGE: the MB edge, the only one that
-// can carry bS = 4.
-template <bool MBEDGE>
-__device__ __forceinline__ void filt_line(int (&v)[20], const int k, const int bS, const int alpha, const int beta,
-                                          const int beta_ap, const uint32_t tcs)
+// can carry bS = 4; it reads p3 and q3 and can change p2..q2, an internal
+// edge (bS < 4) reads p2..q2 and changes p1..q1.
+// The q1 result does not depend on p2, so it comes first and p2 is taken
+// through p2of(v[1], q1 result): the line's own sample (OwnP2), or the q1
+// the lane of the edge before has just computed (QuadP2, deblock_dir step B).
+struct OwnP2 { __device__ __forceinline__ int operator()(int p2, int) const { return p2; } };
+template <bool MBEDGE, class P2 = OwnP2>
+__device__ __forceinline__ void filt_line(int (&v)[8], const int bS, const int alpha, const int beta,
+                                          const int beta_ap, const uint32_t tcs, const P2 &p2of = P2())
 {
-    const int o = 4 * k;
-    const int p2 = v[o + 1], p1 = v[o + 2], p0 = v[o + 3];
-    const int q0 = v[o + 4], q1 = v[o + 5], q2 = v[o + 6];
+    const int p1 = v[2], p0 = v[3];
+    const int q0 = v[4], q1 = v[5], q2 = v[6];
     const int d0 = absd(p0, q0);
     // filterSamples as one sign test: v_sad_u8 subtracts each threshold in
     // its addend, one v_max3 joins the three
@@ -1043,27 +1048,31 @@ __device__ __forceinline__ void filt_line(int (&v)[20], const int k, const int b
 #else
     const bool f = bS != 0 && max(m0, max(m1, m2)) < 0;
 #endif
-    const bool ap = absd(p2, p0) < beta_ap, aq = absd(q2, q0) < beta_ap;
+    const bool aq = absd(q2, q0) < beta_ap;
     // bS < 4
     const int tc0 = (int)__builtin_amdgcn_ubfe(tcs, (uint32_t)bS << 3, 8);    // bS = 4: offset 32 -> byte 0 (unused)
-    const int tc = tc0 + (int)ap + (int)aq;
-    const int d = med3i((((q0 - p0) << 2) + (p1 - q1) + 4) >> 3, -tc, tc);
     const int avg = (int)__builtin_amdgcn_lerp((uint32_t)p0, (uint32_t)q0, 1u);    // (p0 + q0 + 1) >> 1 (v_lerp_u8)
     const int ntc0 = -tc0;
-    int n_p1 = p1 + med3i((mad_m2(p1, p2) + avg) >> 1, ntc0, tc0);
     int n_q1 = q1 + med3i((mad_m2(q1, q2) + avg) >> 1, ntc0, tc0);
+    MATERIALIZE(n_q1);
+    int r_q1 = f && aq ? n_q1 : q1;
+    // the one value that crosses from edge to edge
+    const int p2 = p2of(v[1], r_q1);
+    const bool ap = absd(p2, p0) < beta_ap;
+    const int tc = tc0 + (int)ap + (int)aq;
+    const int d = med3i((((q0 - p0) << 2) + (p1 - q1) + 4) >> 3, -tc, tc);
+    int n_p1 = p1 + med3i((mad_m2(p1, p2) + avg) >> 1, ntc0, tc0);
     int n_p0 = clip255(p0 + d), n_q0 = clip255(q0 - d);
-    MATERIALIZE(n_p1); MATERIALIZE(n_q1); MATERIALIZE(n_p0); MATERIALIZE(n_q0);
+    MATERIALIZE(n_p1); MATERIALIZE(n_p0); MATERIALIZE(n_q0);
     int r_p2 = p2, r_q2 = q2;
     int r_p1 = f && ap ? n_p1 : p1;
-    int r_q1 = f && aq ? n_q1 : q1;
     int r_p0 = f ? n_p0 : p0;
     int r_q0 = f ? n_q0 : q0;
     if (MBEDGE) {
         // bS == 4: MB edges next to intra MBs only -- skipped unless some lane needs it
         const bool b4 = f & (bS >= 4);
         if (__builtin_amdgcn_ballot_w64(b4) != 0) {
-            const int p3 = v[o], q3 = v[o + 7];
+            const int p3 = v[0], q3 = v[7];
             const bool strong = d0 < ((alpha >> 2) + 2);
             const bool sp = ap && strong, sq = aq && strong;
             int s_p0 = (p2 + 2 * p1 + 2 * p0 + 2 * q0 + q1 + 4) >> 3, w_p0 = (2 * p1 + p0 + q1 + 2) >> 2;
@@ -1080,121 +1089,141 @@ __device__ __forceinline__ void filt_line(int (&v)[20], const int k, const int b
             r_q2 = b4 && sq ? s_q2 : r_q2;
         }
     }
-    v[o + 1] = r_p2; v[o + 2] = r_p1; v[o + 3] = r_p0;
-    v[o + 4] = r_q0; v[o + 5] = r_q1; v[o + 6] = r_q2;
+    v[1] = r_p2; v[2] = r_p1; v[3] = r_p0;
+    v[4] = r_q0; v[5] = r_q1; v[6] = r_q2;
 }
 
-// all edges of one direction: lanes 0..15 = luma lines, 16..31 = chroma
-// lines (comp = bit 3, index = bits 0..2).  dir 0: lines are rows, edges are
-// the 4 (chroma 2) vertical edges, left to right; dir 1: columns / horizontal
-// edges, top to bottom.  Each lane owns its line for all edges of the
-// direction, so no cross-lane ordering is needed inside a direction.  Lanes
-// 32..63 mirror lanes 0..31 (same addresses, same values) so that every
-// access is unconditional.
-struct NoMid { __device__ __forceinline__ void operator()() const {} };
-// Mid (dir 0): called once the MB edge (edge 0) is filtered and its samples
-// (region cols -4..-1, the left MB's cols 12..15, now final) are written back
-// -- the row hand-off publishes from there without waiting for the internal
-// edges (edges 1..3 touch only this MB's columns 1..14)
-// One pass's per-line filter parameters, from the MB's deblocking record:
-// this line's four bS nibbles (chroma: its edges 0, 1 sit on luma edges 0,
-// 2) and the two threshold sets {alpha, beta, tc0(bS 1..3)} of the MB edge
-// and the internal edges.  They depend on nothing the chain produces, so the
-// row waves compute them off the chain (before the hdone / top waits).
+// All edges of one direction in two steps on the lane map of deblock_lanes.h
+// (lane = 4 * q + e: chroma line q for e = 0, luma line q for e = 1..3).
+// dir 0: lines are rows, edges are the 4 (chroma 2) vertical edges; dir 1:
+// columns / horizontal edges.
+//   step A  the MB edge of every line (e = 0, 1; e = 2, 3 repeat e = 1 and
+//           store into their junk slot)
+//   step B  the internal edges, one per lane: each lane computes its q1,
+//           hands it to the lane of the next edge as that edge's p2 (one
+//           quad_perm DPP move) and finishes.  The lanes of edge 1 take
+//           p2..p0 from what they held after step A.
+// Every lane loads what both of its steps read before step A runs: step A
+// changes nothing another lane's step B reads.
+//
+// One pass's per-lane filter parameters, from the MB's deblocking record: the
+// bS of the lane's edge in each step (a chroma line's edges 0, 1 sit on luma
+// edges 0, 2) and the threshold sets {alpha, beta, tc0(bS 1..3)} of the MB
+// edge (step A) and the internal edges (step B).  They depend on nothing the
+// chain produces, so the row waves compute them off the chain (before the
+// hdone / top waits).
 struct DbPar {
-    uint32_t bsw, tcs_e, tcs_i;
-    int alpha_e, beta_e, alpha_i, beta_i;
+    int bs_a, bs_b;
+    uint32_t tcs_a, tcs_b;
+    int alpha_a, beta_a, bap_a, alpha_b, beta_b, bap_b;
 };
 __device__ __forceinline__ DbPar dbpar(const int dir, const uint8_t *db, int lane, bool mb_edge_on)
 {
-    const int li = lane & 31;
-    const bool chroma = li >= 16;
-    const int idx = chroma ? (li & 7) : (li & 15);
-    const int seg = chroma ? idx >> 1 : idx >> 2;
+    const bool chroma = dbl_chroma(lane);
     DbPar P;
-    uint32_t bsw = *(const uint16_t *)(db + dir * 8 + seg * 2);
-    if (chroma) bsw = (bsw & 15) | ((bsw >> 4) & 0xF0);
-    if (!mb_edge_on) bsw &= ~15u;
-    P.bsw = bsw;
+    const uint32_t bsw = *(const uint16_t *)(db + dir * 8 + dbl_bs_seg(lane) * 2);
+    P.bs_a = mb_edge_on ? (int)((bsw >> (4 * dbl_bs_nibble(DBL_STEP_A, lane))) & 15) : 0;
+    P.bs_b = (int)((bsw >> (4 * dbl_bs_nibble(DBL_STEP_B, lane))) & 15);
     const uint8_t *pe = db + 16 + ((chroma ? 3 : 0) + 1 + dir) * 8;    // MB edge class
     const uint8_t *pi = db + 16 + (chroma ? 3 : 0) * 8;                  // internal class
     const uint2 te = *(const uint2 *)pe, ti = *(const uint2 *)pi;
     const uint32_t cplus = chroma ? 0x01010100u : 0u;
-    P.alpha_e = te.x & 255; P.beta_e = (te.x >> 8) & 255; P.alpha_i = ti.x & 255; P.beta_i = (ti.x >> 8) & 255;
-    P.tcs_e = (((te.x >> 8) & 0xFFFF00u) | (te.y << 24)) + cplus;
-    P.tcs_i = (((ti.x >> 8) & 0xFFFF00u) | (ti.y << 24)) + cplus;
+    P.alpha_a = te.x & 255; P.beta_a = (te.x >> 8) & 255; P.alpha_b = ti.x & 255; P.beta_b = (ti.x >> 8) & 255;
+    P.bap_a = chroma ? 0 : P.beta_a; P.bap_b = chroma ? 0 : P.beta_b;
+    P.tcs_a = (((te.x >> 8) & 0xFFFF00u) | (te.y << 24)) + cplus;
+    P.tcs_b = (((ti.x >> 8) & 0xFFFF00u) | (ti.y << 24)) + cplus;
     return P;
 }
 
-// pre (dir 0): the line's columns 0..15 (dwords 1..4 of its region row),
-// read off the chain; only the left halo (dword 0) is read here
+// step B's p2: lanes of edge 1 (and chroma) keep the sample step A left, the
+// others take the q1 of the lane before them in the quad
+// (constructed where it is used, QuadP2{from_a}: handed through a function
+// that returns it, the object went to scratch memory in every k_wgpp instance
+// -- 16 B per lane, and the whole gain of the two-step pass with it)
+struct QuadP2 {
+    bool from_a;
+    __device__ __forceinline__ int operator()(int p2, int q1) const
+    {
+        const int x = __builtin_amdgcn_mov_dpp(q1, DBL_P2_QUAD_PERM, 0xF, 0xF, true);
+        return from_a ? p2 : x;
+    }
+};
+
+// byte offset of the lane's line (dir 0: its region row) in its plane
+__device__ __forceinline__ int db_row_off(int lane) { return (dbl_line(lane) + (dbl_chroma(lane) ? 2 : 4)) * RY_S; }
+
+// pre (dir 0): dwords 1, k and k + 1 of the lane's region row (k: its step B
+// edge), the MB's own columns, read off the chain; only the left halo (dword
+// 0) is read here
 // use_halo (dir 0): the line's left halo (dword 0) is `halo`, already in a
 // register (passed by value: a pointer chosen at run time would put it in
 // scratch memory)
-template <class Mid = NoMid>
 __device__ __forceinline__ void deblock_dir(const int dir, const DbPar &P, uint8_t *ry, uint8_t *ru, uint8_t *rv,
                                             uint8_t *junk, int lane, const uint32_t *pre = nullptr,
-                                            bool use_halo = false, uint32_t halo = 0, const Mid &mid = Mid())
+                                            bool use_halo = false, uint32_t halo = 0)
 {
-    const int li = lane & 31;
-    const bool chroma = li >= 16;
-    const int idx = chroma ? (li & 7) : (li & 15);
-    uint8_t *D = chroma ? ((li & 8) ? rv : ru) : ry;
-    const uint32_t bsw = P.bsw, tcs_e = P.tcs_e, tcs_i = P.tcs_i;
-    const int alpha_e = P.alpha_e, beta_e = P.beta_e, alpha_i = P.alpha_i, beta_i = P.beta_i;
+    const bool chroma = dbl_chroma(lane);
+    const int pl = dbl_plane(lane), idx = dbl_line(lane), kb = dbl_edge(DBL_STEP_B, lane);
+    uint8_t *D = pl == DBL_LUMA ? ry : pl == DBL_CB ? ru : rv;
+    const bool st_a = dbl_stores(DBL_STEP_A, lane), from_a = dbl_b_from_a(lane);
+    uint8_t *jk = junk + lane * 4;
     // one stride for both planes (RC_S == RY_S): every access below is
-    // base + immediate.  Chroma lines read past their 12/10 samples into
-    // neighbouring LDS (values unused) and write back only what they own.
+    // base + immediate.  Chroma lines read past the samples they use into
+    // neighbouring LDS (values unused) and write back only what the map says.
     static_assert(RC_S == RY_S, "deblock_dir assumes one region stride");
-    int v[20];
+    // the map's sample windows, as the loads and stores below spell them out
+    static_assert(dbl_load_first(DBL_STEP_A, 0) == 0 && dbl_load_count(DBL_STEP_A) == 8, "a[j] = sample j");
+    static_assert(dbl_load_first(DBL_STEP_B, 0) == 1 && dbl_load_count(DBL_STEP_B) == 6, "b[j] = sample 4k + j, j = 1..6");
+    static_assert(dbl_store_first(0, DBL_STEP_A, false, 0) == 0 && dbl_store_count(0, DBL_STEP_A, false) == 8 &&
+                  dbl_store_first(0, DBL_STEP_A, true, 0) == 0 && dbl_store_count(0, DBL_STEP_A, true) == 8, "dir 0 step A: dwords 0, 1");
+    static_assert(dbl_store_first(1, DBL_STEP_A, false, 0) == 1 && dbl_store_count(1, DBL_STEP_A, false) == 6 &&
+                  dbl_store_first(1, DBL_STEP_A, true, 0) == 3 && dbl_store_count(1, DBL_STEP_A, true) == 2, "dir 1 step A: a[1..6], chroma a[3..4]");
+    static_assert(dbl_store_first(0, DBL_STEP_B, false, 0) == 2 && dbl_store_count(0, DBL_STEP_B, false) == 4 &&
+                  dbl_store_first(1, DBL_STEP_B, true, 0) == 2 && dbl_store_count(1, DBL_STEP_B, true) == 4, "step B: b[2..5]");
+    uint8_t *const row = D + db_row_off(lane);                            // dir 0
+    uint8_t *const col = D + idx + 4 - (chroma ? 2 * RY_S : 0);           // dir 1: col[j * RY_S] = sample j
+    uint8_t *const colb = col + 4 * kb * RY_S;
+    int a[8], b[8];
+    b[0] = b[7] = 0;
     if (dir == 0) {
-        const uint32_t *row = (const uint32_t *)(D + (idx + (chroma ? 2 : 4)) * RY_S);
-#pragma unroll
-        for (int j = 0; j < 5; j++) {
-            const uint32_t w = (pre && j > 0) ? pre[j - 1] : (j == 0 && use_halo) ? halo : row[j];
-            v[4 * j] = w & 255; v[4 * j + 1] = (w >> 8) & 255; v[4 * j + 2] = (w >> 16) & 255; v[4 * j + 3] = w >> 24;
-        }
+        const uint32_t *rw = (const uint32_t *)row;
+        const uint32_t w0 = use_halo ? halo : rw[0], w1 = pre ? pre[0] : rw[1];
+        const uint32_t wk = pre ? pre[1] : rw[kb], wk1 = pre ? pre[2] : rw[kb + 1];
+        a[0] = w0 & 255; a[1] = (w0 >> 8) & 255; a[2] = (w0 >> 16) & 255; a[3] = w0 >> 24;
+        a[4] = w1 & 255; a[5] = (w1 >> 8) & 255; a[6] = (w1 >> 16) & 255; a[7] = w1 >> 24;
+        b[1] = (wk >> 8) & 255; b[2] = (wk >> 16) & 255; b[3] = wk >> 24;
+        b[4] = wk1 & 255; b[5] = (wk1 >> 8) & 255; b[6] = (wk1 >> 16) & 255;
     } else {
-        // v[j] = sample row j-4 of this column (chroma region row 0 = sample row -2)
-        const uint8_t *col = D + idx + 4 - (chroma ? 2 * RY_S : 0);
 #pragma unroll
-        for (int j = 0; j < 20; j++) v[j] = col[j * RY_S];
+        for (int j = 0; j < 8; j++) a[j] = col[j * RY_S];
+#pragma unroll
+        for (int j = 1; j < 7; j++) b[j] = colb[j * RY_S];
     }
-    {
-        const int b = (int)(bsw & 15);
-        if (__builtin_amdgcn_ballot_w64(b != 0) != 0)     // wave-uniform skip
-            filt_line<true>(v, 0, b, alpha_e, beta_e, chroma ? 0 : beta_e, tcs_e);
-    }
+    // ---- step A
+    if (__builtin_amdgcn_ballot_w64(P.bs_a != 0) != 0)     // wave-uniform skip
+        filt_line<true>(a, P.bs_a, P.alpha_a, P.beta_a, P.bap_a, P.tcs_a);
+    // write-back without divergence: what a lane does not store goes to its
+    // junk slot.  dir 0: the halo dword first (cols -4..-1, final from here)
     if (dir == 0) {
-        // cols -4..-1 are final after the MB edge: write them back now, then
-        // let the caller publish
-        uint32_t *row = (uint32_t *)(D + (idx + (chroma ? 2 : 4)) * RY_S);
-        row[0] = (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
+        *(uint32_t *)(st_a ? row : jk) = (uint32_t)a[0] | ((uint32_t)a[1] << 8) | ((uint32_t)a[2] << 16) | ((uint32_t)a[3] << 24);
+        *(uint32_t *)(st_a ? row + 4 : jk) = (uint32_t)a[4] | ((uint32_t)a[5] << 8) | ((uint32_t)a[6] << 16) | ((uint32_t)a[7] << 24);
+    } else {
+#pragma unroll
+        for (int j = 1; j < 7; j++)
+            *((st_a && (!chroma || j == 3 || j == 4)) ? col + j * RY_S : jk) = (uint8_t)a[j];
+    }
+    wave_sync();
+    // ---- step B
+    if (__builtin_amdgcn_ballot_w64(P.bs_b != 0) == 0) return;
+    b[1] = from_a ? a[5] : b[1]; b[2] = from_a ? a[6] : b[2]; b[3] = from_a ? a[7] : b[3];
+    filt_line<false>(b, P.bs_b, P.alpha_b, P.beta_b, P.bap_b, P.tcs_b, QuadP2{from_a});
+    if (dir == 0) {
+        *(uint16_t *)(row + 4 * kb + 2) = (uint16_t)(b[2] | (b[3] << 8));
+        *(uint16_t *)(row + 4 * kb + 4) = (uint16_t)(b[4] | (b[5] << 8));
         wave_sync();
-        mid();
-    }
-#pragma unroll
-    for (int k = 1; k < 4; k++) {
-        const int b = (int)((bsw >> (4 * k)) & 15);
-        if (__builtin_amdgcn_ballot_w64(b != 0) == 0) continue;
-        filt_line<false>(v, k, b, alpha_i, beta_i, chroma ? 0 : beta_i, tcs_i);
-    }
-    // write-back without divergence: samples a lane does not own go to its
-    // junk slot; lanes 32..63 store exactly what lanes 0..31 store
-    if (dir == 0) {
-        uint32_t *row = (uint32_t *)(D + (idx + (chroma ? 2 : 4)) * RY_S);
-        uint32_t *jk = (uint32_t *)(junk + lane * 4);
-#pragma unroll
-        for (int j = 1; j < 5; j++) {
-            const uint32_t w = (uint32_t)v[4 * j] | ((uint32_t)v[4 * j + 1] << 8) | ((uint32_t)v[4 * j + 2] << 16) | ((uint32_t)v[4 * j + 3] << 24);
-            *((!chroma || j < 3) ? row + j : jk) = w;
-        }
     } else {
-        uint8_t *col = D + idx + 4 - (chroma ? 2 * RY_S : 0);
-        uint8_t *jk = junk + lane * 4;
 #pragma unroll
-        for (int j = 1; j < 19; j++)
-            *((!chroma || j == 3 || j == 4 || j == 7 || j == 8) ? col + j * RY_S : jk) = (uint8_t)v[j];
+        for (int j = 2; j < 6; j++) colb[j * RY_S] = (uint8_t)b[j];
     }
 }
 
@@ -1603,19 +1632,19 @@ __device__ void row_pp(const ReconArgs &a, int p, int r, PPLds &L, const int w, 
         sb_left = k >= 12 && k < 24;
         sb_top = k >= 24;
     }
-    // left-halo copy from the partner's region: lanes 0..15 luma rows, 16..31
-    // chroma rows (cols 12..15 / 4..7 -> -4..-1); lanes 32..63 into junk
-    // (lanes 32..63 read what lanes 0..31 read -- the vertical pass takes
-    // the copied dword as its line's halo, and its lanes 32..63 mirror)
+    // left-halo copy from the partner's region: every lane the row of its
+    // vertical-pass line (deblock_lanes.h; cols 12..15 / 4..7 -> -4..-1) --
+    // the vertical pass takes the copied dword as its line's halo.  The lanes
+    // that store nothing in the pass's step A read what their quad's luma
+    // lane reads and copy into junk.
     uint32_t cp_src, cp_dst;
     {
-        int off, step;
-        const uint8_t *D;
-        const int cl = lane & 31;
-        if (cl < 16) { D = Gp.ry; off = (cl + 4) * RY_S; step = 16; }
-        else { const int k = cl - 16; D = (k >> 3) ? Gp.rv : Gp.ru; off = ((k & 7) + 2) * RC_S; step = 8; }
+        const int pl = dbl_plane(lane);
+        const uint8_t *D = pl == DBL_LUMA ? Gp.ry : pl == DBL_CB ? Gp.ru : Gp.rv;
+        const int off = db_row_off(lane), step = pl == DBL_LUMA ? 16 : 8;
         cp_src = (uint32_t)((int)(D - (const uint8_t *)&Gp) + off + step);
-        cp_dst = lane < 32 ? (uint32_t)((int)(D - (const uint8_t *)&Gp) + off) : (uint32_t)((int)(junk - Lb) + lane * 4);
+        cp_dst = dbl_stores(DBL_STEP_A, lane) ? (uint32_t)((int)(D - (const uint8_t *)&Gp) + off)
+                                              : (uint32_t)((int)(junk - Lb) + lane * 4);
     }
     // publishing: slot ls = le (0..23; lanes 24..63 repeat slots 16..23 /
     // 0..23 with the same values) stores granule gi(ls).  Slots 0..7 are the
@@ -1665,13 +1694,14 @@ __device__ void row_pp(const ReconArgs &a, int p, int r, PPLds &L, const int w, 
         pq_off = !pchroma ? (12 + pj) * 16 : 256 + comp * 64 + (6 + row) * 8;
     }
     const bool is_patch = le < 8;
-    // the vertical pass's line in the region (deblock_dir dir 0): luma rows
-    // for lanes 0..15, Cb / Cr rows for 16..31 (32..63 mirror)
+    // the vertical pass's line in the region (deblock_dir dir 0, the lane map
+    // of deblock_lanes.h) and the lane's step B edge
     uint32_t vrow_lds;
+    const int vkb = dbl_edge(DBL_STEP_B, lane);
     {
-        const int vl = lane & 31, vch = vl >= 16, vidx = vch ? (vl & 7) : (vl & 15);
-        const uint8_t *D = vch ? ((vl & 8) ? G.rv : G.ru) : G.ry;
-        vrow_lds = (uint32_t)((int)(D - Lb) + (vidx + (vch ? 2 : 4)) * RY_S);
+        const int pl = dbl_plane(lane);
+        const uint8_t *D = pl == DBL_LUMA ? G.ry : pl == DBL_CB ? G.ru : G.rv;
+        vrow_lds = (uint32_t)((int)(D - Lb) + db_row_off(lane));
     }
     // own samples from the ring slot: luma all lanes, chroma lanes 0..31
     const uint32_t own_y_lds = (uint32_t)((int)(G.ry - Lb) + (orow + 4) * RY_S + 4 + oq * 4);
@@ -1773,13 +1803,13 @@ __device__ void row_pp(const ReconArgs &a, int p, int r, PPLds &L, const int w, 
         wave_sync();
         const DbPar Pv = dbpar(0, G.db, lane, avail & DB_LEFT);
         const DbPar Ph = dbpar(1, G.db, lane, avail & DB_TOP);
-        // the vertical pass's own columns 0..15 of the lane's line (only its
+        // the vertical pass's own columns of the lane's line: dword 1 for the
+        // MB edge, dwords k and k + 1 for the lane's internal edge (only the
         // left halo arrives on the chain)
-        uint32_t vpre[4];
+        uint32_t vpre[3];
         {
             const uint32_t *row = (const uint32_t *)(Lb + vrow_lds);
-#pragma unroll
-            for (int j = 0; j < 4; j++) vpre[j] = row[1 + j];
+            vpre[0] = row[1]; vpre[1] = row[vkb]; vpre[2] = row[vkb + 1];
         }
         // the hand-off patch's inputs (below): MB c+1's unfiltered columns
         // 0..3 and its left-edge bS / thresholds, from its ring slot -- its MC
@@ -1913,12 +1943,10 @@ __device__ void row_pp(const ReconArgs &a, int p, int r, PPLds &L, const int w, 
                 if (CHK && __builtin_amdgcn_readfirstlane(*(const uint16_t *)&R->db[s1][CHK_TAG_OFF]) != c + 1 && lane == 0)
                     atomicOr(perr, CHK_RING);
                 const uint32_t pdw = ent;
-                int v[20];
+                int v[8];
 #pragma unroll
                 for (int x = 0; x < 4; x++) { v[x] = (pdw >> (8 * x)) & 255; v[4 + x] = (p_q >> (8 * x)) & 255; }
-#pragma unroll
-                for (int x = 8; x < 20; x++) v[x] = 0;
-                filt_line<true>(v, 0, p_bS, p_alpha, p_beta, pchroma ? 0 : p_beta, p_tcs);
+                filt_line<true>(v, p_bS, p_alpha, p_beta, pchroma ? 0 : p_beta, p_tcs);
                 const uint32_t newp = (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
                 if (is_patch) ent = newp;
             }

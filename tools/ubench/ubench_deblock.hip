@@ -1,7 +1,7 @@
 // Micro-benchmark (diagnostics only): shader cycles of one lone wave's
 // deblocking passes, deblock_dir() of recon_kernels.hip on a PPRegion in LDS
 // filled with pseudo-random samples, and of the bare filter arithmetic
-// (filt_line on registers, 4 edges), per bS mode:
+// (filt_line on registers, the pass's two steps), per bS mode:
 //   0: MB edge bS 2, internal edges 0      (skip-like P MBs)
 //   1: every edge bS 2                     (coded P MBs)
 //   2: MB edge bS 4, internal edges 3      (intra MBs)
@@ -39,23 +39,25 @@ __global__ __launch_bounds__(64) void k_ub(unsigned long long *out, int iters, i
     unsigned long long t2 = clock64();
     // the row hand-off patch's arithmetic: one MB-edge step of one line
     // (row_pp applies it to MB c's rows 12..15 before publishing them)
-    int pv[20];
-    for (int j = 0; j < 20; j++) pv[j] = 100 + ((lane * 5 + j * 11) & 15);
+    int pv[8];
+    for (int j = 0; j < 8; j++) pv[j] = 100 + ((lane * 5 + j * 11) & 15);
     const int pbS = bsmode == 2 ? 4 : 2;
     unsigned long long tp0 = clock64();
-    for (int it = 0; it < iters; it++) filt_line<true>(pv, 0, pbS, 40, 10, 10, 0x03020100u);
+    for (int it = 0; it < iters; it++) filt_line<true>(pv, pbS, 40, 10, 10, 0x03020100u);
     unsigned long long tp1 = clock64();
-    // the filter arithmetic alone: 4 dependent edges on a register line
-    int v[20];
-    for (int j = 0; j < 20; j++) v[j] = 100 + ((lane * 7 + j * 13) & 15);
+    // the filter arithmetic alone, the two steps of a pass on registers: the
+    // MB edge, then one internal edge per lane with the quad hand-over
+    int v[8], vb[8];
+    for (int j = 0; j < 8; j++) { v[j] = 100 + ((lane * 7 + j * 13) & 15); vb[j] = 100 + ((lane * 3 + j * 5) & 15); }
     const int bS0 = bsmode == 2 ? 4 : 2, bSi = bsmode == 0 ? 0 : bsmode == 1 ? 2 : 3;
     for (int it = 0; it < iters; it++) {
-        filt_line<true>(v, 0, bS0, 40, 10, 10, 0x03020100u);
-        for (int k = 1; k < 4; k++) filt_line<false>(v, k, bSi, 40, 10, 10, 0x03020100u);
+        filt_line<true>(v, bS0, 40, 10, 10, 0x03020100u);
+        vb[1] = v[5]; vb[2] = v[6]; vb[3] = v[7];
+        filt_line<false>(vb, bSi, 40, 10, 10, 0x03020100u, QuadP2{dbl_b_from_a(lane)});
     }
     unsigned long long t3 = clock64();
     int acc = 0;
-    for (int j = 0; j < 20; j++) acc += v[j] + pv[j];
+    for (int j = 0; j < 8; j++) acc += v[j] + vb[j] + pv[j];
     if (lane == 0) {
         out[0] = (t1 - t0) / iters; out[1] = (t2 - t1) / iters; out[2] = (t3 - t2) / iters;
         out[3] = G.ry[100] + acc;
@@ -196,7 +198,7 @@ int main()
         unsigned long long hh[5];
         hipLaunchKernelGGL(k_ub, dim3(1), dim3(64), 0, 0, d, 2000, mode);
         (void)hipMemcpy(hh, d, 40, hipMemcpyDeviceToHost);
-        printf("bsmode %d: V %llu cycles (%.3f us), H %llu cycles (%.3f us), filt x4 %llu cycles, patch edge %llu cycles\n", mode,
+        printf("bsmode %d: V %llu cycles (%.3f us), H %llu cycles (%.3f us), filt A+B %llu cycles, patch edge %llu cycles\n", mode,
                hh[0], hh[0] / mhz, hh[1], hh[1] / mhz, hh[2], hh[4]);
         if (mode == 1) { vh_us = (hh[0] + hh[1]) / mhz; patch_us = hh[4] / mhz; }
     }
