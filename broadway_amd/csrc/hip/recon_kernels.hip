@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../../include/h264mi_records.h"
+#include "../common/mc_window.h"
 #include "wgpp_variants.h"
 #include "deblock_lanes.h"
 
@@ -122,7 +123,7 @@ struct ReconArgs {
 #endif
 #define PROG_AT(base, pic, h, r, w) ((base) + (((size_t)(pic) * (h) + (r)) * 2 + (w)) * PROG_STRIDE)
 // DEP_COLS finality rule, the one place it is stated (dep_rows_ok waits on
-// it, chk_access checks the loads against it).  It follows row_pp's store
+// it, chk_ref_rows checks the loads against it).  It follows row_pp's store
 // map: MB x of row R is final once row R has stored MBs 0..x + DEPC_SAME_ROW - 1
 // (MB x + 1 stores MB x's columns 12..15 after its left edge) and row R + 1
 // MBs 0..x + DEPC_ROW_BELOW - 1 (MB (R + 1, x) stores row R's rows 12..15
@@ -232,8 +233,8 @@ __device__ __forceinline__ void drain_vm() { asm volatile("s_waitcnt vmcnt(0)" :
 
 __device__ __forceinline__ int clip255(int v) { return min(max(v, 0), 255); }
 __device__ __forceinline__ int clip3(int lo, int hi, int v) { return min(max(v, lo), hi); }
-__device__ __forceinline__ int blk_x(int b) { return ((b >> 2) & 1) * 2 + (b & 1); }
-__device__ __forceinline__ int blk_y(int b) { return ((b >> 3) & 1) * 2 + ((b >> 1) & 1); }
+__device__ __forceinline__ int blk_x(int b) { return mcw_blk_x(b); }
+__device__ __forceinline__ int blk_y(int b) { return mcw_blk_y(b); }
 __device__ __forceinline__ int blk_of(int x4, int y4) { return ((y4 >> 1) * 2 + (x4 >> 1)) * 4 + (y4 & 1) * 2 + (x4 & 1); }
 
 // ---------------------------------------------------------------------------
@@ -2047,6 +2048,11 @@ typedef uint32_t u32x3a4 __attribute__((ext_vector_type(3), aligned(4)));
 typedef uint32_t u32x2a4 __attribute__((ext_vector_type(2), aligned(4)));
 __device__ __forceinline__ uint32_t rec_dw(uint32_t v0, int i) { return (uint32_t)__builtin_amdgcn_readlane((int)v0, i); }
 
+// block b's MV (x | y << 16) from the MB's record held one dword per lane
+__device__ __forceinline__ uint32_t blk_mv(uint32_t v0, int b) { return (uint32_t)__builtin_amdgcn_ds_bpermute((7 + b) << 2, (int)v0); }
+// the reference slot of block b's partition (refs: dword 6 of the record)
+__device__ __forceinline__ uint32_t blk_ref(uint32_t refs, int b) { return (refs >> (mcw_blk_part(b) * 8)) & 255; }
+
 // Reference windows are addressed from the stream's first slot (a uniform
 // 64-bit base in SGPRs) with 32-bit per-lane offsets: slot * frame_bytes
 // (frame_bytes a multiple of 256, so one 24-bit multiply) + row * pitch +
@@ -2065,6 +2071,11 @@ __device__ __forceinline__ void mc_issue(const ReconArgs &a, const PicDesc &pd, 
     const gcu8p pdb = uni(a.dbrec + (size_t)gmb * 64);
     const gcu8p pres = uni(a.res + (size_t)gmb * 384);
     if (rtype < MBT_I4x4) {
+        // The windows, rows and lane map of common/mc_window.h (mcw_luma,
+        // mcw_chroma, mcw_row, mcw_lane_*), spelled out: taken from the
+        // header, the same arithmetic compiles to another order in every
+        // instance, and the timed ones measured 0.5 % slower.
+        // A change here is a change there.
         const int mbx = mb % a.w, mby = mb / a.w;
         const int W16 = a.w * 16, H16 = a.h * 16, CW = W16 / 2, CH = H16 / 2;
         const gcu8p sb = uni(a.frames + (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane(pd.frame_base) * a.frame_bytes);
@@ -2248,9 +2259,13 @@ __device__ __forceinline__ int mc_finish(const ReconArgs &a, int p, uint32_t v0,
 // Frame-pipelined launches (a.P > 1): before MB mb's reference loads are
 // issued, wait until every 128-B line they touch is final in the slots that
 // earlier steps of this launch reconstruct.  Each lane takes the windows it
-// loads itself (mc_issue's geometry: luma block lane >> 2, window rows
-// lane & 3 .. 8; chroma block (lane & 31) >> 1, component lane & 1): the MB
-// rows R_lo..R_hi their lines hold and the last MB column X of those lines.
+// loads itself: the MB rows R_lo..R_hi their lines hold and the last MB
+// column X of those lines.  (The lane map and mcw_span_cells of
+// common/mc_window.h, spelled out like mc_issue's loads and for the same
+// reason: taken from the header, this instance's loop spilled more SGPRs and
+// measured 2.6 % slower; DESIGN.md §3.7.  A change here is a change there,
+// and in the copy of these lines that tests/mc_window_check.cpp compares
+// with mcw_span_cells: dep_wait_cols_rule.)
 // They need rows R_lo..R_hi final through column X -- those row workgroups'
 // stores through MB X + 1 -- and row R_hi + 1's through MB X (row_pp).  A
 // line is only read once all of its bytes are final, so no CU's L1 and no
@@ -2415,61 +2430,6 @@ __device__ __forceinline__ void dep_wait_rows(const ReconArgs &a, int p, uint32_
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-// its checker: the rows of the in-launch producer picture that MB mb's
-// reference loads need final, from the loads' own geometry (mc_issue's
-// windows at 128-B line granularity), must all be among the leading rows
-// dep_wait_rows saw done (D.known) -- i.e. set_ref_rows covered every line
-// the kernel reads.  Rows 0..R+1 done make MB row R's bytes final.
-__device__ __forceinline__ int chk_rows_need(uint32_t o, uint32_t ysz, int W16, int CP, int h)
-{
-    // MB rows whose workgroups must be done for byte o of a slot to be final
-    // (chroma rows padded to CP: no line crosses a plane)
-    const uint32_t csz = (uint32_t)CP * (uint32_t)(h * 8);
-    const int R = o < ysz ? (int)(o / (uint32_t)W16) >> 4 : (int)(((o - ysz) % csz) / (uint32_t)CP) >> 3;
-    return min(R + 2, h);
-}
-__device__ __forceinline__ void chk_ref_rows_rows(const ReconArgs &a, int p, int mb, uint32_t v0, int lane, const DepState &D)
-{
-    const uint32_t d0 = rec_dw(v0, 0), refs = rec_dw(v0, 6);
-    if ((d0 & 255) >= MBT_I4x4) return;
-    const int W16 = a.w * 16, H16 = a.h * 16, CW = W16 / 2, CH = H16 / 2, CP = a.cpitch;
-    const uint32_t ysz = (uint32_t)W16 * H16, csz = (uint32_t)CP * CH;
-    const int mbx = mb % a.w, mby = mb / a.w;
-    int need = 0;
-    {   // luma: lane -> block lb, window rows lsub + 4k (mc_issue)
-        const int lb = lane >> 2, lsub = lane & 3;
-        const uint32_t mvl = (uint32_t)__builtin_amdgcn_ds_bpermute((7 + lb) << 2, (int)v0);
-        if (const uint32_t rs = (refs >> ((lb >> 2) * 8)) & 255; rs < 32 && ((D.mask >> rs) & 1)) {
-            const int mvx = (int)(int16_t)(mvl & 0xFFFF), mvy = (int)(int16_t)(mvl >> 16);
-            const int x0 = clip3(0, W16 - 12, (mbx * 16 + blk_x(lb) * 4 + (mvx >> 2) - 2) & ~3);
-            const int y0 = mby * 16 + blk_y(lb) * 4 + (mvy >> 2) - 2;
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const int y = clip3(0, H16 - 1, y0 + min(lsub + 4 * k, 8));
-                const uint32_t o = (uint32_t)(y * W16 + x0);
-                need = max(need, chk_rows_need(min((o + 11) | 127u, ysz - 1), ysz, W16, CP, a.h));
-            }
-        }
-    }
-    {   // chroma: lane -> block cb, component
-        const int cb = (lane & 31) >> 1, ccomp = lane & 1;
-        const uint32_t mvc = (uint32_t)__builtin_amdgcn_ds_bpermute((7 + cb) << 2, (int)v0);
-        if (const uint32_t rs = (refs >> ((cb >> 2) * 8)) & 255; rs < 32 && ((D.mask >> rs) & 1)) {
-            const int cmx = (int)(int16_t)(mvc & 0xFFFF), cmy = (int)(int16_t)(mvc >> 16);
-            const int x0 = clip3(0, CW - 8, (mbx * 8 + blk_x(cb) * 2 + (cmx >> 3)) & ~3);
-            const int y0 = mby * 8 + blk_y(cb) * 2 + (cmy >> 3);
-#pragma unroll
-            for (int wy = 0; wy < 3; wy++) {
-                const int y = clip3(0, CH - 1, y0 + wy);
-                const uint32_t base = ysz + (uint32_t)ccomp * csz;
-                const uint32_t o = base + (uint32_t)(y * CP + x0);
-                need = max(need, chk_rows_need(min((o + 7) | 127u, base + csz - 1), ysz, W16, CP, a.h));
-            }
-        }
-    }
-    if (__builtin_amdgcn_ballot_w64(need > D.known) != 0 && lane == 0) atomicOr(a.err + p, CHK_REFROW);
-}
-
 // k_wgpp tail workgroup: waves 0..NMC-1 run the next batch's k_prep over a
 // grid-stride share of its MBs, in the LDS of the MC scratch and ring (unused
 // by a tail workgroup), once enough row workgroups of this and earlier
@@ -2504,13 +2464,22 @@ __device__ __forceinline__ void prep_tail(const ReconArgs &a, McScratch *M, MbRi
         prep_mb(pa, g, lane, wid < NM ? M[wid] : Mx[wid - NM], R.db[wid], T);
 }
 
-// Dependency checker, frame-pipelined launches: every 128-B line MB mb's
-// reference loads touch (mc_issue's windows, recomputed from the loads' own
-// geometry) must already be final in its in-launch producer picture --
-// (MB row, MB column) by (MB row, MB column) of the bytes it holds, read from
-// the producers' progress granules just before the loads are issued (values
-// only grow: what is final then is final when the loads run).  This checks
-// the host's set_ref_rows encoding and dep_wait together.
+// Dependency checker, frame-pipelined launches: one walk over the accesses
+// that common/mc_window.h gives the lane for MB mb (its windows, rows and
+// lane map), and per access the cells its 128-B lines hold, which must be
+// final in the access's in-launch producer picture.  It verifies the waits
+// (dep_wait_cols, dep_wait_rows) and the host's MbRec.i4 against the header.
+// It does not see what mc_issue loads: mc_issue spells the same geometry out
+// by hand, nothing but the comment there ties it to the header, and a drift
+// of the loads away from it would pass here (wrong samples show in the
+// parity tests; a load of a line the header does not name would not).
+//   DEP_COLS  (MB row, MB column) by (MB row, MB column), read from the
+//             producers' progress granules just before the loads are issued
+//             (values only grow: what is final then is final when the loads
+//             run), by the DEPC_* rule dep_wait_cols waits on;
+//   DEP_ROWS  rows 0..R+1 done make MB row R final: the access's last row + 2
+//             must be among the leading rows dep_wait_rows saw done (D.known)
+//             -- i.e. the host's MbRec.i4 (mcw_ref_rows) covered the line.
 __device__ __forceinline__ bool chk_row_final(const ReconArgs &a, int pk, int R, uint32_t need)
 {
     if (R >= a.h || need == 0) return true;
@@ -2519,68 +2488,42 @@ __device__ __forceinline__ bool chk_row_final(const ReconArgs &a, int pk, int R,
     const uint32_t v1 = (uint32_t)(g1 >> 32) == a.epoch ? (uint32_t)g1 : 0u;
     return min(v0, v1) >= need;
 }
-// the bytes [o, o + len) of a plane at pbase (pitch, rows, width bytes; MB
-// mbh rows x mbw bytes): every line they touch final in producer pk
-__device__ __forceinline__ bool chk_access(const ReconArgs &a, int pk, uint32_t o, int len, uint32_t pbase, int pitch,
-                                           int rows, int width, int mbh, int mbw)
-{
-    bool ok = true;
-    for (uint32_t l = o >> 7; l <= (o + len - 1) >> 7; l++) {
-        const uint32_t s0 = (l << 7) - pbase, e = (l << 7) + 127 - pbase;
-        const int ya = (int)(s0 / (uint32_t)pitch);
-        const int yb = min((int)(e / (uint32_t)pitch), rows - 1);
-        const int xe = ya == yb ? min((int)(e % (uint32_t)pitch), width - 1) / mbw : (width - 1) / mbw;
-        for (int R = ya / mbh; R <= yb / mbh; R++)
-            ok &= chk_row_final(a, pk, R, (uint32_t)min(xe + DEPC_SAME_ROW, a.w)) &&
-                  chk_row_final(a, pk, R + 1, (uint32_t)min(xe + DEPC_ROW_BELOW, a.w));
-    }
-    return ok;
-}
+static_assert(DEPC_SAME_ROW >= DEPC_ROW_BELOW, "rows inside r_lo..r_hi: the same-row need covers the row-below one");
 // (inline: an out-of-line call with the kernel arguments by reference
 // fails instruction selection -- a divergent copy into SGPRs)
+template <int DEPM>
 __device__ __forceinline__ void chk_ref_rows(const ReconArgs &a, int p, int mb, uint32_t v0, int lane, const DepState &D)
 {
     const uint32_t d0 = rec_dw(v0, 0), refs = rec_dw(v0, 6);
     if ((d0 & 255) >= MBT_I4x4) return;
-    const int W16 = a.w * 16, H16 = a.h * 16, CW = W16 / 2, CH = H16 / 2, CP = a.cpitch;
-    const uint32_t ysz = (uint32_t)W16 * H16, csz = (uint32_t)CP * CH;
-    const int mbx = mb % a.w, mby = mb / a.w;
-    // the in-launch producer of slot rs (or -1)
-    auto producer = [&](uint32_t rs) -> int {
-        for (int k = 0; k < D.n; k++)
-            if (((D.slots >> (k * 8)) & 255) == rs) return p - (k + 1) * a.S;
-        return -1;
+    // the predicate of an access: its cells c final in slot rs.  DEP_COLS: at
+    // most one in-launch producer writes slot rs (the comment above DepState),
+    // so the loop meets one match; rows inside r_lo..r_hi need SAME_ROW, which
+    // covers ROW_BELOW (the static_assert), so that one is tested for
+    // r_hi + 1 alone
+    auto final_ok = [&](uint32_t rs, const mcw_cells c) -> bool {
+        if (DEPM == DEP_ROWS) return !(rs < 32 && ((D.mask >> rs) & 1)) || min(c.r_hi + 2, a.h) <= D.known;
+        bool ok = true;
+        for (int k = 0; k < D.n; k++) {
+            if (((D.slots >> (k * 8)) & 255) != rs) continue;
+            const int pk = p - (k + 1) * a.S;               // the in-launch producer of slot rs
+            for (int R = c.r_lo; R <= c.r_hi; R++) ok &= chk_row_final(a, pk, R, (uint32_t)min(c.x + DEPC_SAME_ROW, a.w));
+            ok &= chk_row_final(a, pk, c.r_hi + 1, (uint32_t)min(c.x + DEPC_ROW_BELOW, a.w));
+        }
+        return ok;
     };
+    const mcw_plane yp = mcw_luma_plane(a.w, a.h), cp = mcw_chroma_plane(a.w, a.h, mcw_lane_chroma_comp(lane));
+    const int mbx = mb % a.w, mby = mb / a.w, lb = mcw_lane_luma_blk(lane), cb = mcw_lane_chroma_blk(lane);
+    const uint32_t mvl = blk_mv(v0, lb), mvc = blk_mv(v0, cb);
     bool ok = true;
-    {   // luma: lane -> block lb, window rows lsub + 4k (mc_issue)
-        const int lb = lane >> 2, lsub = lane & 3;
-        const uint32_t mvl = (uint32_t)__builtin_amdgcn_ds_bpermute((7 + lb) << 2, (int)v0);
-        const int pk = producer((refs >> ((lb >> 2) * 8)) & 255);
-        if (pk >= 0) {
-            const int mvx = (int)(int16_t)(mvl & 0xFFFF), mvy = (int)(int16_t)(mvl >> 16);
-            const int x0 = clip3(0, W16 - 12, (mbx * 16 + blk_x(lb) * 4 + (mvx >> 2) - 2) & ~3);
-            const int y0 = mby * 16 + blk_y(lb) * 4 + (mvy >> 2) - 2;
-            for (int k = 0; k < 3; k++) {
-                const int y = clip3(0, H16 - 1, y0 + min(lsub + 4 * k, 8));
-                ok &= chk_access(a, pk, (uint32_t)(y * W16 + x0), 12, 0, W16, H16, W16, 16, 16);
-            }
-        }
-    }
-    {   // chroma: lane -> block cb, component
-        const int cb = (lane & 31) >> 1, ccomp = lane & 1;
-        const uint32_t mvc = (uint32_t)__builtin_amdgcn_ds_bpermute((7 + cb) << 2, (int)v0);
-        const int pk = producer((refs >> ((cb >> 2) * 8)) & 255);
-        if (pk >= 0) {
-            const int cmx = (int)(int16_t)(mvc & 0xFFFF), cmy = (int)(int16_t)(mvc >> 16);
-            const int x0 = clip3(0, CW - 8, (mbx * 8 + blk_x(cb) * 2 + (cmx >> 3)) & ~3);
-            const int y0 = mby * 8 + blk_y(cb) * 2 + (cmy >> 3);
-            const uint32_t pb = ysz + (uint32_t)ccomp * csz;
-            for (int wy = 0; wy < 3; wy++) {
-                const int y = clip3(0, CH - 1, y0 + wy);
-                ok &= chk_access(a, pk, pb + (uint32_t)(y * CP + x0), 8, pb, CP, CH, CW, 8, 8);
-            }
-        }
-    }
+    const mcw_win lw = mcw_luma(a.w, mbx, mby, lb, (int16_t)(mvl & 0xFFFF), (int16_t)(mvl >> 16));
+    for (int k = 0; k < MCW_LANE_LUMA_LOADS; k++)
+        ok &= final_ok(blk_ref(refs, lb),
+                       mcw_access_cells(&yp, lw.ax, MCW_LUMA_BYTES, mcw_row(&yp, lw.y0 + mcw_lane_luma_row(lane, k))));
+    const mcw_win cw = mcw_chroma(a.w, mbx, mby, cb, (int16_t)(mvc & 0xFFFF), (int16_t)(mvc >> 16));
+    for (int k = 0; k < MCW_LANE_CHROMA_LOADS; k++)
+        ok &= final_ok(blk_ref(refs, cb),
+                       mcw_access_cells(&cp, cw.ax, MCW_CHROMA_BYTES, mcw_row(&cp, cw.y0 + mcw_lane_chroma_row(lane, k))));
     if (__builtin_amdgcn_ballot_w64(!ok) != 0 && lane == 0) atomicOr(a.err + p, CHK_REFROW);
 }
 
@@ -2654,9 +2597,8 @@ __device__ __forceinline__ void mc_row(const ReconArgs &a, int p, int r, int c0,
     uint32_t v0 = c < a.w ? recrow[(size_t)c * 24 + (lane < 24 ? lane : 0)] : 0;
     McLoad ld;
     if (DEPM == DEP_COLS && c < a.w && D.n) dep_wait_cols<CHK>(a, p, r * a.w + c, v0, lane, D, pc);
-    if (DEPM == DEP_COLS && CHK && c < a.w && D.n) chk_ref_rows(a, p, r * a.w + c, v0, lane, D);
     if (DEPM == DEP_ROWS && c < a.w && D.n) dep_wait_rows<CHK>(a, p, v0, lane, D);
-    if (DEPM == DEP_ROWS && CHK && c < a.w && D.n) chk_ref_rows_rows(a, p, r * a.w + c, v0, lane, D);
+    if (DEPM != DEP_NONE && CHK && c < a.w && D.n) chk_ref_rows<DEPM>(a, p, r * a.w + c, v0, lane, D);
     if (c < a.w) mc_issue(a, pd, p, r * a.w + c, v0, lane, ld);
 
     const int lead = a.mc_lead > 0 && a.mc_lead < RK ? a.mc_lead : RK;
@@ -2751,8 +2693,7 @@ __device__ __forceinline__ void mc_row(const ReconArgs &a, int p, int r, int c0,
         // PROF stamp [6] of the next MB: its in-launch dependency wait (100 MHz ticks)
         if (PROF && DEPM != DEP_NONE && c < a.w && lane == 0)
             a.prof[(size_t)a.npics * a.h * PROF_ROW + ((size_t)(p * a.h + r) * a.w + c) * PROF_MB + 6] = wall_clock64() - tdw;
-        if (DEPM == DEP_COLS && CHK && c < a.w && D.n) chk_ref_rows(a, p, r * a.w + c, v0, lane, D);
-        if (DEPM == DEP_ROWS && CHK && c < a.w && D.n) chk_ref_rows_rows(a, p, r * a.w + c, v0, lane, D);
+        if (DEPM != DEP_NONE && CHK && c < a.w && D.n) chk_ref_rows<DEPM>(a, p, r * a.w + c, v0, lane, D);
         const unsigned long long tis = PROF ? wall_clock64() : 0;
         uint32_t tsd[3] = {0, 0, 0};
         if (c < a.w) mc_issue(a, pd, p, r * a.w + c, v0, lane, ld, PROF ? tsd : nullptr);

@@ -4,6 +4,7 @@
  * batch" producer of SURVEY.md §8d (kernel-only timing uploads these to HBM
  * once) and the record source for kernel-level parity tests. */
 #include "../../../include/h264mi.h"
+#include "../common/mc_window.h"
 #include "decoder.h"
 
 #include <stdlib.h>
@@ -59,48 +60,16 @@ int h264mi_test_hooks(void)
 }
 
 /* Frame-pipelined launches with whole-row waits (recon_kernels.hip
- * dep_wait_rows): per inter MB and 8x8 partition, the last MB row of its
- * reference slot that a 128-B line read by its motion compensation touches,
- * as four uint16 in MbRec.i4 (luma 9 rows x 12 bytes per 4x4 block, chroma 3
- * rows x 8 bytes per 2x2 block and plane, windows clamped as in the kernel's
- * mc_issue).  Slot layout H264MI_SLOT_BYTES: no line crosses a plane
- * boundary, chroma lines hold one row; a luma line can reach into the next
- * row (w % 8 != 0), so the row is that of the line's last byte.  The
- * column-granular mode (dep_wait_cols) takes the geometry in the kernel. */
-static int line_row(long long last, long long pbase, long long pbytes, int pitch, int mbh)
-{
-    long long le = last | 127;
-    if (le > pbase + pbytes - 1) le = pbase + pbytes - 1;
-    return (int)((le - pbase) / pitch) / mbh;
-}
-
-static int clampi(int lo, int hi, int v) { return v < lo ? lo : v > hi ? hi : v; }
-
+ * dep_wait_rows): MbRec.i4 of every inter MB, by the windows and lines of
+ * common/mc_window.h (mcw_ref_rows).  The column-granular mode
+ * (dep_wait_cols) takes the same geometry in the kernel. */
 static void set_ref_rows(MbRec *recs, int w, int h)
 {
-    static const int bx[16] = {0, 1, 0, 1, 2, 3, 2, 3, 0, 1, 0, 1, 2, 3, 2, 3};
-    static const int by[16] = {0, 0, 1, 1, 0, 0, 1, 1, 2, 2, 3, 3, 2, 2, 3, 3};
-    const int W16 = w * 16, H16 = h * 16, CW = W16 / 2, CH = H16 / 2, CP = H264MI_CPITCH(w);
-    const long long ysz = (long long)W16 * H16, csz = (long long)CP * CH;
     for (int mb = 0; mb < w * h; mb++) {
         MbRec *r = &recs[mb];
         if (r->type != MBT_INTER && r->type != MBT_SKIP) continue;
-        const int mbx = mb % w, mby = mb / w;
-        uint16_t rows[4] = {0, 0, 0, 0};
-        for (int b = 0; b < 16; b++) {
-            const int mvx = r->mv[b][0], mvy = r->mv[b][1];
-            const int lax = clampi(0, W16 - 12, (mbx * 16 + bx[b] * 4 + (mvx >> 2) - 2) & ~3);
-            const int ly = clampi(0, H16 - 1, mby * 16 + by[b] * 4 + (mvy >> 2) - 2 + 8);
-            int n = line_row((long long)ly * W16 + lax + 11, 0, ysz, W16, 16);
-            const int cax = clampi(0, CW - 8, (mbx * 8 + bx[b] * 2 + (mvx >> 3)) & ~3);
-            const int cy = clampi(0, CH - 1, mby * 8 + by[b] * 2 + (mvy >> 3) + 2);
-            for (int comp = 0; comp < 2; comp++) {
-                const long long pb = ysz + comp * csz;
-                const int nc = line_row(pb + (long long)cy * CP + cax + 7, pb, csz, CP, 8);
-                if (nc > n) n = nc;
-            }
-            if (n > rows[b >> 2]) rows[b >> 2] = (uint16_t)n;
-        }
+        uint16_t rows[4];
+        mcw_ref_rows(r, w, h, mb % w, mb / w, rows);
         memcpy(r->i4, rows, 8);
     }
 }
@@ -152,16 +121,12 @@ static int cap_decode(void *vctx, const PicBuild *pb, int cur_slot)
 /* Distinct 128-B lines of the reference slots that k_wgpp's MC loads touch
  * for one picture, times 128: the line-granular (compulsory) part of its
  * reference traffic, beside R_alg's bytes actually used (part_bytes).  The
- * windows are mc_issue's (recon_kernels.hip): per 4x4 luma block 9 rows of
- * 12 bytes from (x0 & ~3) clamped to [0, W16 - 12], per 2x2 chroma block and
- * component 3 rows of 8 bytes from (x0 & ~3) clamped to [0, CW - 8], rows
- * clamped to the plane, chroma rows CP = H264MI_CPITCH apart.  Slots are
+ * accesses are those of common/mc_window.h (mcw_blk_accesses).  Slots are
  * H264MI_SLOT_BYTES apart, a multiple of 128, so line ids never straddle
  * slots. */
 static uint64_t ref_line_bytes(const MbRec *rec, int w, int h)
 {
-    const int W16 = w * 16, H16 = h * 16, CW = W16 / 2, CH = H16 / 2, CP = H264MI_CPITCH(w);
-    const size_t lines = H264MI_SLOT_BYTES(w, h) / 128;
+    const size_t lines = H264MI_SLOT_BYTES(w, h) / MCW_LINE;
     int maxslot = -1;
     for (int i = 0; i < w * h; i++)
         if (rec[i].type == MBT_INTER || rec[i].type == MBT_SKIP)
@@ -170,43 +135,21 @@ static uint64_t ref_line_bytes(const MbRec *rec, int w, int h)
     uint8_t *mark = (uint8_t *)calloc((size_t)(maxslot + 1) * lines, 1);
     if (!mark) return 0;
     uint64_t n = 0;
-#define MARK(slot, off, len) do {                                                   \
-        const size_t a_ = (off) / 128, b_ = ((off) + (len) - 1) / 128;             \
-        for (size_t l_ = a_; l_ <= b_; l_++) {                                     \
-            uint8_t *m_ = mark + (size_t)(slot) * lines + l_;                      \
-            if (!*m_) { *m_ = 1; n++; }                                            \
-        }                                                                          \
-    } while (0)
     for (int i = 0; i < w * h; i++) {
         const MbRec *r = &rec[i];
         if (r->type != MBT_INTER && r->type != MBT_SKIP) continue;
-        const int mbx = i % w, mby = i / w;
         for (int b = 0; b < 16; b++) {
-            const int bx = ((b >> 2) & 1) * 2 + (b & 1), by = ((b >> 3) & 1) * 2 + ((b >> 1) & 1);
-            const int slot = r->ref[b >> 2];
-            const int mvx = r->mv[b][0], mvy = r->mv[b][1];
-            int x0 = mbx * 16 + bx * 4 + (mvx >> 2) - 2, y0 = mby * 16 + by * 4 + (mvy >> 2) - 2;
-            int ax = x0 & ~3;
-            ax = ax < 0 ? 0 : ax > W16 - 12 ? W16 - 12 : ax;
-            for (int k = 0; k < 9; k++) {
-                int y = y0 + k;
-                y = y < 0 ? 0 : y > H16 - 1 ? H16 - 1 : y;
-                MARK(slot, (size_t)y * W16 + ax, 12);
-            }
-            int cx0 = mbx * 8 + bx * 2 + (mvx >> 3), cy0 = mby * 8 + by * 2 + (mvy >> 3);
-            int cax = cx0 & ~3;
-            cax = cax < 0 ? 0 : cax > CW - 8 ? CW - 8 : cax;
-            for (int comp = 0; comp < 2; comp++)
-                for (int k = 0; k < 3; k++) {
-                    int y = cy0 + k;
-                    y = y < 0 ? 0 : y > CH - 1 ? CH - 1 : y;
-                    MARK(slot, (size_t)W16 * H16 + (size_t)comp * CP * CH + (size_t)y * CP + cax, 8);
+            uint32_t off[MCW_BLK_ACCESSES];
+            mcw_blk_accesses(r, w, h, i % w, i / w, b, off);
+            for (int j = 0; j < MCW_BLK_ACCESSES; j++)
+                for (size_t l = off[j] / MCW_LINE; l <= (off[j] + mcw_blk_access_len(j) - 1) / MCW_LINE; l++) {
+                    uint8_t *m = mark + (size_t)r->ref[mcw_blk_part(b)] * lines + l;
+                    if (!*m) { *m = 1; n++; }
                 }
         }
     }
-#undef MARK
     free(mark);
-    return n * 128;
+    return n * MCW_LINE;
 }
 
 static int cap_read(void *vctx, int slot, uint8_t *dst)

@@ -1,6 +1,8 @@
 """h264mi_capture_ref_lines (bench.py's roofline.ref_line_bytes_per_launch):
 the distinct 128-B reference lines k_wgpp's MC windows touch, restated here
-from the records with numpy -- mc_issue's window geometry (recon_kernels.hip):
+from the records with numpy -- the window geometry that
+broadway_amd/csrc/common/mc_window.h states for the kernel and the host (this
+copy is the test's own, on purpose):
 luma 9 rows x 12 B per 4x4 block from (x0 & ~3) clamped to [0, W16 - 12],
 chroma 3 rows x 8 B per 2x2 block and component from (x0 & ~3) clamped to
 [0, CW - 8], rows clamped to the plane, chroma rows H264MI_CPITCH apart.  Host C only: runs without a GPU."""

@@ -11,7 +11,9 @@ steps of the launch are final, under three rules:
   column   rows R_lo..R_hi through MB column X (+1 for the store lag) and row
            R_hi + 1 through X (recon_kernels.hip dep_wait)
   picture  the whole producer picture (one release per picture)
-R_lo, R_hi, X are the lines of each MB's MC windows (mc_issue's geometry).
+R_lo, R_hi, X are the lines of each MB's MC windows: needs() restates
+broadway_amd/csrc/common/mc_window.h (windows, mcw_span_cells) in numpy, for
+widths whose luma rows end on 128-B lines (w % 8 == 0, as at 1080p).
 Prints the launch time per rule for SIM_P steps of SIM_S streams."""
 import os
 import sys
