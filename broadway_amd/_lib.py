@@ -107,9 +107,20 @@ class AccMvDesc(C.Structure):
                [("id", C.c_int * 8), ("scale", C.c_float * 8), ("bias", C.c_float * 8)]
 
 
+class AccResDesc(C.Structure):
+    """h264mi_accres_desc (include/h264mi.h)."""
+    _fields_ = [(n, C.c_int) for n in ("x", "y", "cw", "ch", "planes", "dtype", "colour", "unanchored")] + \
+               [("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
 # channel ids of AccMvDesc.id, by name
 ACCMV_CHANNELS = {"adx": 0, "ady": 1, "jx": 2, "jy": 3, "anchored": 4}
 ACCMV_MAX_CH = 8
+
+# AccResDesc.planes and .unanchored, by name
+ACCRES_PLANES = {"y": 0, "uv": 1, "yuv": 2, "rgb": 3}
+ACCRES_UNANCHORED = {"key": 0, "zero": 1}
+ACCRES_MAX_KEYS = 8
 
 # ResidualDesc.planes, by name
 RESID_PLANES = {"y": 0, "uv": 1, "yuv": 2}
@@ -301,6 +312,19 @@ def mi() -> C.CDLL:
         L.H264SwDecKeepAccMotion.restype = i32
         L.H264SwDecLastPictureAccMotion.argtypes = [vp, ad, vp, vp]
         L.H264SwDecLastPictureAccMotion.restype = i32
+    if hasattr(L, "h264mi_accres_device"):                  # (optional, as above)
+        rd = C.POINTER(AccResDesc)
+        szp = C.POINTER(sz)
+        L.h264mi_accres_device.argtypes = [vp, szp, vp, szp, vp, szp, i32, i32, i32, rd, vp, sz, vp]
+        L.h264mi_accres_device.restype = i32
+        L.h264mi_engine_keep_accres.argtypes = [vp, i32]
+        L.h264mi_engine_keep_accres.restype = i32
+        L.h264mi_engine_accres_held.argtypes = [vp, i32, i32]
+        L.h264mi_engine_accres_held.restype = i32
+        L.h264mi_engine_export_accres.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), rd, vp, sz, vp]
+        L.h264mi_engine_export_accres.restype = i32
+        L.h264mi_engine_conceal.argtypes = [vp, i32, i32, C.POINTER(i32), i32, C.POINTER(C.c_uint8)]
+        L.h264mi_engine_conceal.restype = i32
     L.h264mi_engine_sync.argtypes = [vp]
     L.h264mi_engine_sync.restype = i32
     L.h264mi_engine_kernel.argtypes = [vp]

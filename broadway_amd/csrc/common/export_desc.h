@@ -115,6 +115,23 @@ static inline int accmv_window_ok(const h264mi_accmv_desc *d, int w_mbs, int h_m
            d->cw <= 16 * w_mbs - d->x && d->ch <= 16 * h_mbs - d->y;
 }
 
+/* h264mi_accres_desc: planes, element type, a colour id 0..3 (never
+ * H264MI_TENSOR_COLOUR_STREAM) and a policy; the window is accmv_window_ok's,
+ * even for UV */
+static inline int accres_desc_fixed_ok(const h264mi_accres_desc *d)
+{
+    return d->planes >= H264MI_ACCRES_Y && d->planes <= H264MI_ACCRES_RGB && export_dtype_field(d->dtype) &&
+           d->colour >= 0 && d->colour <= H264MI_TENSOR_COLOUR_BT709_FULL &&
+           (d->unanchored == H264MI_ACCRES_KEY || d->unanchored == H264MI_ACCRES_ZERO);
+}
+
+static inline int accres_window_ok(const h264mi_accres_desc *d, int w_mbs, int h_mbs)
+{
+    return accmv_size_ok(w_mbs, h_mbs) && d->x >= 0 && d->y >= 0 && d->cw >= 1 && d->ch >= 1 &&
+           d->cw <= 16 * w_mbs - d->x && d->ch <= 16 * h_mbs - d->y &&
+           (d->planes != H264MI_ACCRES_UV || !((d->x | d->y | d->cw | d->ch) & 1));
+}
+
 /* An SPS's crop window in luma samples (the whole picture without cropping;
  * the offsets are in the SPS's units of 2 samples) */
 typedef struct { int x, y, cw, ch; } export_window;

@@ -10,6 +10,7 @@
 #include "mbinfo.hip"
 #include "residual.hip"
 #include "accmv.hip"
+#include "accres.hip"
 #include "conceal.hip"
 #include <hip/hip_ext.h>
 
@@ -101,6 +102,10 @@ struct h264mi_engine {
     uint32_t *d_acc;          // h264mi_engine_keep_accmv: per (stream, slot) the origin map of the last reconstruction into it (NULL: off)
     unsigned long long *acc_key;  // per stream: serial of its current key picture (host; 0: none yet)
     unsigned long long *acc_ser;  // per (stream, slot): the key serial its map was written under (host; 0: no map)
+    uint8_t *d_akey;          // h264mi_engine_keep_accres: per (stream, entry < akey_n) a key picture's frame (NULL: off)
+    int akey_n;               // entries per stream (0: off)
+    unsigned long long *akey_tag; // per (stream, entry): the key serial whose picture the entry holds (host; 0: none)
+    int *akey_slot;           // per stream: the slot its current key picture sits in (host; -1: none, or written over)
     int steps;                // pictures per stream per launch (h264mi_engine_set_steps)
     unsigned long long *d_prog;   // per picture row of a launch, per row wave: {MBs stored, epoch} (frame-pipelined launches)
     unsigned *d_done;             // per picture row of a launch: epoch once the row is stored
@@ -276,6 +281,9 @@ extern "C" void h264mi_engine_destroy(h264mi_engine *e)
     (void)hipFree(e->d_acc);
     free(e->acc_key);
     free(e->acc_ser);
+    (void)hipFree(e->d_akey);
+    free(e->akey_tag);
+    free(e->akey_slot);
     (void)hipFree(e->d_frames); (void)hipFree(e->d_prof); (void)hipFree(e->d_rec); (void)hipFree(e->d_coef);
     (void)hipFree(e->d_pics); (void)hipFree(e->d_gjunk);
     (void)hipHostFree(e->h_rec); (void)hipHostFree(e->h_coef); (void)hipHostFree(e->h_pics);
@@ -529,6 +537,36 @@ static int keep_batch(h264mi_engine *e, int npics, const int *stream, const int 
 static size_t acc_words(const h264mi_engine *e) { return (size_t)e->nmbs * 256; }
 static int accmv_clear(h264mi_engine *e, size_t first, size_t n);
 
+// Key-picture retention (h264mi_engine_keep_accres): the samples of `slot`,
+// which holds the stream's current key picture (serial s = acc_key[stream]),
+// into the stream's entry s % akey_n, behind everything queued on the engine's
+// stream so far -- the launch that reconstructs the slot is.  An export that
+// reads the entry's previous picture (serial s - akey_n) runs on the same
+// stream (export_ordered), so this copy waits for it as a decode into a slot
+// waits for the slot's export.
+static int accres_copy_key(h264mi_engine *e, int stream, int slot)
+{
+    const unsigned long long s = e->acc_key[stream];
+    const size_t entry = (size_t)stream * e->akey_n + (size_t)(s % (unsigned)e->akey_n);
+    HIPCHECK(hipMemcpyAsync(e->d_akey + entry * e->frame_bytes,
+                            e->d_frames + e->frame_bytes * ((size_t)stream * e->nslots + slot), e->frame_bytes,
+                            hipMemcpyDeviceToDevice, e->st));
+    e->akey_tag[entry] = s;
+    return 0;
+}
+
+// a picture that is no key picture and is decoded into the slot of its stream's
+// current key: the second pass of a concealment (host/conceal.c: the concealed
+// MBs are zero-vector skip records that name the slot itself, which no other
+// picture does) reconstructs the key picture again, now filtered; any other
+// picture replaces it
+static bool accres_second_pass(const h264mi_engine *e, const MbRec *r, int slot)
+{
+    for (int m = 0; m < e->nmbs; m++)
+        if (r[m].type <= MBT_SKIP && r[m].ref[0] == slot) return true;
+    return false;
+}
+
 static int accmv_batch(h264mi_engine *e, int npics, const int *stream, const int *cur_slot, const void *const *recs)
 {
     accmv_step_args a;
@@ -556,6 +594,20 @@ static int accmv_batch(h264mi_engine *e, int npics, const int *stream, const int
                         a.ref[k][s] = e->d_acc + (b + s) * acc_words(e);
             }
             e->acc_ser[b + cur_slot[i]] = e->acc_key[stream[i]];
+            if (!e->d_akey) continue;
+            // (a later picture of this batch into the same slot leaves nothing to copy after the launch)
+            bool last = true;
+            for (int j = i + 1; j < npics && last; j++) last = stream[j] != stream[i] || cur_slot[j] != cur_slot[i];
+            if (key) {
+                e->akey_slot[stream[i]] = last ? cur_slot[i] : -1;
+                if (last && accres_copy_key(e, stream[i], cur_slot[i])) return -1;
+            } else if (e->akey_slot[stream[i]] == cur_slot[i]) {
+                if (last && accres_second_pass(e, r, cur_slot[i])) {
+                    if (accres_copy_key(e, stream[i], cur_slot[i])) return -1;
+                } else {
+                    e->akey_slot[stream[i]] = -1;
+                }
+            }
         }
         accmv_step_launch(n, e->st, a);
         HIPCHECK(hipGetLastError());
@@ -1383,6 +1435,7 @@ extern "C" int h264mi_engine_forget_records(h264mi_engine *e, int stream, int sl
     if (e->d_acc) {
         // the slot's map says nothing about its picture: none as a reference, (x, y, 0) when exported
         e->acc_ser[(size_t)stream * e->nslots + slot] = 0;
+        if (e->akey_slot && e->akey_slot[stream] == slot) e->akey_slot[stream] = -1;    // (its entry stays: the GOP's pictures export against it)
         return accmv_clear(e, (size_t)stream * e->nslots + slot, 1);
     }
     return 0;
@@ -1569,6 +1622,7 @@ extern "C" int h264mi_engine_keep_accmv(h264mi_engine *e, int on)
         }
         return 0;
     }
+    if (h264mi_engine_keep_accres(e, 0)) return -1;     // the keys go with the maps they are read through
     HIPCHECK(hipStreamSynchronize(e->st));
     (void)hipFree(e->d_acc);
     free(e->acc_key); free(e->acc_ser);
@@ -1586,6 +1640,126 @@ extern "C" int h264mi_engine_export_accmv(h264mi_engine *e, int n, const int *st
         std::vector<size_t> off((size_t)n);
         for (int k = 0; k < n; k++) off[k] = acc_words(e) * 4 * ((size_t)streams[k] * e->nslots + slots[k]);
         return h264mi_accmv_device(e->d_acc, off.data(), n, e->w, e->h, desc, d_out, out_stride, e->st);
+    });
+}
+
+// an export descriptor h264mi_accres_device accepts on a w_mbs x h_mbs picture
+static bool accres_desc_ok(const h264mi_accres_desc *d, int w_mbs, int h_mbs)
+{
+    return d && accres_desc_fixed_ok(d) && accres_window_ok(d, w_mbs, h_mbs);
+}
+
+// The accumulated residual (accres.hip k_accres): the window desc->(x, y, cw,
+// ch) of npics pictures -- frame, key frame or none ((size_t)-1), origin map,
+// each at its offset -- as contiguous (planes, ch, cw) elements of desc->dtype
+// at d_out + k * out_stride; device pointers, asynchronous on `stream`;
+// ACCRES_MAX_PICS pictures per launch.  -1 (nothing launched) on a bad argument.
+extern "C" int h264mi_accres_device(const void *d_cur, const size_t *cur_offsets, const void *d_key,
+                                    const size_t *key_offsets, const void *d_maps, const size_t *map_offsets, int npics,
+                                    int w_mbs, int h_mbs, const h264mi_accres_desc *desc, void *d_out, size_t out_stride,
+                                    void *stream)
+{
+    static_assert(H264MI_ACCRES_Y == ACCRES_Y && H264MI_ACCRES_UV == ACCRES_UV && H264MI_ACCRES_YUV == ACCRES_YUV &&
+                      H264MI_ACCRES_RGB == ACCRES_RGB && ACCRES_MAX_PICS == EXPORT_MAX_PICS &&
+                      H264MI_TENSOR_COLOUR_BT709_FULL == TENSOR_COLOUR_SETS - 1,
+                  "include/h264mi.h and accres.hip name the same planes, bounds and colour sets");
+    if (!d_cur || !cur_offsets || !key_offsets || !d_maps || !map_offsets || !d_out || npics < 1 ||
+        (((size_t)(uintptr_t)d_cur | (size_t)(uintptr_t)d_key | (size_t)(uintptr_t)d_maps) & 3) ||
+        !accres_desc_ok(desc, w_mbs, h_mbs))
+        return -1;
+    for (int k = 0; k < npics; k++) {
+        if ((map_offsets[k] | cur_offsets[k]) & 3) return -1;
+        if (key_offsets[k] != (size_t)-1 && (!d_key || (key_offsets[k] & 3))) return -1;
+    }
+    const size_t es = export_elem_size(desc->dtype);
+    if (!export_aligned(d_out, out_stride, es)) return -1;
+    const int ow = desc->planes == H264MI_ACCRES_UV ? desc->cw / 2 : desc->cw;
+    const bool v16 = export_v16(d_out, out_stride, (size_t)ow * es);
+    accres_args a;
+    a.cur = (const uint8_t *)d_cur; a.key = (const uint8_t *)d_key; a.maps = (const uint8_t *)d_maps;
+    a.W = 16 * w_mbs; a.H = 16 * h_mbs; a.cpitch = H264MI_CPITCH(w_mbs);
+    a.x = desc->x; a.y = desc->y; a.cw = desc->cw; a.ch = desc->ch;
+    a.planes = desc->planes; a.zero = desc->unanchored == H264MI_ACCRES_ZERO;
+    a.out_stride = out_stride;
+    a.col = tensor_colour_sets[desc->colour];
+    for (int c = 0; c < 3; c++) { a.scale[c] = desc->scale[c]; a.bias[c] = desc->bias[c]; }
+    return export_launches(npics, map_offsets, a.map_off, &a.out, d_out, out_stride, [&](int k0, int n) {
+        for (int k = 0; k < ACCRES_MAX_PICS; k++) {
+            a.cur_off[k] = k < n ? cur_offsets[k0 + k] : 0;
+            a.key_off[k] = k < n && key_offsets[k0 + k] != (size_t)-1 ? key_offsets[k0 + k] : ACCRES_NO_KEY;
+        }
+        accres_launch(desc->dtype, v16, n, (hipStream_t)stream, a);
+    });
+}
+
+static void accres_free(h264mi_engine *e)
+{
+    (void)hipFree(e->d_akey);
+    free(e->akey_tag); free(e->akey_slot);
+    e->d_akey = NULL; e->akey_tag = NULL; e->akey_slot = NULL;
+    e->akey_n = 0;
+}
+
+// Key-picture retention: nkeys frames per stream, none tagged, so switching on
+// starts from nothing (pictures decoded before have no key).  Off, and a change
+// of nkeys, wait for the engine's stream (copies and exports run on it) and free.
+extern "C" int h264mi_engine_keep_accres(h264mi_engine *e, int nkeys)
+{
+    if (!e || nkeys < 0 || nkeys > H264MI_ACCRES_MAX_KEYS) return -1;
+    if (nkeys == e->akey_n) return 0;
+    if (nkeys && !e->d_acc) return -1;          // a key is read through an origin map
+    HIPCHECK(hipSetDevice(e->dev));
+    if (e->akey_n) {
+        HIPCHECK(hipStreamSynchronize(e->st));
+        accres_free(e);
+    }
+    if (!nkeys) return 0;
+    const size_t ne = (size_t)e->nstreams * nkeys;
+    e->akey_tag = (unsigned long long *)calloc(ne, sizeof(unsigned long long));
+    e->akey_slot = (int *)malloc(sizeof(int) * (size_t)e->nstreams);
+    if (!e->akey_tag || !e->akey_slot || hipMalloc(&e->d_akey, ne * e->frame_bytes) != hipSuccess) {
+        e->d_akey = NULL;
+        accres_free(e);
+        return -1;
+    }
+    for (int s = 0; s < e->nstreams; s++) e->akey_slot[s] = -1;
+    e->akey_n = nkeys;
+    return 0;
+}
+
+// the entry that holds the key of the slot's picture, or -1: the slot's map
+// carries serial t, and entry t % akey_n holds that key iff it is tagged t
+static long accres_entry(const h264mi_engine *e, int stream, int slot)
+{
+    const unsigned long long t = e->acc_ser[(size_t)stream * e->nslots + slot];
+    const size_t entry = (size_t)stream * e->akey_n + (size_t)(t % (unsigned)e->akey_n);
+    return t && e->akey_tag[entry] == t ? (long)entry : -1;
+}
+
+extern "C" int h264mi_engine_accres_held(h264mi_engine *e, int stream, int slot)
+{
+    if (!e || !e->d_akey || stream < 0 || stream >= e->nstreams || slot < 0 || slot >= e->nslots) return -1;
+    return accres_entry(e, stream, slot) >= 0;
+}
+
+// The accumulated residual of the slots (streams[k], slots[k]) against the keys
+// held for them, as tensors in the caller's memory, ordered between the
+// caller's stream and ours by export_ordered
+extern "C" int h264mi_engine_export_accres(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                           const h264mi_accres_desc *desc, void *d_out, size_t out_stride, void *stream)
+{
+    if (!e || !e->d_akey || n < 1 || !streams || !slots || !d_out || !accres_desc_ok(desc, e->w, e->h)) return -1;
+    return export_ordered(e, n, streams, slots, d_out, out_stride, export_elem_size(desc->dtype), stream, [&] {
+        std::vector<size_t> cur((size_t)n), key((size_t)n), map((size_t)n);
+        for (int k = 0; k < n; k++) {
+            const size_t b = (size_t)streams[k] * e->nslots + slots[k];
+            const long entry = accres_entry(e, streams[k], slots[k]);
+            cur[k] = e->frame_bytes * b;
+            key[k] = entry < 0 ? (size_t)-1 : e->frame_bytes * (size_t)entry;
+            map[k] = acc_words(e) * 4 * b;
+        }
+        return h264mi_accres_device(e->d_frames, cur.data(), e->d_akey, key.data(), e->d_acc, map.data(), n, e->w, e->h,
+                                    desc, d_out, out_stride, e->st);
     });
 }
 
@@ -1637,6 +1811,8 @@ extern "C" int h264mi_engine_conceal(h264mi_engine *e, int stream, int slot, con
                        e->w, e->h, e->cpitch, (const int *)e->d_conceal, n, (const uint8_t *)(e->d_conceal + sizeof(int) * (size_t)e->nmbs));
     HIPCHECK(hipGetLastError());
     g_conceal_launches++;
+    // the slot's samples changed after its reconstruction: a key picture's copy is taken again
+    if (e->d_akey && e->akey_slot[stream] == slot && accres_copy_key(e, stream, slot)) return -1;
     return 0;
 }
 
@@ -1718,6 +1894,7 @@ int engine_reuse(h264mi_engine *e)
     e->last_kernel = NULL;
     if (h264mi_engine_keep_coefs(e, 0) || h264mi_engine_keep_records(e, 0) || h264mi_engine_keep_accmv(e, 0))
         return -1;                                                                          // the previous owner's retention
+    // (keep_accmv(0) took the key pictures with it: h264mi_engine_keep_accres needs the maps, so it is never on without them)
     // the epoch keeps counting: the mailboxes hold tags of earlier launches only
     HIPCHECK(hipMemsetAsync(e->d_frames, 0, e->frame_bytes * e->nslots * e->nstreams, e->st));
     return 0;

@@ -257,6 +257,60 @@ def accmv_desc(channels=("adx", "ady"), window=None, dtype=None, scale=None, bia
     return d, len(channels), dtype
 
 
+def accres_desc(planes="y", window=None, dtype=None, scale=None, bias=None, colour=None, unanchored="key"):
+    """(``_lib.AccResDesc``, number of planes, torch dtype) of an export of the
+    accumulated residual (Engine.to_accres; include/h264mi.h defines the
+    field): every sample of the picture minus its
+    origin in the key picture of its GOP.  ``planes`` is "y" (one plane), "uv"
+    (Cb and Cr at half resolution), "yuv" (three planes at luma resolution,
+    chroma by nearest neighbour) or "rgb" (three planes at luma resolution,
+    the difference of the two pixels converted under ``colour``: a name of
+    ``_lib.TENSOR_COLOURS`` but "stream", None is "reference"; "rgb" only).
+    ``unanchored``: "key" -- a sample whose chain back started at an intra MB is
+    set against the key picture where that chain started -- or "zero": such a
+    sample is 0.  window, dtype, scale and bias as for ``residual_desc``."""
+    import torch
+    if not isinstance(planes, str) or planes not in _lib.ACCRES_PLANES:
+        raise ValueError(f"planes {planes!r}: one of {sorted(_lib.ACCRES_PLANES)}")
+    if not isinstance(unanchored, str) or unanchored not in _lib.ACCRES_UNANCHORED:
+        raise ValueError(f"unanchored {unanchored!r}: one of {sorted(_lib.ACCRES_UNANCHORED)}")
+    if colour is not None and planes != "rgb":
+        raise ValueError(f"colour: planes {planes!r} have no colour set (only 'rgb')")
+    colour = "reference" if colour is None else colour
+    if not isinstance(colour, str) or colour not in _lib.TENSOR_COLOURS or colour == "stream":
+        raise ValueError(f"colour {colour!r}: one of {sorted(set(_lib.TENSOR_COLOURS) - {'stream'})}")
+    np_ = {"y": 1, "uv": 2, "yuv": 3, "rgb": 3}[planes]
+    dtype = torch.int16 if dtype is None else dtype
+    dts = {torch.int16: _lib.TENSOR_I16, torch.float16: _lib.TENSOR_F16, torch.bfloat16: _lib.TENSOR_BF16,
+           torch.float32: _lib.TENSOR_F32}
+    if dtype not in dts:
+        raise ValueError(f"dtype {dtype}: one of torch.int16, float16, bfloat16, float32")
+
+    def per_plane(v, default, what):
+        if v is None:
+            return (default,) * np_
+        v = tuple(float(f) for f in v) if hasattr(v, "__len__") else (float(v),) * np_
+        if len(v) != np_:
+            raise ValueError(f"{what}: a scalar or one value per plane")
+        return v
+
+    d = _lib.AccResDesc()
+    if window is not None:
+        try:
+            d.x, d.y, d.cw, d.ch = (int(v) for v in window)
+        except (TypeError, ValueError):
+            raise ValueError(f"window {window!r}: (x, y, cw, ch)") from None
+        if d.x < 0 or d.y < 0 or d.cw < 1 or d.ch < 1:
+            raise ValueError(f"window {tuple(window)}: x, y >= 0 and cw, ch >= 1 (luma samples)")
+        if planes == "uv" and (d.x | d.y | d.cw | d.ch) & 1:
+            raise ValueError(f"window {tuple(window)}: x, y, cw and ch are even for planes 'uv'")
+    d.planes, d.dtype = _lib.ACCRES_PLANES[planes], dts[dtype]
+    d.colour, d.unanchored = _lib.TENSOR_COLOURS[colour], _lib.ACCRES_UNANCHORED[unanchored]
+    d.scale[:np_] = per_plane(scale, 1.0, "scale")
+    d.bias[:np_] = per_plane(bias, 0.0, "bias")
+    return d, np_, dtype
+
+
 @dataclass
 class CapturedPicture:
     rec: int            # host address of w*h MbRec
@@ -594,6 +648,64 @@ class Engine:
                 self._L.h264mi_engine_export_accmv(self._h, n, c_streams, c_slots, C.byref(desc), out.data_ptr(),
                                                    nch * desc.ch * desc.cw * out.element_size(), st) != 0:
             raise RuntimeError("h264mi_engine_export_accmv failed (keep_accmv off, or stream, slot or window "
+                               "out of range?)")
+        return out
+
+    def keep_accres(self, nkeys: int = 2) -> None:
+        """Keep the samples of each stream's last ``nkeys`` (1..8) key pictures
+        on the device beyond the life of their frame slots, from the next
+        ``decode`` on (to_accres reads them): one frame per key (3.20 MB at
+        1080p) and one device-to-device copy per key picture.  With 2, every
+        picture of the previous GOP stays exportable after the next key picture
+        was decoded.  Needs ``keep_accmv()`` first; ``keep_accmv(False)``
+        switches this off too.  ``nkeys=0`` waits for the engine and frees
+        them.  ``decode_device*`` launches retain nothing."""
+        if not hasattr(self._L, "h264mi_engine_keep_accres") or \
+                self._L.h264mi_engine_keep_accres(self._h, int(nkeys)) != 0:
+            raise RuntimeError("h264mi_engine_keep_accres failed (keep_accmv off, or nkeys not in 0..8?)")
+
+    def conceal(self, stream: int, slot: int, order: Sequence[int], decoded: Sequence[int]) -> None:
+        """Neighbour-based concealment of the MBs ``order`` (in that order) of
+        the picture in (stream, slot), in place, behind the work queued so far
+        (``h264mi_engine_conceal``); ``decoded``: per MB 1 (decoded) or 0."""
+        n = len(order)
+        o = (C.c_int * max(n, 1))(*order)
+        d = (C.c_uint8 * (self.w_mbs * self.h_mbs))(*decoded)
+        if self._L.h264mi_engine_conceal(self._h, stream, slot, o, n, d) != 0:
+            raise RuntimeError("h264mi_engine_conceal failed (a bad stream, slot or MB, or a picture too large)")
+
+    def accres_held(self, stream: int, slot: int) -> bool:
+        """Whether the key picture of the picture in (stream, slot) is held;
+        to_accres gives zeros for a slot whose key is not."""
+        r = self._L.h264mi_engine_accres_held(self._h, stream, slot) if hasattr(self._L, "h264mi_engine_accres_held") \
+            else -1
+        if r < 0:
+            raise RuntimeError("h264mi_engine_accres_held failed (keep_accres off, or a bad stream or slot)")
+        return bool(r)
+
+    def to_accres(self, streams: Sequence[int], slots: Sequence[int], planes="y", window=None, dtype=None,
+                  scale=None, bias=None, colour=None, unanchored="key", out=None, stream=None):
+        """The accumulated residual of the pictures last decoded into the slots
+        (streams[k], slots[k]) -- each sample minus its origin in the key
+        picture of its GOP -- as one ``(n, 1 | 2 | 3, rows, columns)`` torch
+        tensor on ``cuda:{self.device}``: ``planes`` "y", "yuv" and "rgb" give
+        ``(ch, cw)`` planes of ``window`` = (x, y, cw, ch) in luma samples
+        (None: the whole MB-aligned picture), "uv" ``(ch / 2, cw / 2)``
+        (``accres_desc``; a slot whose key is not held -- ``accres_held`` --
+        reads as zeros).  Needs ``keep_accmv()`` and ``keep_accres()`` before
+        the decodes.  ``out`` and ``stream`` as for ``to_tensor``; the host is
+        never synchronised."""
+        n, c_streams, c_slots = self._pictures(streams, slots)
+        if window is None:
+            window = (0, 0, self.w_mbs * 16, self.h_mbs * 16)
+        desc, npl, dtype = accres_desc(planes, window, dtype, scale, bias, colour, unanchored)
+        hs = 1 if planes == "uv" else 0
+        shape = (n, npl, desc.ch >> hs, desc.cw >> hs)
+        out, st = self._out(shape, dtype, out, stream)
+        if not hasattr(self._L, "h264mi_engine_export_accres") or \
+                self._L.h264mi_engine_export_accres(self._h, n, c_streams, c_slots, C.byref(desc), out.data_ptr(),
+                                                    npl * shape[2] * shape[3] * out.element_size(), st) != 0:
+            raise RuntimeError("h264mi_engine_export_accres failed (keep_accres off, or stream, slot or window "
                                "out of range?)")
         return out
 

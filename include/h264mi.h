@@ -380,6 +380,50 @@ H264SwDecRet H264SwDecKeepAccMotion(H264SwDecInst decInst, u32 on);
  * (H264SWDEC_PARAM_ERR also without H264SwDecKeepAccMotion). */
 H264SwDecRet H264SwDecLastPictureAccMotion(H264SwDecInst decInst, const h264mi_accmv_desc *desc, void *d_dst,
                                            void *hip_stream);
+/* The accumulated residual as a device tensor (accres.hip): every
+ * sample of the current picture minus its origin in the key picture of its
+ * GOP, cur(p) - key(J(p)) -- the third input of CoViAR-style models beside the
+ * key picture's pixels and the accumulated motion above.
+ * Everything lives on the MB-aligned picture, W = 16 * w_mbs by H = 16 * h_mbs.
+ * A frame is a picture in the engine's slot layout (h264mi_records.h): luma
+ * rows W bytes apart, then Cb, then Cr, each 8 * h_mbs rows H264MI_CPITCH(w_mbs)
+ * bytes apart, H264MI_SLOT_BYTES(w_mbs, h_mbs) in all.
+ * Inputs per picture: the current frame C, a key frame K or none, and an origin
+ * map M in h264mi_accmv_desc's word format.  For luma sample (x, y), m = M[y *
+ * W + x] gives JX, JY and A = ANCHORED; a word with JX >= W or JY >= H is
+ * clamped to W - 1 / H - 1 (the engine's maps never hold one: the clamp makes
+ * the stateless call well defined, and nothing outside K is ever read).
+ * planes:
+ *   H264MI_ACCRES_Y    one plane, v = C.Y[y][x] - K.Y[JY][JX].
+ *   H264MI_ACCRES_UV   two planes (Cb, Cr) at half resolution: x, y, cw, ch
+ *                      must be even; chroma sample (cx, cy) uses the word of
+ *                      luma (2 cx, 2 cy), v = C.Cb[cy][cx] - K.Cb[JY >> 1][JX >> 1],
+ *                      Cr the same.
+ *   H264MI_ACCRES_YUV  three planes at luma resolution: Y as above, and at (x,
+ *                      y) C.Cb[y >> 1][x >> 1] - K.Cb[JY >> 1][JX >> 1] with that
+ *                      sample's own word, Cr the same.
+ *   H264MI_ACCRES_RGB  three planes at luma resolution: v_c = rgb_c(C at (x, y))
+ *                      - rgb_c(K at (JX, JY)), chroma sited as for YUV, rgb_c the
+ *                      integer conversion of colour id `colour` in 0..3 (the ids
+ *                      and arithmetic of h264mi_tensor_colour_coeffs);
+ *                      H264MI_TENSOR_COLOUR_STREAM is refused.
+ * `colour` must be 0..3 whatever the planes.  unanchored: H264MI_ACCRES_KEY
+ * (0): (JX, JY) is used whatever A says -- CoViAR's convention, an intra sample
+ * pretends it came from its own position; H264MI_ACCRES_ZERO (1): v = 0 where
+ * A = 0.  Without a key frame every v is 0.
+ * v lies in -255..255.  Elements: H264MI_TENSOR_I16 (v) or F16 / BF16 / F32,
+ * fma((float)v, scale[c], bias[c]) of plane position c, converted as for
+ * h264mi_tensor_desc; U8 is refused.  The window (x, y, cw, ch) lies anywhere
+ * inside W x H, both at most H264MI_ACCMV_MAX_DIM. */
+enum { H264MI_ACCRES_Y = 0, H264MI_ACCRES_UV = 1, H264MI_ACCRES_YUV = 2, H264MI_ACCRES_RGB = 3 };
+enum { H264MI_ACCRES_KEY = 0, H264MI_ACCRES_ZERO = 1 };
+#define H264MI_ACCRES_MAX_KEYS 8
+typedef struct {
+    int x, y, cw, ch, planes, dtype, colour, unanchored;
+    float scale[3], bias[3];
+} h264mi_accres_desc;
+/* (The export is an engine-level call for now: h264mi_accres_device and
+ * h264mi_engine_keep_accres / _export_accres below; there is no H264SwDec call.) */
 /* Extension (no reference counterpart): where an instance's time went, in
  * seconds since H264SwDecInit -- host parse (NAL extraction, headers, CAVLC /
  * MB layer, DPB, concealment), record upload + kernel launch, waiting for the
@@ -700,6 +744,54 @@ int  h264mi_engine_keep_accmv(h264mi_engine *e, int on);
  * d_out is not on the engine's device. */
 int  h264mi_engine_export_accmv(h264mi_engine *e, int n, const int *streams, const int *slots,
                                 const h264mi_accmv_desc *desc, void *d_out, size_t out_stride, void *hip_stream);
+/* the accumulated residual (h264mi_accres_desc above) of npics pictures of
+ * w_mbs x h_mbs MBs: picture k's current frame starts cur_offsets[k] bytes
+ * after d_cur, its key frame key_offsets[k] bytes after d_key -- (size_t)-1:
+ * picture k has no key and is all zeros; d_key may be NULL when every picture
+ * has none -- and its origin map map_offsets[k] bytes after d_maps (host arrays;
+ * any order, repeats allowed; every pointer and offset a multiple of 4).
+ * Picture k's (planes, ch, cw) elements go, contiguous, to d_out + k *
+ * out_stride under the alignment rules of h264mi_mbinfo_device; nothing else is
+ * written, and no byte outside the three planes of a frame or the W * H words
+ * of a map is read.  Stateless; asynchronous on `hip_stream`.  -1 on a bad
+ * argument or a picture beyond H264MI_ACCMV_MAX_DIM, nothing launched.  For
+ * decode_device* callers that own frames and maps. */
+int  h264mi_accres_device(const void *d_cur, const size_t *cur_offsets, const void *d_key, const size_t *key_offsets,
+                          const void *d_maps, const size_t *map_offsets, int npics, int w_mbs, int h_mbs,
+                          const h264mi_accres_desc *desc, void *d_out, size_t out_stride, void *hip_stream);
+/* key-picture retention: nkeys in 1..H264MI_ACCRES_MAX_KEYS allocates nstreams *
+ * nkeys frames (3.20 MB per 1080p key: 51 MB for eight streams with two keys
+ * each); it needs h264mi_engine_keep_accmv on (-1 while that is off, and
+ * switching that off switches this off).  From then on, whenever a decode
+ * bumps a stream's key serial to s (h264mi_engine_keep_accmv's key-picture
+ * rule), one device-to-device copy of the reconstructed slot into the stream's
+ * entry s % nkeys is queued behind the reconstruction, on the engine's stream,
+ * and the entry is tagged s.  The copy is queued again when something rewrites
+ * the key picture in its slot: h264mi_engine_conceal on that slot, and a
+ * decode into it whose inter records reference the slot itself (the second
+ * pass of the H264SwDec path's concealment).  A slot whose map carries serial t exports against
+ * entry t % nkeys iff t != 0 and the entry is tagged t (its key is *held*); so
+ * with nkeys = 2 every picture of the previous GOP stays exportable after the
+ * next key picture was decoded.  Older pictures, pictures decoded before
+ * retention went on, slots nothing was decoded into, slots
+ * h264mi_engine_forget_records was called for, and the pictures of a GOP whose
+ * key picture's slot was decoded into again later in the key picture's own
+ * batch (nothing is left to copy behind that launch) have no key and export
+ * zeros.
+ * The decode_device* launches retain nothing.  0 (the default: nothing is
+ * allocated or queued) waits for the engine's stream and frees the frames; a
+ * different nkeys starts again from nothing.  -1 on a bad argument or a HIP
+ * error. */
+int  h264mi_engine_keep_accres(h264mi_engine *e, int nkeys);
+/* 1: the key picture of the slot's picture is held, 0: it is not (the slot
+ * exports zeros), -1: retention is off or a bad stream or slot */
+int  h264mi_engine_accres_held(h264mi_engine *e, int stream, int slot);
+/* the accumulated residual of the slots (streams[k], slots[k]), k < n, against
+ * the keys held for them, as tensors in the caller's memory, ordered as
+ * h264mi_engine_export_accmv orders its export.  -1 when retention is off, on a
+ * bad stream, slot or desc, or when d_out is not on the engine's device. */
+int  h264mi_engine_export_accres(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                 const h264mi_accres_desc *desc, void *d_out, size_t out_stride, void *hip_stream);
 int  h264mi_engine_sync(h264mi_engine *e);
 /* number of (launch, picture) slots flagged since the last call: residual
  * range errors (reference transform.c:181) or a bounded wait that expired;
