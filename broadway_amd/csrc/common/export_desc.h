@@ -41,6 +41,22 @@ static inline int export_aligned(const void *d_out, size_t out_stride, size_t es
     return !(((size_t)(uintptr_t)d_out | out_stride) & (es - 1));
 }
 
+/* a window in luma samples of the MB-aligned picture; even: x, y, cw and ch are all even */
+static inline int export_luma_window_ok(int x, int y, int cw, int ch, int w_mbs, int h_mbs, int even)
+{
+    return x >= 0 && y >= 0 && cw >= 1 && ch >= 1 && cw <= 16 * w_mbs - x && ch <= 16 * h_mbs - y &&
+           (!even || !((x | y | cw | ch) & 1));
+}
+
+/* a channel list: 1..max ids, each below n */
+static inline int export_ids_ok(const int *id, int count, int max, int n)
+{
+    if (count < 1 || count > max) return 0;
+    for (int c = 0; c < count; c++)
+        if (id[c] < 0 || id[c] >= n) return 0;
+    return 1;
+}
+
 /* h264mi_tensor_desc: a pixel window is even and lies inside width x height */
 static inline int tensor_desc_fixed_ok(const h264mi_tensor_desc *t)
 {
@@ -69,10 +85,7 @@ static inline int resize_window_ok(const h264mi_tensor_resize_desc *d, int width
 /* h264mi_mbinfo_desc: the window is in 4x4 blocks of a w_mbs x h_mbs picture */
 static inline int mbinfo_desc_fixed_ok(const h264mi_mbinfo_desc *d)
 {
-    if (d->nch < 1 || d->nch > H264MI_MBINFO_MAX_CH || !export_dtype_field(d->dtype)) return 0;
-    for (int c = 0; c < d->nch; c++)
-        if (d->ch[c] < 0 || d->ch[c] >= H264MI_MBINFO_NCHANNELS) return 0;
-    return 1;
+    return export_ids_ok(d->ch, d->nch, H264MI_MBINFO_MAX_CH, H264MI_MBINFO_NCHANNELS) && export_dtype_field(d->dtype);
 }
 
 static inline int mbinfo_window_ok(const h264mi_mbinfo_desc *d, int w_mbs, int h_mbs)
@@ -90,8 +103,7 @@ static inline int residual_desc_fixed_ok(const h264mi_residual_desc *d)
 
 static inline int residual_window_ok(const h264mi_residual_desc *d, int w_mbs, int h_mbs)
 {
-    return d->x >= 0 && d->y >= 0 && d->cw >= 1 && d->ch >= 1 && d->cw <= 16 * w_mbs - d->x &&
-           d->ch <= 16 * h_mbs - d->y && (d->planes != H264MI_RESID_UV || !((d->x | d->y | d->cw | d->ch) & 1));
+    return export_luma_window_ok(d->x, d->y, d->cw, d->ch, w_mbs, h_mbs, d->planes == H264MI_RESID_UV);
 }
 
 /* h264mi_accmv_desc: an origin map holds 15-bit coordinates, and the window is
@@ -103,16 +115,12 @@ static inline int accmv_size_ok(int w_mbs, int h_mbs)
 
 static inline int accmv_desc_fixed_ok(const h264mi_accmv_desc *d)
 {
-    if (d->nch < 1 || d->nch > H264MI_ACCMV_MAX_CH || !export_dtype_field(d->dtype)) return 0;
-    for (int c = 0; c < d->nch; c++)
-        if (d->id[c] < 0 || d->id[c] >= H264MI_ACCMV_NCHANNELS) return 0;
-    return 1;
+    return export_ids_ok(d->id, d->nch, H264MI_ACCMV_MAX_CH, H264MI_ACCMV_NCHANNELS) && export_dtype_field(d->dtype);
 }
 
 static inline int accmv_window_ok(const h264mi_accmv_desc *d, int w_mbs, int h_mbs)
 {
-    return accmv_size_ok(w_mbs, h_mbs) && d->x >= 0 && d->y >= 0 && d->cw >= 1 && d->ch >= 1 &&
-           d->cw <= 16 * w_mbs - d->x && d->ch <= 16 * h_mbs - d->y;
+    return accmv_size_ok(w_mbs, h_mbs) && export_luma_window_ok(d->x, d->y, d->cw, d->ch, w_mbs, h_mbs, 0);
 }
 
 /* h264mi_accres_desc: planes, element type, a colour id 0..3 (never
@@ -127,9 +135,8 @@ static inline int accres_desc_fixed_ok(const h264mi_accres_desc *d)
 
 static inline int accres_window_ok(const h264mi_accres_desc *d, int w_mbs, int h_mbs)
 {
-    return accmv_size_ok(w_mbs, h_mbs) && d->x >= 0 && d->y >= 0 && d->cw >= 1 && d->ch >= 1 &&
-           d->cw <= 16 * w_mbs - d->x && d->ch <= 16 * h_mbs - d->y &&
-           (d->planes != H264MI_ACCRES_UV || !((d->x | d->y | d->cw | d->ch) & 1));
+    return accmv_size_ok(w_mbs, h_mbs) &&
+           export_luma_window_ok(d->x, d->y, d->cw, d->ch, w_mbs, h_mbs, d->planes == H264MI_ACCRES_UV);
 }
 
 /* An SPS's crop window in luma samples (the whole picture without cropping;

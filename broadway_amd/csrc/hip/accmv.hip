@@ -178,20 +178,8 @@ __global__ __launch_bounds__(256) void k_accmv(const accmv_args a)
         uint8_t *d = O + (((size_t)c * a.ch + yy) * a.cw + col) * ES;
         uint32_t e[NE];
 #pragma unroll
-        for (int k = 0; k < NE; k++) e[k] = mbinfo_elem<DT>(accmv_value(id, w[k], X + k, Y), s, bb);
-        if constexpr (V16) {
-            crop_u32x4 o;
-            if constexpr (ES == 2) {
-                o.x = e[0] | e[1] << 16; o.y = e[2] | e[3] << 16;
-                o.z = e[4] | e[5] << 16; o.w = e[6] | e[7] << 16;
-            } else {
-                o.x = e[0]; o.y = e[1]; o.z = e[2]; o.w = e[3];
-            }
-            __builtin_nontemporal_store(o, (crop_u32x4 *)d);
-        } else {
-            if constexpr (ES == 2) __builtin_nontemporal_store((uint16_t)e[0], (uint16_t *)d);
-            else __builtin_nontemporal_store(e[0], (uint32_t *)d);
-        }
+        for (int k = 0; k < NE; k++) e[k] = field_elem<DT>(accmv_value(id, w[k], X + k, Y), s, bb);
+        field_store<DT, V16>(e, d);
     }
 }
 
@@ -201,11 +189,5 @@ static void accmv_launch(int dt, bool v16, int npics, hipStream_t st, const accm
     const int ne = v16 ? 16 / tensor_elem_size(dt) : 1;
     const unsigned ni = (unsigned)(a.cw / ne) * (unsigned)a.ch;
     const dim3 grid((ni + 255) / 256, 1, npics), block(256);
-#define ACCMV_CASE(D)                                                               \
-    if (dt == D) {                                                                  \
-        if (v16) hipLaunchKernelGGL((k_accmv<D, true>), grid, block, 0, st, a);     \
-        else hipLaunchKernelGGL((k_accmv<D, false>), grid, block, 0, st, a);        \
-    }
-    ACCMV_CASE(TENSOR_F16) ACCMV_CASE(TENSOR_BF16) ACCMV_CASE(TENSOR_F32) ACCMV_CASE(TENSOR_I16)
-#undef ACCMV_CASE
+    FIELD_LAUNCH(k_accmv, dt, v16, grid, block, 0, st, a);
 }

@@ -248,20 +248,8 @@ __global__ __launch_bounds__(256) void k_accres(const accres_args a)
         uint8_t *d = O + (((size_t)c * OH + yy) * OW + col) * ES;
         uint32_t e[NE];
 #pragma unroll
-        for (int k = 0; k < NE; k++) e[k] = mbinfo_elem<DT>(v[c][k], s, bb);
-        if constexpr (V16) {
-            crop_u32x4 o;
-            if constexpr (ES == 2) {
-                o.x = e[0] | e[1] << 16; o.y = e[2] | e[3] << 16;
-                o.z = e[4] | e[5] << 16; o.w = e[6] | e[7] << 16;
-            } else {
-                o.x = e[0]; o.y = e[1]; o.z = e[2]; o.w = e[3];
-            }
-            __builtin_nontemporal_store(o, (crop_u32x4 *)d);
-        } else {
-            if constexpr (ES == 2) __builtin_nontemporal_store((uint16_t)e[0], (uint16_t *)d);
-            else __builtin_nontemporal_store(e[0], (uint32_t *)d);
-        }
+        for (int k = 0; k < NE; k++) e[k] = field_elem<DT>(v[c][k], s, bb);
+        field_store<DT, V16>(e, d);
     }
 }
 
@@ -272,11 +260,5 @@ static void accres_launch(int dt, bool v16, int npics, hipStream_t st, const acc
     const int ne = v16 ? 16 / tensor_elem_size(dt) : 1;
     const unsigned ni = (unsigned)((a.cw >> hs) / ne) * (unsigned)(a.ch >> hs);
     const dim3 grid((ni + 255) / 256, 1, npics), block(256);
-#define ACCRES_CASE(D)                                                              \
-    if (dt == D) {                                                                  \
-        if (v16) hipLaunchKernelGGL((k_accres<D, true>), grid, block, 0, st, a);    \
-        else hipLaunchKernelGGL((k_accres<D, false>), grid, block, 0, st, a);       \
-    }
-    ACCRES_CASE(TENSOR_F16) ACCRES_CASE(TENSOR_BF16) ACCRES_CASE(TENSOR_F32) ACCRES_CASE(TENSOR_I16)
-#undef ACCRES_CASE
+    FIELD_LAUNCH(k_accres, dt, v16, grid, block, 0, st, a);
 }

@@ -7,6 +7,7 @@
 #include "crop.hip"
 #include "tensor.hip"
 #include "resize.hip"
+#include "field_store.h"
 #include "mbinfo.hip"
 #include "residual.hip"
 #include "accmv.hip"

@@ -76,14 +76,6 @@ __device__ __forceinline__ int mbinfo_value(int id, const uint32_t *r, int b)
     }
 }
 
-// v as the element type's bits
-template <int DT>
-__device__ __forceinline__ uint32_t mbinfo_elem(int v, float s, float b)
-{
-    if constexpr (DT == TENSOR_I16) return (uint32_t)v & 0xFFFFu;
-    else return tensor_float_bits<DT>(__builtin_fmaf((float)v, s, b));
-}
-
 // a V16 item: the 16 / ES elements from column S (= its first column's
 // position inside its MB, a compile-time constant, the same for every item of
 // a launch: bx & 3) of the MB whose record is r0, block row bits yb = (y >> 1)
@@ -98,16 +90,9 @@ __device__ __forceinline__ void mbinfo_item16(int id, const uint32_t *r0, int yb
 #pragma unroll
     for (int k = 0; k < NE; k++) {
         const int x = (S + k) & 3;
-        e[k] = mbinfo_elem<DT>(mbinfo_value(id, r0 + ((S + k) >> 2) * MBINFO_LDS_STRIDE, yb + ((x & 2) << 1) + (x & 1)), s, bb);
+        e[k] = field_elem<DT>(mbinfo_value(id, r0 + ((S + k) >> 2) * MBINFO_LDS_STRIDE, yb + ((x & 2) << 1) + (x & 1)), s, bb);
     }
-    crop_u32x4 o;
-    if constexpr (ES == 2) {
-        o.x = e[0] | e[1] << 16; o.y = e[2] | e[3] << 16;
-        o.z = e[4] | e[5] << 16; o.w = e[6] | e[7] << 16;
-    } else {
-        o.x = e[0]; o.y = e[1]; o.z = e[2]; o.w = e[3];
-    }
-    __builtin_nontemporal_store(o, (crop_u32x4 *)d);
+    field_store<DT, true>(e, d);
 }
 
 // grid: (ceil(bw / MBINFO_COLS), MB rows the window touches, pictures of this launch)
@@ -152,9 +137,8 @@ __global__ __launch_bounds__(64) void k_mbinfo(const mbinfo_args a)
                 default: mbinfo_item16<DT, 3>(id, r, yb, s, bb, d); break;
                 }
             } else {
-                const uint32_t e = mbinfo_elem<DT>(mbinfo_value(id, r, yb + ((X & 2) << 1) + (X & 1)), s, bb);
-                if constexpr (ES == 2) __builtin_nontemporal_store((uint16_t)e, (uint16_t *)d);
-                else __builtin_nontemporal_store(e, (uint32_t *)d);
+                const uint32_t e[1] = {field_elem<DT>(mbinfo_value(id, r, yb + ((X & 2) << 1) + (X & 1)), s, bb)};
+                field_store<DT, false>(e, d);
             }
         }
     }
@@ -164,11 +148,5 @@ __global__ __launch_bounds__(64) void k_mbinfo(const mbinfo_args a)
 static void mbinfo_launch(int dt, bool v16, int npics, hipStream_t st, const mbinfo_args &a)
 {
     const dim3 grid((a.bw + MBINFO_COLS - 1) / MBINFO_COLS, ((a.by + a.bh - 1) >> 2) - (a.by >> 2) + 1, npics), block(64);
-#define MBINFO_CASE(D)                                                                \
-    if (dt == D) {                                                                    \
-        if (v16) hipLaunchKernelGGL((k_mbinfo<D, true>), grid, block, 0, st, a);      \
-        else hipLaunchKernelGGL((k_mbinfo<D, false>), grid, block, 0, st, a);         \
-    }
-    MBINFO_CASE(TENSOR_F16) MBINFO_CASE(TENSOR_BF16) MBINFO_CASE(TENSOR_F32) MBINFO_CASE(TENSOR_I16)
-#undef MBINFO_CASE
+    FIELD_LAUNCH(k_mbinfo, dt, v16, grid, block, 0, st, a);
 }

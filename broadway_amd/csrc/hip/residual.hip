@@ -143,14 +143,6 @@ __device__ __forceinline__ void resid_block(int type, uint32_t cb, uint32_t m, i
     }
 }
 
-// v as the element type's bits
-template <int DT>
-__device__ __forceinline__ uint32_t resid_elem(int v, float s, float b)
-{
-    if constexpr (DT == TENSOR_I16) return (uint32_t)v & 0xFFFFu;
-    else return tensor_float_bits<DT>(__builtin_fmaf((float)v, s, b));
-}
-
 // grid: (ceil(cw / RESID_COLS), MB rows the window touches, pictures of this launch)
 template <int DT, bool V16>
 __global__ __launch_bounds__(256) void k_residual(const residual_args a)
@@ -223,23 +215,10 @@ __global__ __launch_bounds__(256) void k_residual(const residual_args a)
             const int Y = or0 + yy, X = (a.x >> hs) + col;
             const int16_t *row = src + ((Y >> sh) - rb) * RESID_LDS_STRIDE - cb0;
             uint8_t *d = O + (((size_t)c * OH + (Y - (a.y >> hs))) * OW + col) * ES;
-            if constexpr (V16) {
-                uint32_t e[NE];
+            uint32_t e[NE];
 #pragma unroll
-                for (int k = 0; k < NE; k++) e[k] = resid_elem<DT>(row[(X + k) >> sh], s, bb);
-                crop_u32x4 q;
-                if constexpr (ES == 2) {
-                    q.x = e[0] | e[1] << 16; q.y = e[2] | e[3] << 16;
-                    q.z = e[4] | e[5] << 16; q.w = e[6] | e[7] << 16;
-                } else {
-                    q.x = e[0]; q.y = e[1]; q.z = e[2]; q.w = e[3];
-                }
-                __builtin_nontemporal_store(q, (crop_u32x4 *)d);
-            } else {
-                const uint32_t e = resid_elem<DT>(row[X >> sh], s, bb);
-                if constexpr (ES == 2) __builtin_nontemporal_store((uint16_t)e, (uint16_t *)d);
-                else __builtin_nontemporal_store(e, (uint32_t *)d);
-            }
+            for (int k = 0; k < NE; k++) e[k] = field_elem<DT>(row[(X + k) >> sh], s, bb);
+            field_store<DT, V16>(e, d);
         }
     }
 }
@@ -248,11 +227,5 @@ __global__ __launch_bounds__(256) void k_residual(const residual_args a)
 static void residual_launch(int dt, bool v16, int npics, hipStream_t st, const residual_args &a)
 {
     const dim3 grid((a.cw + RESID_COLS - 1) / RESID_COLS, ((a.y + a.ch - 1) >> 4) - (a.y >> 4) + 1, npics), block(256);
-#define RESID_CASE(D)                                                                   \
-    if (dt == D) {                                                                      \
-        if (v16) hipLaunchKernelGGL((k_residual<D, true>), grid, block, 0, st, a);      \
-        else hipLaunchKernelGGL((k_residual<D, false>), grid, block, 0, st, a);         \
-    }
-    RESID_CASE(TENSOR_F16) RESID_CASE(TENSOR_BF16) RESID_CASE(TENSOR_F32) RESID_CASE(TENSOR_I16)
-#undef RESID_CASE
+    FIELD_LAUNCH(k_residual, dt, v16, grid, block, 0, st, a);
 }

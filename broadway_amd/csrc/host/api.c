@@ -324,110 +324,100 @@ int H264SwDecLastTensorColour(H264SwDecInst decInst)
     return ((DecContainer *)decInst)->dec.last_tensor_colour1 - 1;
 }
 
-/* Record retention for H264SwDecLastPictureMbInfo (include/h264mi.h): the
- * backend keeps it across configure, so it may be called before the headers */
-H264SwDecRet H264SwDecKeepMbInfo(H264SwDecInst decInst, u32 on)
+/* The kept fields (decoder.h's H264_KEEP_*) behind the H264SwDecKeep* /
+ * H264SwDecLastPicture* call pairs (include/h264mi.h): a field's descriptor
+ * type and its two rules (common/export_desc.h).  Every field descriptor
+ * starts like FieldHead; `blocks`: the window is in 4x4 blocks and absent when
+ * its width is 0 (then: the blocks covering the crop window), else it is in
+ * luma samples and absent when width and height are 0 (then: the crop window). */
+typedef struct { int x, y, cw, ch, count, dtype; } FieldHead;
+typedef union {
+    FieldHead head;
+    h264mi_mbinfo_desc mbinfo;
+    h264mi_residual_desc residual;
+    h264mi_accmv_desc accmv;
+} FieldDesc;
+
+static int mbinfo_fixed(const FieldDesc *d) { return mbinfo_desc_fixed_ok(&d->mbinfo); }
+static int mbinfo_window(const FieldDesc *d, int w_mbs, int h_mbs) { return mbinfo_window_ok(&d->mbinfo, w_mbs, h_mbs); }
+static int residual_fixed(const FieldDesc *d) { return residual_desc_fixed_ok(&d->residual); }
+static int residual_window(const FieldDesc *d, int w_mbs, int h_mbs) { return residual_window_ok(&d->residual, w_mbs, h_mbs); }
+static int accmv_fixed(const FieldDesc *d) { return accmv_desc_fixed_ok(&d->accmv); }
+static int accmv_window(const FieldDesc *d, int w_mbs, int h_mbs) { return accmv_window_ok(&d->accmv, w_mbs, h_mbs); }
+
+static const struct {
+    size_t size;
+    int (*fixed_ok)(const FieldDesc *d);
+    int (*window_ok)(const FieldDesc *d, int w_mbs, int h_mbs);
+    int blocks;
+} field_rules[H264_KEEP_KINDS] = {
+    [H264_KEEP_RECORDS] = {sizeof(h264mi_mbinfo_desc), mbinfo_fixed, mbinfo_window, 1},
+    [H264_KEEP_COEFS] = {sizeof(h264mi_residual_desc), residual_fixed, residual_window, 0},
+    [H264_KEEP_ACCMV] = {sizeof(h264mi_accmv_desc), accmv_fixed, accmv_window, 0},
+};
+
+/* Retention of a kind for its H264SwDecLastPicture* call: the backend keeps it
+ * across configure, so it may be called before the headers */
+static H264SwDecRet keep_field(H264SwDecInst decInst, int kind, u32 on)
 {
     if (decInst == NULL) return H264SWDEC_PARAM_ERR;
     DecContainer *c = (DecContainer *)decInst;
-    if (!c->dec.be.keep_records || !c->dec.be.export_mbinfo) return H264SWDEC_PARAM_ERR;
-    if (c->dec.be.keep_records(c->dec.be.ctx, on != 0)) return H264SWDEC_PARAM_ERR;
-    c->dec.keep_mbinfo = on != 0;
+    if (!c->dec.be.field[kind].keep || !c->dec.be.field[kind].export_field) return H264SWDEC_PARAM_ERR;
+    if (c->dec.be.field[kind].keep(c->dec.be.ctx, kind, on != 0)) return H264SWDEC_PARAM_ERR;
+    c->dec.keep[kind] = on != 0;
     return H264SWDEC_OK;
 }
 
-/* The MB side-information field of the picture the last H264SwDecNextPicture*
- * call delivered (include/h264mi.h); desc->bw == 0: the blocks covering the
- * active SPS's crop window.  The DPB is not touched.  Everything the export
- * can refuse is checked before anything is queued. */
+/* The field of a kind of the picture the last H264SwDecNextPicture* call
+ * delivered.  The DPB is not touched.  Everything the export can refuse is
+ * checked before anything is queued. */
+static H264SwDecRet last_picture_field(H264SwDecInst decInst, int kind, const void *desc, void *d_dst, void *hip_stream)
+{
+    if (decInst == NULL || desc == NULL || d_dst == NULL) return H264SWDEC_PARAM_ERR;
+    DecContainer *c = (DecContainer *)decInst;
+    if (!c->dec.be.field[kind].export_field || !c->dec.keep[kind]) return H264SWDEC_PARAM_ERR;
+    FieldDesc m;
+    memcpy(&m, desc, field_rules[kind].size);
+    if (!field_rules[kind].fixed_ok(&m) || !export_aligned(d_dst, 0, export_elem_size(m.head.dtype))) return H264SWDEC_PARAM_ERR;
+    const Sps *s = h264dec_active_sps(&c->dec);
+    if (!s || !c->dec.last_out_slot1) return H264SWDEC_OK;      /* no picture delivered */
+    if (m.head.cw == 0 && (field_rules[kind].blocks || m.head.ch == 0)) {
+        export_window w = sps_crop_window(s);
+        if (field_rules[kind].blocks) w = export_window_blocks(w);
+        m.head.x = w.x; m.head.y = w.y; m.head.cw = w.cw; m.head.ch = w.ch;
+    }
+    if (!field_rules[kind].window_ok(&m, s->w_mbs, s->h_mbs)) return H264SWDEC_PARAM_ERR;
+    if (c->dec.be.field[kind].export_field(c->dec.be.ctx, kind, c->dec.last_out_slot1 - 1, &m, d_dst, hip_stream))
+        return H264SWDEC_PARAM_ERR;         /* (d_dst not on the decoder's GPU) */
+    return H264SWDEC_PIC_RDY;
+}
+
+/* Record retention and the MB side-information field; desc->bw == 0: the
+ * blocks covering the active SPS's crop window */
+H264SwDecRet H264SwDecKeepMbInfo(H264SwDecInst decInst, u32 on) { return keep_field(decInst, H264_KEEP_RECORDS, on); }
+
 H264SwDecRet H264SwDecLastPictureMbInfo(H264SwDecInst decInst, const h264mi_mbinfo_desc *desc, void *d_dst,
                                         void *hip_stream)
 {
-    if (decInst == NULL || desc == NULL || d_dst == NULL) return H264SWDEC_PARAM_ERR;
-    DecContainer *c = (DecContainer *)decInst;
-    if (!c->dec.be.export_mbinfo || !c->dec.keep_mbinfo) return H264SWDEC_PARAM_ERR;
-    h264mi_mbinfo_desc m = *desc;
-    if (!mbinfo_desc_fixed_ok(&m) || !export_aligned(d_dst, 0, export_elem_size(m.dtype))) return H264SWDEC_PARAM_ERR;
-    const Sps *s = h264dec_active_sps(&c->dec);
-    if (!s || !c->dec.last_out_slot1) return H264SWDEC_OK;      /* no picture delivered */
-    if (m.bw == 0) {
-        const export_window b = export_window_blocks(sps_crop_window(s));
-        m.bx = b.x; m.by = b.y; m.bw = b.cw; m.bh = b.ch;
-    }
-    if (!mbinfo_window_ok(&m, s->w_mbs, s->h_mbs)) return H264SWDEC_PARAM_ERR;
-    if (c->dec.be.export_mbinfo(c->dec.be.ctx, c->dec.last_out_slot1 - 1, &m, d_dst, hip_stream))
-        return H264SWDEC_PARAM_ERR;         /* (d_dst not on the decoder's GPU) */
-    return H264SWDEC_PIC_RDY;
+    return last_picture_field(decInst, H264_KEEP_RECORDS, desc, d_dst, hip_stream);
 }
 
-/* Coefficient retention for H264SwDecLastPictureResidual (include/h264mi.h) */
-H264SwDecRet H264SwDecKeepResidual(H264SwDecInst decInst, u32 on)
-{
-    if (decInst == NULL) return H264SWDEC_PARAM_ERR;
-    DecContainer *c = (DecContainer *)decInst;
-    if (!c->dec.be.keep_coefs || !c->dec.be.export_residual) return H264SWDEC_PARAM_ERR;
-    if (c->dec.be.keep_coefs(c->dec.be.ctx, on != 0)) return H264SWDEC_PARAM_ERR;
-    c->dec.keep_residual = on != 0;
-    return H264SWDEC_OK;
-}
+/* Coefficient retention and the residual; desc->cw == desc->ch == 0: the active SPS's crop window */
+H264SwDecRet H264SwDecKeepResidual(H264SwDecInst decInst, u32 on) { return keep_field(decInst, H264_KEEP_COEFS, on); }
 
-/* The residual of the picture the last H264SwDecNextPicture* call delivered
- * (include/h264mi.h); desc->cw == desc->ch == 0: the active SPS's crop window.
- * The DPB is not touched.  Everything the export can refuse is checked before
- * anything is queued. */
 H264SwDecRet H264SwDecLastPictureResidual(H264SwDecInst decInst, const h264mi_residual_desc *desc, void *d_dst,
                                           void *hip_stream)
 {
-    if (decInst == NULL || desc == NULL || d_dst == NULL) return H264SWDEC_PARAM_ERR;
-    DecContainer *c = (DecContainer *)decInst;
-    if (!c->dec.be.export_residual || !c->dec.keep_residual) return H264SWDEC_PARAM_ERR;
-    h264mi_residual_desc m = *desc;
-    if (!residual_desc_fixed_ok(&m) || !export_aligned(d_dst, 0, export_elem_size(m.dtype))) return H264SWDEC_PARAM_ERR;
-    const Sps *s = h264dec_active_sps(&c->dec);
-    if (!s || !c->dec.last_out_slot1) return H264SWDEC_OK;      /* no picture delivered */
-    if (m.cw == 0 && m.ch == 0) {
-        const export_window w = sps_crop_window(s);
-        m.x = w.x; m.y = w.y; m.cw = w.cw; m.ch = w.ch;
-    }
-    if (!residual_window_ok(&m, s->w_mbs, s->h_mbs)) return H264SWDEC_PARAM_ERR;
-    if (c->dec.be.export_residual(c->dec.be.ctx, c->dec.last_out_slot1 - 1, &m, d_dst, hip_stream))
-        return H264SWDEC_PARAM_ERR;         /* (d_dst not on the decoder's GPU) */
-    return H264SWDEC_PIC_RDY;
+    return last_picture_field(decInst, H264_KEEP_COEFS, desc, d_dst, hip_stream);
 }
 
-/* Origin-map retention for H264SwDecLastPictureAccMotion (include/h264mi.h) */
-H264SwDecRet H264SwDecKeepAccMotion(H264SwDecInst decInst, u32 on)
-{
-    if (decInst == NULL) return H264SWDEC_PARAM_ERR;
-    DecContainer *c = (DecContainer *)decInst;
-    if (!c->dec.be.keep_accmv || !c->dec.be.export_accmv) return H264SWDEC_PARAM_ERR;
-    if (c->dec.be.keep_accmv(c->dec.be.ctx, on != 0)) return H264SWDEC_PARAM_ERR;
-    c->dec.keep_accmv = on != 0;
-    return H264SWDEC_OK;
-}
+/* Origin-map retention and the accumulated motion; desc->cw == desc->ch == 0: the active SPS's crop window */
+H264SwDecRet H264SwDecKeepAccMotion(H264SwDecInst decInst, u32 on) { return keep_field(decInst, H264_KEEP_ACCMV, on); }
 
-/* The accumulated motion of the picture the last H264SwDecNextPicture* call
- * delivered (include/h264mi.h); desc->cw == desc->ch == 0: the active SPS's
- * crop window.  The DPB is not touched.  Everything the export can refuse is
- * checked before anything is queued. */
 H264SwDecRet H264SwDecLastPictureAccMotion(H264SwDecInst decInst, const h264mi_accmv_desc *desc, void *d_dst,
                                            void *hip_stream)
 {
-    if (decInst == NULL || desc == NULL || d_dst == NULL) return H264SWDEC_PARAM_ERR;
-    DecContainer *c = (DecContainer *)decInst;
-    if (!c->dec.be.export_accmv || !c->dec.keep_accmv) return H264SWDEC_PARAM_ERR;
-    h264mi_accmv_desc m = *desc;
-    if (!accmv_desc_fixed_ok(&m) || !export_aligned(d_dst, 0, export_elem_size(m.dtype))) return H264SWDEC_PARAM_ERR;
-    const Sps *s = h264dec_active_sps(&c->dec);
-    if (!s || !c->dec.last_out_slot1) return H264SWDEC_OK;      /* no picture delivered */
-    if (m.cw == 0 && m.ch == 0) {
-        const export_window w = sps_crop_window(s);
-        m.x = w.x; m.y = w.y; m.cw = w.cw; m.ch = w.ch;
-    }
-    if (!accmv_window_ok(&m, s->w_mbs, s->h_mbs)) return H264SWDEC_PARAM_ERR;
-    if (c->dec.be.export_accmv(c->dec.be.ctx, c->dec.last_out_slot1 - 1, &m, d_dst, hip_stream))
-        return H264SWDEC_PARAM_ERR;         /* (d_dst not on the decoder's GPU) */
-    return H264SWDEC_PIC_RDY;
+    return last_picture_field(decInst, H264_KEEP_ACCMV, desc, d_dst, hip_stream);
 }
 
 H264SwDecRet H264SwDecGetTiming(H264SwDecInst decInst, double *parse_s, double *submit_s, double *wait_s,

@@ -22,6 +22,11 @@ extern "C" {
 /* 1 when H264MI_TEST=1: the test hooks are honoured (capture.c) */
 int h264mi_test_hooks(void);
 
+/* What a backend can keep of each picture on the device, and the field export
+ * that reads it: the records (MB side information), the coefficient blocks
+ * (residual), the origin maps (accumulated motion) */
+enum { H264_KEEP_RECORDS = 0, H264_KEEP_COEFS, H264_KEEP_ACCMV, H264_KEEP_KINDS };
+
 /* Reconstruction backend interface (the device boundary). */
 typedef struct H264Backend {
     void *ctx;
@@ -54,22 +59,16 @@ typedef struct H264Backend {
     int  (*export_tensor)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
     /* the same, resized on the GPU (desc: a checked h264mi_tensor_resize_desc) */
     int  (*export_tensor_resized)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
-    /* optional: from the next decode on, keep (on != 0) each picture's records
-     * on the device until its slot is decoded into again; survives configure */
-    int  (*keep_records)(void *ctx, int on);
-    /* optional: the kept records of slot as the MB side-information field of
-     * desc (a checked h264mi_mbinfo_desc) into device memory d_dst, ordered on
-     * hip_stream like export_tensor; 0 ok, -1 failure */
-    int  (*export_mbinfo)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
-    /* optional: the same for each picture's coefficient blocks (and its
-     * records), and slot's kept picture as the residual tensor of desc (a
-     * checked h264mi_residual_desc) */
-    int  (*keep_coefs)(void *ctx, int on);
-    int  (*export_residual)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
-    /* optional: the same for each picture's origin map (accumulated motion),
-     * and slot's kept map as the tensor of desc (a checked h264mi_accmv_desc) */
-    int  (*keep_accmv)(void *ctx, int on);
-    int  (*export_accmv)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
+    /* optional, per kept field (H264_KEEP_*; a backend without one leaves its
+     * pair NULL).  keep: from the next decode on, keep (on != 0) each
+     * picture's data of that kind on the device until its slot is decoded
+     * into again; survives configure.  export_field: slot's kept data as the
+     * field of desc (a checked descriptor of the kind's type) into device
+     * memory d_dst, ordered on hip_stream like export_tensor; 0 ok, -1 failure */
+    struct {
+        int  (*keep)(void *ctx, int kind, int on);
+        int  (*export_field)(void *ctx, int kind, int slot, const void *desc, void *d_dst, void *hip_stream);
+    } field[H264_KEEP_KINDS];
     /* optional: host memory for the output frames (pinned by the HIP
      * backend, so each picture's D2H copy runs at DMA speed); NULL: malloc */
     void *(*host_alloc)(void *ctx, size_t bytes);
@@ -146,12 +145,10 @@ typedef struct H264Dec {
      * out_frames are not started (nobody reads them); a plain next_output
      * clears it and reads synchronously until the copies are back */
     int      out_cropped;
-    /* the backend keeps records (H264SwDecKeepMbInfo), and the slot of the
-     * picture the last next_output of any kind delivered, plus one (0: none
-     * since the last H264SwDecDecode) */
-    int      keep_mbinfo;
-    int      keep_residual;     /* the same for the coefficients (H264SwDecKeepResidual) */
-    int      keep_accmv;        /* the same for the origin maps (H264SwDecKeepAccMotion) */
+    /* the backend keeps that kind (H264SwDecKeepMbInfo / KeepResidual /
+     * KeepAccMotion), and the slot of the picture the last next_output of any
+     * kind delivered, plus one (0: none since the last H264SwDecDecode) */
+    int      keep[H264_KEEP_KINDS];
     int      last_out_slot1;
     /* the colour id of the last tensor delivered (include/h264mi.h), plus one (0: none yet) */
     int      last_tensor_colour1;

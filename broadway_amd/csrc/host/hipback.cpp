@@ -193,9 +193,7 @@ struct HipBackendCtx {
     unsigned ndecodes, force_flag_at;
     int nslots;
     unsigned enq, synced;   // work items queued on the engine's stream / of those, waited for by hb_sync
-    bool keep;              // keep_records: asked for by the decoder, applied to every engine configured from then on
-    bool keepc;             // keep_coefs: the same
-    bool keepa;             // keep_accmv: the same
+    bool keep[H264_KEEP_KINDS];     // asked for by the decoder, applied to every engine configured from then on
 };
 
 extern "C" int h264mi_set_share(int lanes)
@@ -324,43 +322,14 @@ static bool wait_launched(SharedEng *sh, unsigned long long mine)
 }
 
 // Weak like the crop and tensor entry points below: a backend built against
-// the CPU stand-in of the engine leaves keep_records and keep_coefs NULL.
+// the CPU stand-in of the engine leaves the kept fields' pairs NULL.
 extern "C" int h264mi_engine_keep_records(h264mi_engine *e, int on) __attribute__((weak));
 extern "C" int h264mi_engine_forget_records(h264mi_engine *e, int stream, int slot) __attribute__((weak));
 extern "C" int h264mi_engine_keep_coefs(h264mi_engine *e, int on) __attribute__((weak));
 extern "C" int h264mi_engine_keep_accmv(h264mi_engine *e, int on) __attribute__((weak));
 
-// The decoder's switch `on` (c->keep, c->keepc) onto the instance's engine
-// through h264mi_engine_keep_records / _keep_coefs.  A shared engine's
-// retention is only ever switched on: its other instances may be using it.
-static int hb_keep_apply(HipBackendCtx *c, int (*engine_keep)(h264mi_engine *, int), bool on)
-{
-    if (!c->sh) return engine_keep(c->e, on);
-    if (!on) return 0;
-    std::lock_guard<std::mutex> l(c->sh->mu);
-    return engine_keep(c->e, 1);
-}
-
-static int hb_keep_records(void *vctx, int on)
-{
-    HipBackendCtx *c = (HipBackendCtx *)vctx;
-    c->keep = on != 0;
-    return c->e ? hb_keep_apply(c, h264mi_engine_keep_records, c->keep) : 0;
-}
-
-static int hb_keep_coefs(void *vctx, int on)
-{
-    HipBackendCtx *c = (HipBackendCtx *)vctx;
-    c->keepc = on != 0;
-    return c->e ? hb_keep_apply(c, h264mi_engine_keep_coefs, c->keepc) : 0;
-}
-
-static int hb_keep_accmv(void *vctx, int on)
-{
-    HipBackendCtx *c = (HipBackendCtx *)vctx;
-    c->keepa = on != 0;
-    return c->e ? hb_keep_apply(c, h264mi_engine_keep_accmv, c->keepa) : 0;
-}
+// the decoder's switch for a kept field onto the instance's engine (hb_fields, below the exports)
+static int hb_keep_apply(HipBackendCtx *c, int kind, bool on);
 
 static int hb_configure(void *vctx, int w_mbs, int h_mbs, int nslots)
 {
@@ -383,9 +352,8 @@ static int hb_configure(void *vctx, int w_mbs, int h_mbs, int nslots)
         c->lane = 0;
         c->e = engine_get(c->device, w_mbs, h_mbs, 1, nslots);
     }
-    if (c->e && c->keep && hb_keep_apply(c, h264mi_engine_keep_records, true)) return -1;
-    if (c->e && c->keepc && hb_keep_apply(c, h264mi_engine_keep_coefs, true)) return -1;
-    if (c->e && c->keepa && hb_keep_apply(c, h264mi_engine_keep_accmv, true)) return -1;
+    for (int k = 0; k < H264_KEEP_KINDS; k++)
+        if (c->e && c->keep[k] && hb_keep_apply(c, k, true)) return -1;
     return c->e && c->pref ? 0 : -1;
 }
 
@@ -617,19 +585,43 @@ static int hb_export_tensor_resized(void *vctx, int slot, const void *desc, void
     return slot_flagged((HipBackendCtx *)vctx, slot, false);
 }
 
-static int hb_export_mbinfo(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
+// A kept field's engine calls, by H264_KEEP_*: the retention switch and the export of slot
+#define HB_EXPORT_AS(engine_export)                                                   \
+    [](void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream) {       \
+        return hb_export(vctx, slot, engine_export, desc, d_dst, hip_stream);         \
+    }
+static const struct {
+    int (*engine_keep)(h264mi_engine *, int);
+    int (*export_field)(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream);
+} hb_fields[H264_KEEP_KINDS] = {
+    {h264mi_engine_keep_records, HB_EXPORT_AS(h264mi_engine_export_mbinfo)},
+    {h264mi_engine_keep_coefs, HB_EXPORT_AS(h264mi_engine_export_residual)},
+    {h264mi_engine_keep_accmv, HB_EXPORT_AS(h264mi_engine_export_accmv)},
+};
+#undef HB_EXPORT_AS
+static_assert(H264_KEEP_RECORDS == 0 && H264_KEEP_COEFS == 1 && H264_KEEP_ACCMV == 2, "the order of hb_fields' rows");
+
+// The decoder's switch `on` (c->keep[kind]) onto the instance's engine.  A
+// shared engine's retention is only ever switched on: its other instances may
+// be using it.
+static int hb_keep_apply(HipBackendCtx *c, int kind, bool on)
 {
-    return hb_export(vctx, slot, h264mi_engine_export_mbinfo, desc, d_dst, hip_stream);
+    if (!c->sh) return hb_fields[kind].engine_keep(c->e, on);
+    if (!on) return 0;
+    std::lock_guard<std::mutex> l(c->sh->mu);
+    return hb_fields[kind].engine_keep(c->e, 1);
 }
 
-static int hb_export_residual(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
+static int hb_keep(void *vctx, int kind, int on)
 {
-    return hb_export(vctx, slot, h264mi_engine_export_residual, desc, d_dst, hip_stream);
+    HipBackendCtx *c = (HipBackendCtx *)vctx;
+    c->keep[kind] = on != 0;
+    return c->e ? hb_keep_apply(c, kind, c->keep[kind]) : 0;
 }
 
-static int hb_export_accmv(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
+static int hb_export_field(void *vctx, int kind, int slot, const void *desc, void *d_dst, void *hip_stream)
 {
-    return hb_export(vctx, slot, h264mi_engine_export_accmv, desc, d_dst, hip_stream);
+    return hb_fields[kind].export_field(vctx, slot, desc, d_dst, hip_stream);
 }
 
 // Pinned host blocks (decoder output frames) kept after free for the next
@@ -702,16 +694,18 @@ static int hb_copy(void *vctx, int dst, int src)
 {
     HipBackendCtx *c = (HipBackendCtx *)vctx;
     if (dst >= 0 && dst < c->nslots) c->pref[dst] = NULL;
+    bool kept = false;
+    for (int k = 0; k < H264_KEEP_KINDS; k++) kept |= c->keep[k];
     if (c->sh) {
         std::lock_guard<std::mutex> l(c->sh->mu);
         HIPCHECK(hipMemcpyAsync(h264mi_engine_frame_ptr(c->e, c->lane, dst), h264mi_engine_frame_ptr(c->e, c->lane, src),
                                 engine_slot_bytes(c->e), hipMemcpyDeviceToDevice, engine_stream(c->e)));
         // the copy is no reconstruction: dst's kept records say nothing about it
-        if ((c->keep || c->keepc || c->keepa) && h264mi_engine_forget_records && h264mi_engine_forget_records(c->e, c->lane, dst)) return -1;
+        if (kept && h264mi_engine_forget_records && h264mi_engine_forget_records(c->e, c->lane, dst)) return -1;
         HIPCHECK(hipEventRecord(c->ev_last, engine_stream(c->e)));
         return 0;
     }
-    if ((c->keep || c->keepc || c->keepa) && h264mi_engine_forget_records && h264mi_engine_forget_records(c->e, 0, dst)) return -1;
+    if (kept && h264mi_engine_forget_records && h264mi_engine_forget_records(c->e, 0, dst)) return -1;
     if (h264mi_engine_sync(c->e)) return -1;
     HIPCHECK(hipMemcpy(h264mi_engine_frame_ptr(c->e, 0, dst), h264mi_engine_frame_ptr(c->e, 0, src),
                        engine_slot_bytes(c->e), hipMemcpyDeviceToDevice));
@@ -768,14 +762,15 @@ extern "C" H264Backend h264mi_hip_backend_create(int device)
     be.export_tensor = h264mi_engine_export_tensor ? hb_export_tensor : NULL;
     be.export_tensor_resized = h264mi_engine_export_tensor_resized ? hb_export_tensor_resized : NULL;
     const bool mbinfo = h264mi_engine_keep_records && h264mi_engine_export_mbinfo;
-    be.keep_records = mbinfo ? hb_keep_records : NULL;
-    be.export_mbinfo = mbinfo ? hb_export_mbinfo : NULL;
-    const bool resid = mbinfo && h264mi_engine_keep_coefs && h264mi_engine_export_residual;
-    be.keep_coefs = resid ? hb_keep_coefs : NULL;
-    be.export_residual = resid ? hb_export_residual : NULL;
-    const bool accmv = h264mi_engine_keep_accmv && h264mi_engine_export_accmv && h264mi_engine_forget_records;
-    be.keep_accmv = accmv ? hb_keep_accmv : NULL;
-    be.export_accmv = accmv ? hb_export_accmv : NULL;
+    const bool have[H264_KEEP_KINDS] = {
+        mbinfo,
+        mbinfo && h264mi_engine_keep_coefs && h264mi_engine_export_residual,
+        h264mi_engine_keep_accmv && h264mi_engine_export_accmv && h264mi_engine_forget_records,
+    };
+    for (int k = 0; k < H264_KEEP_KINDS; k++) {
+        be.field[k].keep = have[k] ? hb_keep : NULL;
+        be.field[k].export_field = have[k] ? hb_export_field : NULL;
+    }
     be.host_alloc = hb_host_alloc;
     be.host_free = hb_host_free;
     be.records_wait = hb_records_wait;

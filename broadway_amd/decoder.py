@@ -89,7 +89,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import time
-from typing import Callable, List, Optional
+from typing import Callable, List, NamedTuple, Optional
 
 import numpy as np
 
@@ -100,6 +100,31 @@ STREAM_BUFFER_SIZE = 1024 * 1024
 
 def _now() -> float:
     return time.perf_counter() * 1000.0
+
+
+class _Field(NamedTuple):
+    """A field export of the delivered picture (the option of its name)."""
+    build: str              # its descriptor builder in .engine
+    first: str              # the builder's first argument as an option key (the others: dtype, scale, bias)
+    default: object         # and its default
+    keep: str               # the H264SwDecKeep* call
+    last: str               # the H264SwDecLastPicture* call
+    shape: Callable         # (rows, columns) of (descriptor, x, y, cw, ch): what `last` covers of the crop window
+    kept: str               # what the backend keeps for it (the error text of `keep`)
+    what: str               # what it exports (the error text of `last`)
+
+
+# in the order __init__ takes the options; _emit exports in the reverse order
+_FIELDS = {
+    "mbinfo": _Field("mbinfo_desc", "channels", ("mvx", "mvy"), "H264SwDecKeepMbInfo", "H264SwDecLastPictureMbInfo",
+                     lambda d, x, y, cw, ch: (((y + ch + 3) >> 2) - (y >> 2), ((x + cw + 3) >> 2) - (x >> 2)),
+                     "MB records", "the MB records"),
+    "residual": _Field("residual_desc", "planes", "y", "H264SwDecKeepResidual", "H264SwDecLastPictureResidual",
+                       lambda d, x, y, cw, ch: tuple(v >> (d.planes == _lib.RESID_PLANES["uv"]) for v in (ch, cw)),
+                       "coefficients", "the residual"),
+    "accmv": _Field("accmv_desc", "channels", ("adx", "ady"), "H264SwDecKeepAccMotion", "H264SwDecLastPictureAccMotion",
+                    lambda d, x, y, cw, ch: (ch, cw), "origin maps", "the origin map"),
+}
 
 
 class Decoder:
@@ -122,54 +147,29 @@ class Decoder:
             self._tensor = tensor_desc(None, stream_ok=True, **opts)
             self._resized = opts.get("size") is not None
             self._device = int(os.environ.get("H264MI_DEVICE") or 0)     # the GPU H264SwDecInit takes (api.c)
-        self._mbinfo = self.options.get("mbinfo") or None
-        self.mbinfo = None
-        if self._mbinfo is not None:
-            opts = {} if self._mbinfo is True else dict(self._mbinfo)
-            unknown = set(opts) - {"channels", "dtype", "scale", "bias"}
-            if unknown:
-                raise ValueError(f"mbinfo: unknown keys {sorted(unknown)}")
-            from .engine import mbinfo_desc          # (imports torch)
-            self._mbinfo = mbinfo_desc(opts.pop("channels", ("mvx", "mvy")), None, **opts)
-            self._device = int(os.environ.get("H264MI_DEVICE") or 0)
-        self._residual = self.options.get("residual") or None
-        self.residual = None
-        if self._residual is not None:
-            opts = {} if self._residual is True else dict(self._residual)
-            unknown = set(opts) - {"planes", "dtype", "scale", "bias"}
-            if unknown:
-                raise ValueError(f"residual: unknown keys {sorted(unknown)}")
-            from .engine import residual_desc        # (imports torch)
-            self._residual = residual_desc(opts.pop("planes", "y"), None, **opts)
-            self._device = int(os.environ.get("H264MI_DEVICE") or 0)
-        self._accmv = self.options.get("accmv") or None
-        self.accmv = None
-        if self._accmv is not None:
-            opts = {} if self._accmv is True else dict(self._accmv)
-            unknown = set(opts) - {"channels", "dtype", "scale", "bias"}
-            if unknown:
-                raise ValueError(f"accmv: unknown keys {sorted(unknown)}")
-            from .engine import accmv_desc           # (imports torch)
-            self._accmv = accmv_desc(opts.pop("channels", ("adx", "ady")), None, **opts)
-            self._device = int(os.environ.get("H264MI_DEVICE") or 0)
+        self._fields = {}           # option -> (descriptor, channels or planes, torch dtype) of the fields asked for
+        for name, f in _FIELDS.items():
+            setattr(self, name, None)
+            opts = self.options.get(name) or None
+            if opts is not None:
+                opts = {} if opts is True else dict(opts)
+                unknown = set(opts) - {f.first, "dtype", "scale", "bias"}
+                if unknown:
+                    raise ValueError(f"{name}: unknown keys {sorted(unknown)}")
+                from . import engine                 # (imports torch)
+                self._fields[name] = getattr(engine, f.build)(opts.pop(f.first, f.default), None, **opts)
+                self._device = int(os.environ.get("H264MI_DEVICE") or 0)
         self._L = _lib.mi()
         inst = C.c_void_p()
         ret = self._L.H264SwDecInit(C.byref(inst), 0)
         if ret != _lib.H264SWDEC_OK:
             raise RuntimeError(f"DECODER INITIALIZATION FAILED ({ret})")
         self._inst = inst
-        if self._mbinfo is not None and (not hasattr(self._L, "H264SwDecKeepMbInfo") or
-                                         self._L.H264SwDecKeepMbInfo(inst, 1) != _lib.H264SWDEC_OK):
-            self.close()
-            raise RuntimeError("mbinfo: the backend cannot keep MB records (there is no host fallback)")
-        if self._residual is not None and (not hasattr(self._L, "H264SwDecKeepResidual") or
-                                           self._L.H264SwDecKeepResidual(inst, 1) != _lib.H264SWDEC_OK):
-            self.close()
-            raise RuntimeError("residual: the backend cannot keep coefficients (there is no host fallback)")
-        if self._accmv is not None and (not hasattr(self._L, "H264SwDecKeepAccMotion") or
-                                        self._L.H264SwDecKeepAccMotion(inst, 1) != _lib.H264SWDEC_OK):
-            self.close()
-            raise RuntimeError("accmv: the backend cannot keep origin maps (there is no host fallback)")
+        for name in self._fields:
+            f = _FIELDS[name]
+            if not hasattr(self._L, f.keep) or getattr(self._L, f.keep)(inst, 1) != _lib.H264SWDEC_OK:
+                self.close()
+                raise RuntimeError(f"{name}: the backend cannot keep {f.kept} (there is no host fallback)")
         self._buf = (C.c_uint8 * STREAM_BUFFER_SIZE)()
         self._info = _lib.H264SwDecInfo()
         self._pic = _lib.H264SwDecPicture()
@@ -281,48 +281,21 @@ class Decoder:
         return (i.cropParams.cropLeftOffset, i.cropParams.cropTopOffset, i.cropParams.cropOutWidth,
                 i.cropParams.cropOutHeight)
 
-    def _export_mbinfo(self):
-        """The delivered picture's field over the blocks covering the crop
-        window (the window H264SwDecLastPictureMbInfo takes for bw == 0)."""
-        desc, nch, dtype = self._mbinfo
-        x, y, cw, ch = self._crop_window()
-        bw, bh = ((x + cw + 3) >> 2) - (x >> 2), ((y + ch + 3) >> 2) - (y >> 2)
-        out, st = self._device_empty((nch, bh, bw), dtype)
-        ret = self._L.H264SwDecLastPictureMbInfo(self._inst, C.byref(desc), out.data_ptr(), st)
+    def _export_field(self, name):
+        """The delivered picture's field of that option over the crop window
+        (the window its H264SwDecLastPicture* call takes for a descriptor
+        without one; mbinfo: the blocks covering it)."""
+        f = _FIELDS[name]
+        desc, n, dtype = self._fields[name]
+        out, st = self._device_empty((n,) + f.shape(desc, *self._crop_window()), dtype)
+        ret = getattr(self._L, f.last)(self._inst, C.byref(desc), out.data_ptr(), st)
         if ret != _lib.H264SWDEC_PIC_RDY:
-            raise RuntimeError(f"mbinfo: the backend cannot export the MB records ({ret}; there is no host fallback)")
-        return out
-
-    def _export_residual(self):
-        """The delivered picture's residual over the crop window (the window
-        H264SwDecLastPictureResidual takes for cw == ch == 0)."""
-        desc, npl, dtype = self._residual
-        _, _, cw, ch = self._crop_window()
-        hs = 1 if desc.planes == _lib.RESID_PLANES["uv"] else 0
-        out, st = self._device_empty((npl, ch >> hs, cw >> hs), dtype)
-        ret = self._L.H264SwDecLastPictureResidual(self._inst, C.byref(desc), out.data_ptr(), st)
-        if ret != _lib.H264SWDEC_PIC_RDY:
-            raise RuntimeError(f"residual: the backend cannot export the residual ({ret}; there is no host fallback)")
-        return out
-
-    def _export_accmv(self):
-        """The delivered picture's accumulated motion over the crop window (the
-        window H264SwDecLastPictureAccMotion takes for cw == ch == 0)."""
-        desc, nch, dtype = self._accmv
-        _, _, cw, ch = self._crop_window()
-        out, st = self._device_empty((nch, ch, cw), dtype)
-        ret = self._L.H264SwDecLastPictureAccMotion(self._inst, C.byref(desc), out.data_ptr(), st)
-        if ret != _lib.H264SWDEC_PIC_RDY:
-            raise RuntimeError(f"accmv: the backend cannot export the origin map ({ret}; there is no host fallback)")
+            raise RuntimeError(f"{name}: the backend cannot export {f.what} ({ret}; there is no host fallback)")
         return out
 
     def _emit(self, pic, rgba=None) -> None:
-        if self._accmv is not None:
-            self.accmv = self._export_accmv()
-        if self._residual is not None:
-            self.residual = self._export_residual()
-        if self._mbinfo is not None:
-            self.mbinfo = self._export_mbinfo()
+        for name in reversed(self._fields):
+            setattr(self, name, self._export_field(name))
         w, h = self._out_size()
         if rgba is not None:
             buf = rgba

@@ -115,6 +115,60 @@ def tensor_desc(window, mode="rgb", dtype=None, scale=None, bias=None, mean=None
     return d, planes, dtype
 
 
+def _field_channels(channels, table, max_ch):
+    """The ids of ``channels`` (a name or names of ``table``, 1..max_ch of them)."""
+    if isinstance(channels, str):
+        channels = (channels,)
+    channels = tuple(channels)
+    if not 1 <= len(channels) <= max_ch:
+        raise ValueError(f"channels: 1..{max_ch} names")
+    bad = [c for c in channels if c not in table]
+    if bad:
+        raise ValueError(f"channels {bad}: each one of {sorted(table)}")
+    return [table[c] for c in channels]
+
+
+def _field_desc(d, n, per, window, dtype, scale, bias, blocks=False, uv=False):
+    """What the four field descriptors (mbinfo, residual, accmv, accres) share,
+    filled into ``d``: the window -- d's first four ints, in 4x4 blocks
+    (``blocks``) or luma samples, all even for ``uv`` --, the element type, and
+    scale and bias expanded to ``n`` values, one per ``per`` ("channel" or
+    "plane").  Returns (d, n, torch dtype)."""
+    import torch
+    dtype = torch.int16 if dtype is None else dtype
+    dts = {torch.int16: _lib.TENSOR_I16, torch.float16: _lib.TENSOR_F16, torch.bfloat16: _lib.TENSOR_BF16,
+           torch.float32: _lib.TENSOR_F32}
+    if dtype not in dts:
+        raise ValueError(f"dtype {dtype}: one of torch.int16, float16, bfloat16, float32")
+
+    def expand(v, default, what):
+        if v is None:
+            return (default,) * n
+        v = tuple(float(f) for f in v) if hasattr(v, "__len__") else (float(v),) * n
+        if len(v) != n:
+            raise ValueError(f"{what}: a scalar or one value per {per}")
+        return v
+
+    if window is not None:
+        x, y, w, h = ("bx", "by", "bw", "bh") if blocks else ("x", "y", "cw", "ch")
+        try:
+            vx, vy, vw, vh = (int(v) for v in window)
+        except (TypeError, ValueError):
+            raise ValueError(f"window {window!r}: ({x}, {y}, {w}, {h})") from None
+        for name, v in ((x, vx), (y, vy), (w, vw), (h, vh)):
+            setattr(d, name, v)
+        vx, vy, vw, vh = (getattr(d, name) for name in (x, y, w, h))       # (as the C ints hold them)
+        if vx < 0 or vy < 0 or vw < 1 or vh < 1:
+            raise ValueError(f"window {tuple(window)}: {x}, {y} >= 0 and {w}, {h} >= 1 "
+                             f"({'4x4 blocks' if blocks else 'luma samples'})")
+        if uv and (vx | vy | vw | vh) & 1:
+            raise ValueError(f"window {tuple(window)}: x, y, cw and ch are even for planes 'uv'")
+    d.dtype = dts[dtype]
+    d.scale[:n] = expand(scale, 1.0, "scale")
+    d.bias[:n] = expand(bias, 0.0, "bias")
+    return d, n, dtype
+
+
 def mbinfo_desc(channels, window=None, dtype=None, scale=None, bias=None):
     """(``_lib.MbInfoDesc``, number of channels, torch dtype) of an export of
     motion vectors and MB side information (Engine.to_mbinfo, Decoder's
@@ -126,42 +180,10 @@ def mbinfo_desc(channels, window=None, dtype=None, scale=None, bias=None):
     torch.int16 (the default; the integer itself) or float16 / bfloat16 /
     float32, ``fma(v, scale[c], bias[c])`` of channel position c; scale and
     bias are scalars or one value per channel, default 1 and 0."""
-    import torch
-    if isinstance(channels, str):
-        channels = (channels,)
-    channels = tuple(channels)
-    if not 1 <= len(channels) <= _lib.MBINFO_MAX_CH:
-        raise ValueError(f"channels: 1..{_lib.MBINFO_MAX_CH} names")
-    bad = [c for c in channels if c not in _lib.MBINFO_CHANNELS]
-    if bad:
-        raise ValueError(f"channels {bad}: each one of {sorted(_lib.MBINFO_CHANNELS)}")
-    dtype = torch.int16 if dtype is None else dtype
-    dts = {torch.int16: _lib.TENSOR_I16, torch.float16: _lib.TENSOR_F16, torch.bfloat16: _lib.TENSOR_BF16,
-           torch.float32: _lib.TENSOR_F32}
-    if dtype not in dts:
-        raise ValueError(f"dtype {dtype}: one of torch.int16, float16, bfloat16, float32")
-
-    def per_channel(v, default, what):
-        if v is None:
-            return (default,) * len(channels)
-        v = tuple(float(f) for f in v) if hasattr(v, "__len__") else (float(v),) * len(channels)
-        if len(v) != len(channels):
-            raise ValueError(f"{what}: a scalar or one value per channel")
-        return v
-
+    ids = _field_channels(channels, _lib.MBINFO_CHANNELS, _lib.MBINFO_MAX_CH)
     d = _lib.MbInfoDesc()
-    if window is not None:
-        try:
-            d.bx, d.by, d.bw, d.bh = (int(v) for v in window)
-        except (TypeError, ValueError):
-            raise ValueError(f"window {window!r}: (bx, by, bw, bh)") from None
-        if d.bx < 0 or d.by < 0 or d.bw < 1 or d.bh < 1:
-            raise ValueError(f"window {tuple(window)}: bx, by >= 0 and bw, bh >= 1 (4x4 blocks)")
-    d.nch, d.dtype = len(channels), dts[dtype]
-    d.ch[:len(channels)] = [_lib.MBINFO_CHANNELS[c] for c in channels]
-    d.scale[:len(channels)] = per_channel(scale, 1.0, "scale")
-    d.bias[:len(channels)] = per_channel(bias, 0.0, "bias")
-    return d, len(channels), dtype
+    d.nch, d.ch[:len(ids)] = len(ids), ids
+    return _field_desc(d, len(ids), "channel", window, dtype, scale, bias, blocks=True)
 
 
 def residual_desc(planes="y", window=None, dtype=None, scale=None, bias=None):
@@ -175,38 +197,11 @@ def residual_desc(planes="y", window=None, dtype=None, scale=None, bias=None):
     default; the integer itself) or float16 / bfloat16 / float32, ``fma(v,
     scale[c], bias[c])`` of plane position c; scale and bias are scalars or
     one value per plane, default 1 and 0."""
-    import torch
     if planes not in _lib.RESID_PLANES:
         raise ValueError(f"planes {planes!r}: one of {sorted(_lib.RESID_PLANES)}")
-    np_ = {"y": 1, "uv": 2, "yuv": 3}[planes]
-    dtype = torch.int16 if dtype is None else dtype
-    dts = {torch.int16: _lib.TENSOR_I16, torch.float16: _lib.TENSOR_F16, torch.bfloat16: _lib.TENSOR_BF16,
-           torch.float32: _lib.TENSOR_F32}
-    if dtype not in dts:
-        raise ValueError(f"dtype {dtype}: one of torch.int16, float16, bfloat16, float32")
-
-    def per_plane(v, default, what):
-        if v is None:
-            return (default,) * np_
-        v = tuple(float(f) for f in v) if hasattr(v, "__len__") else (float(v),) * np_
-        if len(v) != np_:
-            raise ValueError(f"{what}: a scalar or one value per plane")
-        return v
-
     d = _lib.ResidualDesc()
-    if window is not None:
-        try:
-            d.x, d.y, d.cw, d.ch = (int(v) for v in window)
-        except (TypeError, ValueError):
-            raise ValueError(f"window {window!r}: (x, y, cw, ch)") from None
-        if d.x < 0 or d.y < 0 or d.cw < 1 or d.ch < 1:
-            raise ValueError(f"window {tuple(window)}: x, y >= 0 and cw, ch >= 1 (luma samples)")
-        if planes == "uv" and (d.x | d.y | d.cw | d.ch) & 1:
-            raise ValueError(f"window {tuple(window)}: x, y, cw and ch are even for planes 'uv'")
-    d.planes, d.dtype = _lib.RESID_PLANES[planes], dts[dtype]
-    d.scale[:np_] = per_plane(scale, 1.0, "scale")
-    d.bias[:np_] = per_plane(bias, 0.0, "bias")
-    return d, np_, dtype
+    d.planes = _lib.RESID_PLANES[planes]
+    return _field_desc(d, {"y": 1, "uv": 2, "yuv": 3}[planes], "plane", window, dtype, scale, bias, uv=planes == "uv")
 
 
 def accmv_desc(channels=("adx", "ady"), window=None, dtype=None, scale=None, bias=None):
@@ -219,42 +214,10 @@ def accmv_desc(channels=("adx", "ady"), window=None, dtype=None, scale=None, bia
     ``dtype``: torch.int16 (the default; the integer itself) or float16 /
     bfloat16 / float32, ``fma(v, scale[c], bias[c])`` of channel position c;
     scale and bias are scalars or one value per channel, default 1 and 0."""
-    import torch
-    if isinstance(channels, str):
-        channels = (channels,)
-    channels = tuple(channels)
-    if not 1 <= len(channels) <= _lib.ACCMV_MAX_CH:
-        raise ValueError(f"channels: 1..{_lib.ACCMV_MAX_CH} names")
-    bad = [c for c in channels if c not in _lib.ACCMV_CHANNELS]
-    if bad:
-        raise ValueError(f"channels {bad}: each one of {sorted(_lib.ACCMV_CHANNELS)}")
-    dtype = torch.int16 if dtype is None else dtype
-    dts = {torch.int16: _lib.TENSOR_I16, torch.float16: _lib.TENSOR_F16, torch.bfloat16: _lib.TENSOR_BF16,
-           torch.float32: _lib.TENSOR_F32}
-    if dtype not in dts:
-        raise ValueError(f"dtype {dtype}: one of torch.int16, float16, bfloat16, float32")
-
-    def per_channel(v, default, what):
-        if v is None:
-            return (default,) * len(channels)
-        v = tuple(float(f) for f in v) if hasattr(v, "__len__") else (float(v),) * len(channels)
-        if len(v) != len(channels):
-            raise ValueError(f"{what}: a scalar or one value per channel")
-        return v
-
+    ids = _field_channels(channels, _lib.ACCMV_CHANNELS, _lib.ACCMV_MAX_CH)
     d = _lib.AccMvDesc()
-    if window is not None:
-        try:
-            d.x, d.y, d.cw, d.ch = (int(v) for v in window)
-        except (TypeError, ValueError):
-            raise ValueError(f"window {window!r}: (x, y, cw, ch)") from None
-        if d.x < 0 or d.y < 0 or d.cw < 1 or d.ch < 1:
-            raise ValueError(f"window {tuple(window)}: x, y >= 0 and cw, ch >= 1 (luma samples)")
-    d.nch, d.dtype = len(channels), dts[dtype]
-    d.id[:len(channels)] = [_lib.ACCMV_CHANNELS[c] for c in channels]
-    d.scale[:len(channels)] = per_channel(scale, 1.0, "scale")
-    d.bias[:len(channels)] = per_channel(bias, 0.0, "bias")
-    return d, len(channels), dtype
+    d.nch, d.id[:len(ids)] = len(ids), ids
+    return _field_desc(d, len(ids), "channel", window, dtype, scale, bias)
 
 
 def accres_desc(planes="y", window=None, dtype=None, scale=None, bias=None, colour=None, unanchored="key"):
@@ -269,7 +232,6 @@ def accres_desc(planes="y", window=None, dtype=None, scale=None, bias=None, colo
     ``unanchored``: "key" -- a sample whose chain back started at an intra MB is
     set against the key picture where that chain started -- or "zero": such a
     sample is 0.  window, dtype, scale and bias as for ``residual_desc``."""
-    import torch
     if not isinstance(planes, str) or planes not in _lib.ACCRES_PLANES:
         raise ValueError(f"planes {planes!r}: one of {sorted(_lib.ACCRES_PLANES)}")
     if not isinstance(unanchored, str) or unanchored not in _lib.ACCRES_UNANCHORED:
@@ -279,36 +241,11 @@ def accres_desc(planes="y", window=None, dtype=None, scale=None, bias=None, colo
     colour = "reference" if colour is None else colour
     if not isinstance(colour, str) or colour not in _lib.TENSOR_COLOURS or colour == "stream":
         raise ValueError(f"colour {colour!r}: one of {sorted(set(_lib.TENSOR_COLOURS) - {'stream'})}")
-    np_ = {"y": 1, "uv": 2, "yuv": 3, "rgb": 3}[planes]
-    dtype = torch.int16 if dtype is None else dtype
-    dts = {torch.int16: _lib.TENSOR_I16, torch.float16: _lib.TENSOR_F16, torch.bfloat16: _lib.TENSOR_BF16,
-           torch.float32: _lib.TENSOR_F32}
-    if dtype not in dts:
-        raise ValueError(f"dtype {dtype}: one of torch.int16, float16, bfloat16, float32")
-
-    def per_plane(v, default, what):
-        if v is None:
-            return (default,) * np_
-        v = tuple(float(f) for f in v) if hasattr(v, "__len__") else (float(v),) * np_
-        if len(v) != np_:
-            raise ValueError(f"{what}: a scalar or one value per plane")
-        return v
-
     d = _lib.AccResDesc()
-    if window is not None:
-        try:
-            d.x, d.y, d.cw, d.ch = (int(v) for v in window)
-        except (TypeError, ValueError):
-            raise ValueError(f"window {window!r}: (x, y, cw, ch)") from None
-        if d.x < 0 or d.y < 0 or d.cw < 1 or d.ch < 1:
-            raise ValueError(f"window {tuple(window)}: x, y >= 0 and cw, ch >= 1 (luma samples)")
-        if planes == "uv" and (d.x | d.y | d.cw | d.ch) & 1:
-            raise ValueError(f"window {tuple(window)}: x, y, cw and ch are even for planes 'uv'")
-    d.planes, d.dtype = _lib.ACCRES_PLANES[planes], dts[dtype]
+    d.planes = _lib.ACCRES_PLANES[planes]
     d.colour, d.unanchored = _lib.TENSOR_COLOURS[colour], _lib.ACCRES_UNANCHORED[unanchored]
-    d.scale[:np_] = per_plane(scale, 1.0, "scale")
-    d.bias[:np_] = per_plane(bias, 0.0, "bias")
-    return d, np_, dtype
+    return _field_desc(d, {"y": 1, "uv": 2, "yuv": 3, "rgb": 3}[planes], "plane", window, dtype, scale, bias,
+                       uv=planes == "uv")
 
 
 @dataclass
@@ -505,6 +442,25 @@ class Engine:
             out.record_stream(st)       # (the caching allocator: the block is in use on `stream` too)
         return out, st.cuda_stream
 
+    def _export_field(self, entry, needs, streams, slots, window, build, out, stream, blocks=False, uv=False):
+        """A field export (to_mbinfo, to_residual, to_accmv, to_accres) through
+        the library's ``entry``, which needs the retention ``needs``:
+        ``build(window)`` is the field's ``*_desc`` call; window None: the whole
+        MB-aligned picture in 4x4 blocks (``blocks``) or luma samples; ``uv``:
+        the planes are at half resolution."""
+        n, c_streams, c_slots = self._pictures(streams, slots)
+        unit = 4 if blocks else 16
+        if window is None:
+            window = (0, 0, self.w_mbs * unit, self.h_mbs * unit)
+        desc, planes, dtype = build(window)
+        rows, cols = (desc.bh, desc.bw) if blocks else (desc.ch >> uv, desc.cw >> uv)
+        out, st = self._out((n, planes, rows, cols), dtype, out, stream)
+        if not hasattr(self._L, entry) or \
+                getattr(self._L, entry)(self._h, n, c_streams, c_slots, C.byref(desc), out.data_ptr(),
+                                        planes * rows * cols * out.element_size(), st) != 0:
+            raise RuntimeError(f"{entry} failed ({needs} off, or stream, slot or window out of range?)")
+        return out
+
     def to_tensor(self, streams: Sequence[int], slots: Sequence[int], window=None, mode: str = "rgb", dtype=None,
                   scale=None, bias=None, mean=None, std=None, out=None, stream=None, size=None, colour=None):
         """The slots (streams[k], slots[k]) as one ``(n, planes, ch, cw)``
@@ -572,17 +528,8 @@ class Engine:
         (``mbinfo_desc``; a slot nothing was decoded into reads as "no
         information").  Needs ``keep_records()`` before the decodes.  ``out``
         and ``stream`` as for ``to_tensor``; the host is never synchronised."""
-        n, c_streams, c_slots = self._pictures(streams, slots)
-        if window is None:
-            window = (0, 0, self.w_mbs * 4, self.h_mbs * 4)
-        desc, nch, dtype = mbinfo_desc(channels, window, dtype, scale, bias)
-        shape = (n, nch, desc.bh, desc.bw)
-        out, st = self._out(shape, dtype, out, stream)
-        if self._L.h264mi_engine_export_mbinfo(self._h, n, c_streams, c_slots, C.byref(desc), out.data_ptr(),
-                                               nch * desc.bh * desc.bw * out.element_size(), st) != 0:
-            raise RuntimeError("h264mi_engine_export_mbinfo failed (keep_records off, or stream, slot or window "
-                               "out of range?)")
-        return out
+        return self._export_field("h264mi_engine_export_mbinfo", "keep_records", streams, slots, window,
+                                  lambda w: mbinfo_desc(channels, w, dtype, scale, bias), out, stream, blocks=True)
 
     def keep_coefs(self, on: bool = True) -> None:
         """Keep each picture's coefficient blocks, and its records, on the
@@ -604,18 +551,9 @@ class Engine:
         a slot nothing was decoded into reads as zeros).  Needs
         ``keep_coefs()`` before the decodes.  ``out`` and ``stream`` as for
         ``to_tensor``; the host is never synchronised."""
-        n, c_streams, c_slots = self._pictures(streams, slots)
-        if window is None:
-            window = (0, 0, self.w_mbs * 16, self.h_mbs * 16)
-        desc, npl, dtype = residual_desc(planes, window, dtype, scale, bias)
-        hs = 1 if planes == "uv" else 0
-        shape = (n, npl, desc.ch >> hs, desc.cw >> hs)
-        out, st = self._out(shape, dtype, out, stream)
-        if self._L.h264mi_engine_export_residual(self._h, n, c_streams, c_slots, C.byref(desc), out.data_ptr(),
-                                                 npl * shape[2] * shape[3] * out.element_size(), st) != 0:
-            raise RuntimeError("h264mi_engine_export_residual failed (keep_coefs off, or stream, slot or window "
-                               "out of range?)")
-        return out
+        return self._export_field("h264mi_engine_export_residual", "keep_coefs", streams, slots, window,
+                                  lambda w: residual_desc(planes, w, dtype, scale, bias), out, stream,
+                                  uv=planes == "uv")
 
     def keep_accmv(self, on: bool = True) -> None:
         """Keep each picture's origin map -- every luma sample traced back to
@@ -638,18 +576,8 @@ class Engine:
         (x, y, 0): no displacement, not anchored).  Needs ``keep_accmv()``
         before the decodes.  ``out`` and ``stream`` as for ``to_tensor``; the
         host is never synchronised."""
-        n, c_streams, c_slots = self._pictures(streams, slots)
-        if window is None:
-            window = (0, 0, self.w_mbs * 16, self.h_mbs * 16)
-        desc, nch, dtype = accmv_desc(channels, window, dtype, scale, bias)
-        shape = (n, nch, desc.ch, desc.cw)
-        out, st = self._out(shape, dtype, out, stream)
-        if not hasattr(self._L, "h264mi_engine_export_accmv") or \
-                self._L.h264mi_engine_export_accmv(self._h, n, c_streams, c_slots, C.byref(desc), out.data_ptr(),
-                                                   nch * desc.ch * desc.cw * out.element_size(), st) != 0:
-            raise RuntimeError("h264mi_engine_export_accmv failed (keep_accmv off, or stream, slot or window "
-                               "out of range?)")
-        return out
+        return self._export_field("h264mi_engine_export_accmv", "keep_accmv", streams, slots, window,
+                                  lambda w: accmv_desc(channels, w, dtype, scale, bias), out, stream)
 
     def keep_accres(self, nkeys: int = 2) -> None:
         """Keep the samples of each stream's last ``nkeys`` (1..8) key pictures
@@ -695,19 +623,9 @@ class Engine:
         reads as zeros).  Needs ``keep_accmv()`` and ``keep_accres()`` before
         the decodes.  ``out`` and ``stream`` as for ``to_tensor``; the host is
         never synchronised."""
-        n, c_streams, c_slots = self._pictures(streams, slots)
-        if window is None:
-            window = (0, 0, self.w_mbs * 16, self.h_mbs * 16)
-        desc, npl, dtype = accres_desc(planes, window, dtype, scale, bias, colour, unanchored)
-        hs = 1 if planes == "uv" else 0
-        shape = (n, npl, desc.ch >> hs, desc.cw >> hs)
-        out, st = self._out(shape, dtype, out, stream)
-        if not hasattr(self._L, "h264mi_engine_export_accres") or \
-                self._L.h264mi_engine_export_accres(self._h, n, c_streams, c_slots, C.byref(desc), out.data_ptr(),
-                                                    npl * shape[2] * shape[3] * out.element_size(), st) != 0:
-            raise RuntimeError("h264mi_engine_export_accres failed (keep_accres off, or stream, slot or window "
-                               "out of range?)")
-        return out
+        return self._export_field("h264mi_engine_export_accres", "keep_accres", streams, slots, window,
+                                  lambda w: accres_desc(planes, w, dtype, scale, bias, colour, unanchored), out, stream,
+                                  uv=planes == "uv")
 
     @property
     def device(self) -> int:
