@@ -113,6 +113,16 @@ class AccResDesc(C.Structure):
                [("scale", C.c_float * 3), ("bias", C.c_float * 3)]
 
 
+class AccMvResizeDesc(C.Structure):
+    """h264mi_accmv_resize_desc (include/h264mi.h)."""
+    _fields_ = [("f", AccMvDesc), ("ow", C.c_int), ("oh", C.c_int), ("filter", C.c_int)]
+
+
+class AccResResizeDesc(C.Structure):
+    """h264mi_accres_resize_desc (include/h264mi.h)."""
+    _fields_ = [("f", AccResDesc), ("ow", C.c_int), ("oh", C.c_int), ("filter", C.c_int)]
+
+
 # channel ids of AccMvDesc.id, by name
 ACCMV_CHANNELS = {"adx": 0, "ady": 1, "jx": 2, "jy": 3, "anchored": 4}
 ACCMV_MAX_CH = 8
@@ -325,6 +335,19 @@ def mi() -> C.CDLL:
         L.h264mi_engine_export_accres.restype = i32
         L.h264mi_engine_conceal.argtypes = [vp, i32, i32, C.POINTER(i32), i32, C.POINTER(C.c_uint8)]
         L.h264mi_engine_conceal.restype = i32
+    if hasattr(L, "h264mi_accmv_resize_device"):            # (optional, as above)
+        ad, rd = C.POINTER(AccMvResizeDesc), C.POINTER(AccResResizeDesc)
+        szp = C.POINTER(sz)
+        L.h264mi_accmv_resize_device.argtypes = [vp, szp, i32, i32, i32, ad, vp, sz, vp]
+        L.h264mi_accmv_resize_device.restype = i32
+        L.h264mi_accres_resize_device.argtypes = [vp, szp, vp, szp, vp, szp, i32, i32, i32, rd, vp, sz, vp]
+        L.h264mi_accres_resize_device.restype = i32
+        L.h264mi_engine_export_accmv_resized.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), ad, vp, sz, vp]
+        L.h264mi_engine_export_accmv_resized.restype = i32
+        L.h264mi_engine_export_accres_resized.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), rd, vp, sz, vp]
+        L.h264mi_engine_export_accres_resized.restype = i32
+        L.H264SwDecLastPictureAccMotionResized.argtypes = [vp, ad, vp, vp]
+        L.H264SwDecLastPictureAccMotionResized.restype = i32
     L.h264mi_engine_sync.argtypes = [vp]
     L.h264mi_engine_sync.restype = i32
     L.h264mi_engine_kernel.argtypes = [vp]

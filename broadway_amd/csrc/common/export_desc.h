@@ -139,6 +139,41 @@ static inline int accres_window_ok(const h264mi_accres_desc *d, int w_mbs, int h
            export_luma_window_ok(d->x, d->y, d->cw, d->ch, w_mbs, h_mbs, d->planes == H264MI_ACCRES_UV);
 }
 
+/* h264mi_accmv_resize_desc and h264mi_accres_resize_desc: the inner
+ * descriptor's rules, resize_desc_*_ok's on the output size, and its bounds on
+ * the source grid gw x gh -- the window, or its half-resolution grid for UV */
+static inline int field_resize_size_ok(int ow, int oh, int filter)
+{
+    return filter == H264MI_RESIZE_TRIANGLE && ow >= 1 && oh >= 1 && ow <= H264MI_RESIZE_MAX_DIM &&
+           oh <= H264MI_RESIZE_MAX_DIM;
+}
+
+static inline int field_resize_grid_ok(int gw, int gh, int ow, int oh)
+{
+    return gw <= H264MI_RESIZE_MAX_DIM && gh <= H264MI_RESIZE_MAX_DIM && gw <= 32 * ow && gh <= 32 * oh;
+}
+
+static inline int accmv_resize_fixed_ok(const h264mi_accmv_resize_desc *d)
+{
+    return accmv_desc_fixed_ok(&d->f) && field_resize_size_ok(d->ow, d->oh, d->filter);
+}
+
+static inline int accmv_resize_window_ok(const h264mi_accmv_resize_desc *d, int w_mbs, int h_mbs)
+{
+    return accmv_window_ok(&d->f, w_mbs, h_mbs) && field_resize_grid_ok(d->f.cw, d->f.ch, d->ow, d->oh);
+}
+
+static inline int accres_resize_fixed_ok(const h264mi_accres_resize_desc *d)
+{
+    return accres_desc_fixed_ok(&d->f) && field_resize_size_ok(d->ow, d->oh, d->filter);
+}
+
+static inline int accres_resize_window_ok(const h264mi_accres_resize_desc *d, int w_mbs, int h_mbs)
+{
+    const int hs = d->f.planes == H264MI_ACCRES_UV;
+    return accres_window_ok(&d->f, w_mbs, h_mbs) && field_resize_grid_ok(d->f.cw >> hs, d->f.ch >> hs, d->ow, d->oh);
+}
+
 /* An SPS's crop window in luma samples (the whole picture without cropping;
  * the offsets are in the SPS's units of 2 samples) */
 typedef struct { int x, y, cw, ch; } export_window;

@@ -12,6 +12,7 @@
 #include "residual.hip"
 #include "accmv.hip"
 #include "accres.hip"
+#include "field_resize.hip"
 #include "conceal.hip"
 #include <hip/hip_ext.h>
 
@@ -1551,23 +1552,28 @@ extern "C" int h264mi_accmv_step_device(const void *d_recs, int w_mbs, int h_mbs
     return 0;
 }
 
-// Origin maps as planar channels (accmv.hip k_accmv): the window desc->(x, y,
-// cw, ch) of the npics maps (16 * w_mbs words a row) that start map_offsets[k]
-// bytes after d_maps, as contiguous (nch, ch, cw) elements of desc->dtype at
-// d_out + k * out_stride; device pointers, asynchronous on `stream`;
-// ACCMV_MAX_PICS pictures per launch.  -1 (nothing launched) on a bad argument.
-extern "C" int h264mi_accmv_device(const void *d_maps, const size_t *map_offsets, int npics, int w_mbs, int h_mbs,
-                                   const h264mi_accmv_desc *desc, void *d_out, size_t out_stride, void *stream)
+// a resized export's descriptor h264mi_accmv_resize_device accepts on a w_mbs x h_mbs picture
+static bool accmv_resize_desc_ok(const h264mi_accmv_resize_desc *d, int w_mbs, int h_mbs)
+{
+    return d && accmv_resize_fixed_ok(d) && accmv_resize_window_ok(d, w_mbs, h_mbs);
+}
+
+// Both accumulated-motion exports (r != NULL: resized, desc = &r->f): one check
+// and one fill of what their kernels share, accmv_args
+static int accmv_device(const void *d_maps, const size_t *map_offsets, int npics, int w_mbs, int h_mbs,
+                        const h264mi_accmv_desc *desc, const h264mi_accmv_resize_desc *r, void *d_out,
+                        size_t out_stride, void *stream)
 {
     if (!d_maps || !map_offsets || !d_out || npics < 1 || ((size_t)(uintptr_t)d_maps & 3) ||
-        !accmv_desc_ok(desc, w_mbs, h_mbs))
+        (r ? !accmv_resize_desc_ok(r, w_mbs, h_mbs) : !accmv_desc_ok(desc, w_mbs, h_mbs)))
         return -1;
     for (int k = 0; k < npics; k++)
         if (map_offsets[k] & 3) return -1;
     const size_t es = export_elem_size(desc->dtype);
     if (!export_aligned(d_out, out_stride, es)) return -1;
     const bool v16 = export_v16(d_out, out_stride, (size_t)desc->cw * es);
-    accmv_args a;
+    fresize_args<fresize_accmv> ra;
+    accmv_args &a = ra.f;
     a.maps = (const uint8_t *)d_maps;
     a.W = 16 * w_mbs;
     a.x = desc->x; a.y = desc->y; a.cw = desc->cw; a.ch = desc->ch; a.nch = desc->nch;
@@ -1577,8 +1583,34 @@ extern "C" int h264mi_accmv_device(const void *d_maps, const size_t *map_offsets
         a.scale[c] = c < desc->nch ? desc->scale[c] : 0.0f;
         a.bias[c] = c < desc->nch ? desc->bias[c] : 0.0f;
     }
-    return export_launches(npics, map_offsets, a.off, &a.out, d_out, out_stride,
-                           [&](int, int n) { accmv_launch(desc->dtype, v16, n, (hipStream_t)stream, a); });
+    ra.ow = r ? r->ow : 0; ra.oh = r ? r->oh : 0;
+    return export_launches(npics, map_offsets, a.off, &a.out, d_out, out_stride, [&](int, int n) {
+        if (r) fresize_launch(desc->dtype, n, (hipStream_t)stream, ra);
+        else accmv_launch(desc->dtype, v16, n, (hipStream_t)stream, a);
+    });
+}
+
+// Origin maps as planar channels (accmv.hip k_accmv): the window desc->(x, y,
+// cw, ch) of the npics maps (16 * w_mbs words a row) that start map_offsets[k]
+// bytes after d_maps, as contiguous (nch, ch, cw) elements of desc->dtype at
+// d_out + k * out_stride; device pointers, asynchronous on `stream`;
+// ACCMV_MAX_PICS pictures per launch.  -1 (nothing launched) on a bad argument.
+extern "C" int h264mi_accmv_device(const void *d_maps, const size_t *map_offsets, int npics, int w_mbs, int h_mbs,
+                                   const h264mi_accmv_desc *desc, void *d_out, size_t out_stride, void *stream)
+{
+    return accmv_device(d_maps, map_offsets, npics, w_mbs, h_mbs, desc, NULL, d_out, out_stride, stream);
+}
+
+// The same fields resized (field_resize.hip): the window's integer field
+// filtered to desc->oh x desc->ow samples per channel, picture k's (nch, oh, ow)
+// elements at d_out + k * out_stride.  The window is at most 16384 a side and
+// 32 times the output on each axis.  Stateless: the tap tables are made in the
+// kernel.  -1 (nothing launched) on a bad argument.
+extern "C" int h264mi_accmv_resize_device(const void *d_maps, const size_t *map_offsets, int npics, int w_mbs, int h_mbs,
+                                          const h264mi_accmv_resize_desc *desc, void *d_out, size_t out_stride,
+                                          void *stream)
+{
+    return accmv_device(d_maps, map_offsets, npics, w_mbs, h_mbs, desc ? &desc->f : NULL, desc, d_out, out_stride, stream);
 }
 
 // the maps of slots [first, first + n) of the engine's pool as (x, y, 0), on its stream
@@ -1633,21 +1665,87 @@ extern "C" int h264mi_engine_keep_accmv(h264mi_engine *e, int on)
 
 // The kept maps of the slots (streams[k], slots[k]) as tensors in the caller's
 // memory, ordered between the caller's stream and ours by export_ordered
-extern "C" int h264mi_engine_export_accmv(h264mi_engine *e, int n, const int *streams, const int *slots,
-                                          const h264mi_accmv_desc *desc, void *d_out, size_t out_stride, void *stream)
+static int engine_export_accmv(h264mi_engine *e, int n, const int *streams, const int *slots,
+                               const h264mi_accmv_desc *desc, const h264mi_accmv_resize_desc *rdesc, void *d_out,
+                               size_t out_stride, void *stream)
 {
-    if (!e || !e->d_acc || n < 1 || !streams || !slots || !d_out || !accmv_desc_ok(desc, e->w, e->h)) return -1;
+    if (!e || !e->d_acc || n < 1 || !streams || !slots || !d_out ||
+        (rdesc ? !accmv_resize_desc_ok(rdesc, e->w, e->h) : !accmv_desc_ok(desc, e->w, e->h)))
+        return -1;
     return export_ordered(e, n, streams, slots, d_out, out_stride, export_elem_size(desc->dtype), stream, [&] {
         std::vector<size_t> off((size_t)n);
         for (int k = 0; k < n; k++) off[k] = acc_words(e) * 4 * ((size_t)streams[k] * e->nslots + slots[k]);
-        return h264mi_accmv_device(e->d_acc, off.data(), n, e->w, e->h, desc, d_out, out_stride, e->st);
+        return accmv_device(e->d_acc, off.data(), n, e->w, e->h, desc, rdesc, d_out, out_stride, e->st);
     });
+}
+
+extern "C" int h264mi_engine_export_accmv(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                          const h264mi_accmv_desc *desc, void *d_out, size_t out_stride, void *stream)
+{
+    return engine_export_accmv(e, n, streams, slots, desc, NULL, d_out, out_stride, stream);
+}
+
+// the same, resized (h264mi_accmv_resize_device)
+extern "C" int h264mi_engine_export_accmv_resized(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                                  const h264mi_accmv_resize_desc *desc, void *d_out, size_t out_stride,
+                                                  void *stream)
+{
+    return engine_export_accmv(e, n, streams, slots, desc ? &desc->f : NULL, desc, d_out, out_stride, stream);
 }
 
 // an export descriptor h264mi_accres_device accepts on a w_mbs x h_mbs picture
 static bool accres_desc_ok(const h264mi_accres_desc *d, int w_mbs, int h_mbs)
 {
     return d && accres_desc_fixed_ok(d) && accres_window_ok(d, w_mbs, h_mbs);
+}
+
+// a resized export's descriptor h264mi_accres_resize_device accepts on a w_mbs x h_mbs picture
+static bool accres_resize_desc_ok(const h264mi_accres_resize_desc *d, int w_mbs, int h_mbs)
+{
+    return d && accres_resize_fixed_ok(d) && accres_resize_window_ok(d, w_mbs, h_mbs);
+}
+
+// Both accumulated-residual exports (r != NULL: resized, desc = &r->f): one
+// check and one fill of what their kernels share, accres_args
+static int accres_device(const void *d_cur, const size_t *cur_offsets, const void *d_key, const size_t *key_offsets,
+                         const void *d_maps, const size_t *map_offsets, int npics, int w_mbs, int h_mbs,
+                         const h264mi_accres_desc *desc, const h264mi_accres_resize_desc *r, void *d_out,
+                         size_t out_stride, void *stream)
+{
+    static_assert(H264MI_ACCRES_Y == ACCRES_Y && H264MI_ACCRES_UV == ACCRES_UV && H264MI_ACCRES_YUV == ACCRES_YUV &&
+                      H264MI_ACCRES_RGB == ACCRES_RGB && ACCRES_MAX_PICS == EXPORT_MAX_PICS &&
+                      H264MI_TENSOR_COLOUR_BT709_FULL == TENSOR_COLOUR_SETS - 1,
+                  "include/h264mi.h and accres.hip name the same planes, bounds and colour sets");
+    if (!d_cur || !cur_offsets || !key_offsets || !d_maps || !map_offsets || !d_out || npics < 1 ||
+        (((size_t)(uintptr_t)d_cur | (size_t)(uintptr_t)d_key | (size_t)(uintptr_t)d_maps) & 3) ||
+        (r ? !accres_resize_desc_ok(r, w_mbs, h_mbs) : !accres_desc_ok(desc, w_mbs, h_mbs)))
+        return -1;
+    for (int k = 0; k < npics; k++) {
+        if ((map_offsets[k] | cur_offsets[k]) & 3) return -1;
+        if (key_offsets[k] != (size_t)-1 && (!d_key || (key_offsets[k] & 3))) return -1;
+    }
+    const size_t es = export_elem_size(desc->dtype);
+    if (!export_aligned(d_out, out_stride, es)) return -1;
+    const int ow = desc->planes == H264MI_ACCRES_UV ? desc->cw / 2 : desc->cw;
+    const bool v16 = export_v16(d_out, out_stride, (size_t)ow * es);
+    fresize_args<fresize_accres> ra;
+    accres_args &a = ra.f;
+    a.cur = (const uint8_t *)d_cur; a.key = (const uint8_t *)d_key; a.maps = (const uint8_t *)d_maps;
+    a.W = 16 * w_mbs; a.H = 16 * h_mbs; a.cpitch = H264MI_CPITCH(w_mbs);
+    a.x = desc->x; a.y = desc->y; a.cw = desc->cw; a.ch = desc->ch;
+    a.planes = desc->planes; a.zero = desc->unanchored == H264MI_ACCRES_ZERO;
+    a.out_stride = out_stride;
+    a.col = tensor_colour_sets[desc->colour];
+    for (int c = 0; c < 3; c++) { a.scale[c] = desc->scale[c]; a.bias[c] = desc->bias[c]; }
+    ra.ow = r ? r->ow : 0; ra.oh = r ? r->oh : 0;
+    return export_launches(npics, map_offsets, a.map_off, &a.out, d_out, out_stride, [&](int k0, int n) {
+        for (int k = 0; k < ACCRES_MAX_PICS; k++) {
+            a.cur_off[k] = k < n ? cur_offsets[k0 + k] : 0;
+            a.key_off[k] = k < n && key_offsets[k0 + k] != (size_t)-1 ? key_offsets[k0 + k] : ACCRES_NO_KEY;
+        }
+        if (r) fresize_launch(desc->dtype, n, (hipStream_t)stream, ra);
+        else accres_launch(desc->dtype, v16, n, (hipStream_t)stream, a);
+    });
 }
 
 // The accumulated residual (accres.hip k_accres): the window desc->(x, y, cw,
@@ -1660,37 +1758,21 @@ extern "C" int h264mi_accres_device(const void *d_cur, const size_t *cur_offsets
                                     int w_mbs, int h_mbs, const h264mi_accres_desc *desc, void *d_out, size_t out_stride,
                                     void *stream)
 {
-    static_assert(H264MI_ACCRES_Y == ACCRES_Y && H264MI_ACCRES_UV == ACCRES_UV && H264MI_ACCRES_YUV == ACCRES_YUV &&
-                      H264MI_ACCRES_RGB == ACCRES_RGB && ACCRES_MAX_PICS == EXPORT_MAX_PICS &&
-                      H264MI_TENSOR_COLOUR_BT709_FULL == TENSOR_COLOUR_SETS - 1,
-                  "include/h264mi.h and accres.hip name the same planes, bounds and colour sets");
-    if (!d_cur || !cur_offsets || !key_offsets || !d_maps || !map_offsets || !d_out || npics < 1 ||
-        (((size_t)(uintptr_t)d_cur | (size_t)(uintptr_t)d_key | (size_t)(uintptr_t)d_maps) & 3) ||
-        !accres_desc_ok(desc, w_mbs, h_mbs))
-        return -1;
-    for (int k = 0; k < npics; k++) {
-        if ((map_offsets[k] | cur_offsets[k]) & 3) return -1;
-        if (key_offsets[k] != (size_t)-1 && (!d_key || (key_offsets[k] & 3))) return -1;
-    }
-    const size_t es = export_elem_size(desc->dtype);
-    if (!export_aligned(d_out, out_stride, es)) return -1;
-    const int ow = desc->planes == H264MI_ACCRES_UV ? desc->cw / 2 : desc->cw;
-    const bool v16 = export_v16(d_out, out_stride, (size_t)ow * es);
-    accres_args a;
-    a.cur = (const uint8_t *)d_cur; a.key = (const uint8_t *)d_key; a.maps = (const uint8_t *)d_maps;
-    a.W = 16 * w_mbs; a.H = 16 * h_mbs; a.cpitch = H264MI_CPITCH(w_mbs);
-    a.x = desc->x; a.y = desc->y; a.cw = desc->cw; a.ch = desc->ch;
-    a.planes = desc->planes; a.zero = desc->unanchored == H264MI_ACCRES_ZERO;
-    a.out_stride = out_stride;
-    a.col = tensor_colour_sets[desc->colour];
-    for (int c = 0; c < 3; c++) { a.scale[c] = desc->scale[c]; a.bias[c] = desc->bias[c]; }
-    return export_launches(npics, map_offsets, a.map_off, &a.out, d_out, out_stride, [&](int k0, int n) {
-        for (int k = 0; k < ACCRES_MAX_PICS; k++) {
-            a.cur_off[k] = k < n ? cur_offsets[k0 + k] : 0;
-            a.key_off[k] = k < n && key_offsets[k0 + k] != (size_t)-1 ? key_offsets[k0 + k] : ACCRES_NO_KEY;
-        }
-        accres_launch(desc->dtype, v16, n, (hipStream_t)stream, a);
-    });
+    return accres_device(d_cur, cur_offsets, d_key, key_offsets, d_maps, map_offsets, npics, w_mbs, h_mbs, desc, NULL,
+                         d_out, out_stride, stream);
+}
+
+// The same fields resized (field_resize.hip): the window's integer field (UV:
+// its half-resolution grid) filtered to desc->oh x desc->ow samples per plane,
+// picture k's (planes, oh, ow) elements at d_out + k * out_stride; the bounds of
+// h264mi_accmv_resize_device on the grid.  -1 (nothing launched) on a bad argument.
+extern "C" int h264mi_accres_resize_device(const void *d_cur, const size_t *cur_offsets, const void *d_key,
+                                           const size_t *key_offsets, const void *d_maps, const size_t *map_offsets,
+                                           int npics, int w_mbs, int h_mbs, const h264mi_accres_resize_desc *desc,
+                                           void *d_out, size_t out_stride, void *stream)
+{
+    return accres_device(d_cur, cur_offsets, d_key, key_offsets, d_maps, map_offsets, npics, w_mbs, h_mbs,
+                         desc ? &desc->f : NULL, desc, d_out, out_stride, stream);
 }
 
 static void accres_free(h264mi_engine *e)
@@ -1746,10 +1828,13 @@ extern "C" int h264mi_engine_accres_held(h264mi_engine *e, int stream, int slot)
 // The accumulated residual of the slots (streams[k], slots[k]) against the keys
 // held for them, as tensors in the caller's memory, ordered between the
 // caller's stream and ours by export_ordered
-extern "C" int h264mi_engine_export_accres(h264mi_engine *e, int n, const int *streams, const int *slots,
-                                           const h264mi_accres_desc *desc, void *d_out, size_t out_stride, void *stream)
+static int engine_export_accres(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                const h264mi_accres_desc *desc, const h264mi_accres_resize_desc *rdesc, void *d_out,
+                                size_t out_stride, void *stream)
 {
-    if (!e || !e->d_akey || n < 1 || !streams || !slots || !d_out || !accres_desc_ok(desc, e->w, e->h)) return -1;
+    if (!e || !e->d_akey || n < 1 || !streams || !slots || !d_out ||
+        (rdesc ? !accres_resize_desc_ok(rdesc, e->w, e->h) : !accres_desc_ok(desc, e->w, e->h)))
+        return -1;
     return export_ordered(e, n, streams, slots, d_out, out_stride, export_elem_size(desc->dtype), stream, [&] {
         std::vector<size_t> cur((size_t)n), key((size_t)n), map((size_t)n);
         for (int k = 0; k < n; k++) {
@@ -1759,9 +1844,23 @@ extern "C" int h264mi_engine_export_accres(h264mi_engine *e, int n, const int *s
             key[k] = entry < 0 ? (size_t)-1 : e->frame_bytes * (size_t)entry;
             map[k] = acc_words(e) * 4 * b;
         }
-        return h264mi_accres_device(e->d_frames, cur.data(), e->d_akey, key.data(), e->d_acc, map.data(), n, e->w, e->h,
-                                    desc, d_out, out_stride, e->st);
+        return accres_device(e->d_frames, cur.data(), e->d_akey, key.data(), e->d_acc, map.data(), n, e->w, e->h, desc,
+                             rdesc, d_out, out_stride, e->st);
     });
+}
+
+extern "C" int h264mi_engine_export_accres(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                           const h264mi_accres_desc *desc, void *d_out, size_t out_stride, void *stream)
+{
+    return engine_export_accres(e, n, streams, slots, desc, NULL, d_out, out_stride, stream);
+}
+
+// the same, resized (h264mi_accres_resize_device), under the same held-key rule
+extern "C" int h264mi_engine_export_accres_resized(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                                   const h264mi_accres_resize_desc *desc, void *d_out,
+                                                   size_t out_stride, void *stream)
+{
+    return engine_export_accres(e, n, streams, slots, desc ? &desc->f : NULL, desc, d_out, out_stride, stream);
 }
 
 extern "C" void *h264mi_engine_frame_ptr(h264mi_engine *e, int stream, int slot)

@@ -420,6 +420,29 @@ H264SwDecRet H264SwDecLastPictureAccMotion(H264SwDecInst decInst, const h264mi_a
     return last_picture_field(decInst, H264_KEEP_ACCMV, desc, d_dst, hip_stream);
 }
 
+/* The accumulated motion resized: H264SwDecLastPictureAccMotion's steps with
+ * the resize descriptor's two rules and the backend's member for it (the
+ * resized export has no row in field_rules: it keeps nothing of its own) */
+H264SwDecRet H264SwDecLastPictureAccMotionResized(H264SwDecInst decInst, const h264mi_accmv_resize_desc *desc,
+                                                  void *d_dst, void *hip_stream)
+{
+    if (decInst == NULL || desc == NULL || d_dst == NULL) return H264SWDEC_PARAM_ERR;
+    DecContainer *c = (DecContainer *)decInst;
+    if (!c->dec.be.export_accmv_resized || !c->dec.keep[H264_KEEP_ACCMV]) return H264SWDEC_PARAM_ERR;
+    h264mi_accmv_resize_desc m = *desc;
+    if (!accmv_resize_fixed_ok(&m) || !export_aligned(d_dst, 0, export_elem_size(m.f.dtype))) return H264SWDEC_PARAM_ERR;
+    const Sps *s = h264dec_active_sps(&c->dec);
+    if (!s || !c->dec.last_out_slot1) return H264SWDEC_OK;      /* no picture delivered */
+    if (m.f.cw == 0 && m.f.ch == 0) {
+        const export_window w = sps_crop_window(s);
+        m.f.x = w.x; m.f.y = w.y; m.f.cw = w.cw; m.f.ch = w.ch;
+    }
+    if (!accmv_resize_window_ok(&m, s->w_mbs, s->h_mbs)) return H264SWDEC_PARAM_ERR;
+    if (c->dec.be.export_accmv_resized(c->dec.be.ctx, c->dec.last_out_slot1 - 1, &m, d_dst, hip_stream))
+        return H264SWDEC_PARAM_ERR;         /* (d_dst not on the decoder's GPU) */
+    return H264SWDEC_PIC_RDY;
+}
+
 H264SwDecRet H264SwDecGetTiming(H264SwDecInst decInst, double *parse_s, double *submit_s, double *wait_s,
                                 double *copy_s, u32 *pictures)
 {

@@ -69,6 +69,10 @@ typedef struct H264Backend {
         int  (*keep)(void *ctx, int kind, int on);
         int  (*export_field)(void *ctx, int kind, int slot, const void *desc, void *d_dst, void *hip_stream);
     } field[H264_KEEP_KINDS];
+    /* optional: slot's kept origin map (field[H264_KEEP_ACCMV]'s retention) as
+     * the resized field of desc (a checked h264mi_accmv_resize_desc), like
+     * export_field; NULL when the backend cannot */
+    int  (*export_accmv_resized)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
     /* optional: host memory for the output frames (pinned by the HIP
      * backend, so each picture's D2H copy runs at DMA speed); NULL: malloc */
     void *(*host_alloc)(void *ctx, size_t bytes);

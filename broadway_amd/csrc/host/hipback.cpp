@@ -552,8 +552,11 @@ extern "C" int h264mi_engine_export_residual(h264mi_engine *e, int n, const int 
 extern "C" int h264mi_engine_export_accmv(h264mi_engine *e, int n, const int *streams, const int *slots,
                                           const h264mi_accmv_desc *desc, void *d_out, size_t out_stride,
                                           void *hip_stream) __attribute__((weak));
+extern "C" int h264mi_engine_export_accmv_resized(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                                  const h264mi_accmv_resize_desc *desc, void *d_out, size_t out_stride,
+                                                  void *hip_stream) __attribute__((weak));
 
-// The five exports of slot (desc: a checked descriptor of the engine call's
+// The exports of slot (desc: a checked descriptor of the engine call's
 // kind) to d_dst.  Nothing waits here: the decoder synced before (the slot's
 // flags are on the host), and the export orders itself on the engine's and the
 // caller's stream.
@@ -622,6 +625,12 @@ static int hb_keep(void *vctx, int kind, int on)
 static int hb_export_field(void *vctx, int kind, int slot, const void *desc, void *d_dst, void *hip_stream)
 {
     return hb_fields[kind].export_field(vctx, slot, desc, d_dst, hip_stream);
+}
+
+// the kept origin map of slot as the resized field (a member of its own, like export_tensor_resized)
+static int hb_export_accmv_resized(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
+{
+    return hb_export(vctx, slot, h264mi_engine_export_accmv_resized, desc, d_dst, hip_stream);
 }
 
 // Pinned host blocks (decoder output frames) kept after free for the next
@@ -771,6 +780,7 @@ extern "C" H264Backend h264mi_hip_backend_create(int device)
         be.field[k].keep = have[k] ? hb_keep : NULL;
         be.field[k].export_field = have[k] ? hb_export_field : NULL;
     }
+    be.export_accmv_resized = have[H264_KEEP_ACCMV] && h264mi_engine_export_accmv_resized ? hb_export_accmv_resized : NULL;
     be.host_alloc = hb_host_alloc;
     be.host_free = hb_host_free;
     be.records_wait = hb_records_wait;

@@ -78,6 +78,9 @@ of the wasm glue of Decoder/src/Decoder.c:44-162:
   -- the delivered picture's accumulated motion over the SPS crop window,
   built by ``H264SwDecLastPictureAccMotion`` on torch's current stream; the
   arguments of ``Engine.to_accmv`` (default: channels ("adx", "ady"), int16).
+  With ``"size": (oh, ow)`` the field is resized on the GPU
+  (``H264SwDecLastPictureAccMotionResized``) and ``decoder.accmv`` is ``(C, oh,
+  ow)``.
 
 Unlike the reference module (a single global instance) every ``Decoder`` has
 its own H264SwDec instance, so several streams can be decoded side by side.
@@ -112,6 +115,7 @@ class _Field(NamedTuple):
     shape: Callable         # (rows, columns) of (descriptor, x, y, cw, ch): what `last` covers of the crop window
     kept: str               # what the backend keeps for it (the error text of `keep`)
     what: str               # what it exports (the error text of `last`)
+    resized: Optional[str] = None       # the H264SwDecLastPicture*Resized call of its `size` key (None: it has none)
 
 
 # in the order __init__ takes the options; _emit exports in the reverse order
@@ -123,7 +127,8 @@ _FIELDS = {
                        lambda d, x, y, cw, ch: tuple(v >> (d.planes == _lib.RESID_PLANES["uv"]) for v in (ch, cw)),
                        "coefficients", "the residual"),
     "accmv": _Field("accmv_desc", "channels", ("adx", "ady"), "H264SwDecKeepAccMotion", "H264SwDecLastPictureAccMotion",
-                    lambda d, x, y, cw, ch: (ch, cw), "origin maps", "the origin map"),
+                    lambda d, x, y, cw, ch: (ch, cw), "origin maps", "the origin map",
+                    "H264SwDecLastPictureAccMotionResized"),
 }
 
 
@@ -153,7 +158,7 @@ class Decoder:
             opts = self.options.get(name) or None
             if opts is not None:
                 opts = {} if opts is True else dict(opts)
-                unknown = set(opts) - {f.first, "dtype", "scale", "bias"}
+                unknown = set(opts) - {f.first, "dtype", "scale", "bias"} - ({"size"} if f.resized else set())
                 if unknown:
                     raise ValueError(f"{name}: unknown keys {sorted(unknown)}")
                 from . import engine                 # (imports torch)
@@ -287,8 +292,11 @@ class Decoder:
         without one; mbinfo: the blocks covering it)."""
         f = _FIELDS[name]
         desc, n, dtype = self._fields[name]
-        out, st = self._device_empty((n,) + f.shape(desc, *self._crop_window()), dtype)
-        ret = getattr(self._L, f.last)(self._inst, C.byref(desc), out.data_ptr(), st)
+        resized = hasattr(desc, "oh")           # the option's `size`: a resize descriptor
+        out, st = self._device_empty((n,) + ((desc.oh, desc.ow) if resized else f.shape(desc, *self._crop_window())),
+                                     dtype)
+        last = getattr(self._L, f.resized if resized else f.last, None)
+        ret = last(self._inst, C.byref(desc), out.data_ptr(), st) if last else _lib.H264SWDEC_PARAM_ERR
         if ret != _lib.H264SWDEC_PIC_RDY:
             raise RuntimeError(f"{name}: the backend cannot export {f.what} ({ret}; there is no host fallback)")
         return out

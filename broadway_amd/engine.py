@@ -60,6 +60,30 @@ def tensor_colour_bits(colour, unspecified=None, mode="rgb", stream_ok=False):
             _lib.TENSOR_UNSPECIFIED[unspecified] << _lib.TENSOR_UNSPEC_SHIFT)
 
 
+def _resize_size(size):
+    """(oh, ow) of a resized export's ``size``, each 1..16384."""
+    try:
+        oh, ow = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"size {size!r}: (oh, ow)") from None
+    if not (1 <= oh <= _lib.RESIZE_MAX_DIM and 1 <= ow <= _lib.RESIZE_MAX_DIM):
+        raise ValueError(f"size {size!r}: oh and ow are 1..{_lib.RESIZE_MAX_DIM}")
+    return oh, ow
+
+
+def _field_resized(resized, built, size):
+    """A field descriptor triple ``built`` with its descriptor wrapped into the
+    resize descriptor ``resized`` (``f``, then ow, oh and the filter) of
+    ``size`` = (oh, ow); ``size`` None: ``built`` as it is."""
+    if size is None:
+        return built
+    oh, ow = _resize_size(size)
+    f, n, dtype = built
+    d = resized()
+    d.f, d.ow, d.oh, d.filter = f, ow, oh, _lib.RESIZE_TRIANGLE
+    return d, n, dtype
+
+
 def tensor_desc(window, mode="rgb", dtype=None, scale=None, bias=None, mean=None, std=None, size=None, colour=None,
                 unspecified=None, stream_ok=False):
     """(``_lib.TensorDesc``, planes, torch dtype) of a tensor export
@@ -71,12 +95,7 @@ def tensor_desc(window, mode="rgb", dtype=None, scale=None, bias=None, mean=None
     (``tensor_colour_bits``; None: the reference's BT.601 limited range)."""
     import torch
     if size is not None:
-        try:
-            oh, ow = (int(v) for v in size)
-        except (TypeError, ValueError):
-            raise ValueError(f"size {size!r}: (oh, ow)") from None
-        if not (1 <= oh <= _lib.RESIZE_MAX_DIM and 1 <= ow <= _lib.RESIZE_MAX_DIM):
-            raise ValueError(f"size {size!r}: oh and ow are 1..{_lib.RESIZE_MAX_DIM}")
+        oh, ow = _resize_size(size)
         t, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std, None, colour, unspecified, stream_ok)
         d = _lib.TensorResizeDesc()
         d.t, d.ow, d.oh, d.filter = t, ow, oh, _lib.RESIZE_TRIANGLE
@@ -204,7 +223,7 @@ def residual_desc(planes="y", window=None, dtype=None, scale=None, bias=None):
     return _field_desc(d, {"y": 1, "uv": 2, "yuv": 3}[planes], "plane", window, dtype, scale, bias, uv=planes == "uv")
 
 
-def accmv_desc(channels=("adx", "ady"), window=None, dtype=None, scale=None, bias=None):
+def accmv_desc(channels=("adx", "ady"), window=None, dtype=None, scale=None, bias=None, size=None):
     """(``_lib.AccMvDesc``, number of channels, torch dtype) of an export of
     the accumulated motion (Engine.to_accmv, Decoder's ``accmv`` option;
     include/h264mi.h defines the field): ``channels`` names the planes, in
@@ -213,14 +232,18 @@ def accmv_desc(channels=("adx", "ady"), window=None, dtype=None, scale=None, bia
     for the decoder's SPS crop window (cw = ch = 0 in the descriptor).
     ``dtype``: torch.int16 (the default; the integer itself) or float16 /
     bfloat16 / float32, ``fma(v, scale[c], bias[c])`` of channel position c;
-    scale and bias are scalars or one value per channel, default 1 and 0."""
+    scale and bias are scalars or one value per channel, default 1 and 0.
+    With ``size`` = (oh, ow), each 1..16384, the descriptor is a
+    ``_lib.AccMvResizeDesc`` of the resized export (its ``f`` is the one
+    above): the window's integer field filtered to oh x ow per channel
+    (DESIGN 3.5i), int16 rounded to the nearest integer, halves up."""
     ids = _field_channels(channels, _lib.ACCMV_CHANNELS, _lib.ACCMV_MAX_CH)
     d = _lib.AccMvDesc()
     d.nch, d.id[:len(ids)] = len(ids), ids
-    return _field_desc(d, len(ids), "channel", window, dtype, scale, bias)
+    return _field_resized(_lib.AccMvResizeDesc, _field_desc(d, len(ids), "channel", window, dtype, scale, bias), size)
 
 
-def accres_desc(planes="y", window=None, dtype=None, scale=None, bias=None, colour=None, unanchored="key"):
+def accres_desc(planes="y", window=None, dtype=None, scale=None, bias=None, colour=None, unanchored="key", size=None):
     """(``_lib.AccResDesc``, number of planes, torch dtype) of an export of the
     accumulated residual (Engine.to_accres; include/h264mi.h defines the
     field): every sample of the picture minus its
@@ -231,7 +254,9 @@ def accres_desc(planes="y", window=None, dtype=None, scale=None, bias=None, colo
     ``_lib.TENSOR_COLOURS`` but "stream", None is "reference"; "rgb" only).
     ``unanchored``: "key" -- a sample whose chain back started at an intra MB is
     set against the key picture where that chain started -- or "zero": such a
-    sample is 0.  window, dtype, scale and bias as for ``residual_desc``."""
+    sample is 0.  window, dtype, scale and bias as for ``residual_desc``;
+    ``size`` as for ``accmv_desc`` (a ``_lib.AccResResizeDesc``; "uv": its
+    half-resolution grid is what is resized)."""
     if not isinstance(planes, str) or planes not in _lib.ACCRES_PLANES:
         raise ValueError(f"planes {planes!r}: one of {sorted(_lib.ACCRES_PLANES)}")
     if not isinstance(unanchored, str) or unanchored not in _lib.ACCRES_UNANCHORED:
@@ -244,8 +269,9 @@ def accres_desc(planes="y", window=None, dtype=None, scale=None, bias=None, colo
     d = _lib.AccResDesc()
     d.planes = _lib.ACCRES_PLANES[planes]
     d.colour, d.unanchored = _lib.TENSOR_COLOURS[colour], _lib.ACCRES_UNANCHORED[unanchored]
-    return _field_desc(d, {"y": 1, "uv": 2, "yuv": 3, "rgb": 3}[planes], "plane", window, dtype, scale, bias,
-                       uv=planes == "uv")
+    return _field_resized(_lib.AccResResizeDesc,
+                          _field_desc(d, {"y": 1, "uv": 2, "yuv": 3, "rgb": 3}[planes], "plane", window, dtype, scale,
+                                      bias, uv=planes == "uv"), size)
 
 
 @dataclass
@@ -453,7 +479,10 @@ class Engine:
         if window is None:
             window = (0, 0, self.w_mbs * unit, self.h_mbs * unit)
         desc, planes, dtype = build(window)
-        rows, cols = (desc.bh, desc.bw) if blocks else (desc.ch >> uv, desc.cw >> uv)
+        if hasattr(desc, "oh"):                 # a resize descriptor
+            rows, cols = desc.oh, desc.ow
+        else:
+            rows, cols = (desc.bh, desc.bw) if blocks else (desc.ch >> uv, desc.cw >> uv)
         out, st = self._out((n, planes, rows, cols), dtype, out, stream)
         if not hasattr(self._L, entry) or \
                 getattr(self._L, entry)(self._h, n, c_streams, c_slots, C.byref(desc), out.data_ptr(),
@@ -567,17 +596,21 @@ class Engine:
             raise RuntimeError("h264mi_engine_keep_accmv failed")
 
     def to_accmv(self, streams: Sequence[int], slots: Sequence[int], channels=("adx", "ady"), window=None,
-                 dtype=None, scale=None, bias=None, out=None, stream=None):
+                 dtype=None, scale=None, bias=None, out=None, stream=None, size=None):
         """The accumulated motion of the pictures last decoded into the slots
         (streams[k], slots[k]) as one ``(n, C, ch, cw)`` torch tensor on
         ``cuda:{self.device}``, one element per luma sample of ``window`` = (x,
         y, cw, ch) (None: the whole MB-aligned picture) and per name in
         ``channels`` (``accmv_desc``; a slot nothing was decoded into reads as
         (x, y, 0): no displacement, not anchored).  Needs ``keep_accmv()``
-        before the decodes.  ``out`` and ``stream`` as for ``to_tensor``; the
-        host is never synchronised."""
-        return self._export_field("h264mi_engine_export_accmv", "keep_accmv", streams, slots, window,
-                                  lambda w: accmv_desc(channels, w, dtype, scale, bias), out, stream)
+        before the decodes.  ``size`` = (oh, ow): the window's integer field
+        resized on the GPU before the conversion (``accmv_desc``; a window at
+        most 32 times the output and 16384 samples on each axis) -- the result
+        is ``(n, C, oh, ow)``.  ``out`` and ``stream`` as for ``to_tensor``;
+        the host is never synchronised."""
+        entry = "h264mi_engine_export_accmv" if size is None else "h264mi_engine_export_accmv_resized"
+        return self._export_field(entry, "keep_accmv", streams, slots, window,
+                                  lambda w: accmv_desc(channels, w, dtype, scale, bias, size), out, stream)
 
     def keep_accres(self, nkeys: int = 2) -> None:
         """Keep the samples of each stream's last ``nkeys`` (1..8) key pictures
@@ -612,7 +645,7 @@ class Engine:
         return bool(r)
 
     def to_accres(self, streams: Sequence[int], slots: Sequence[int], planes="y", window=None, dtype=None,
-                  scale=None, bias=None, colour=None, unanchored="key", out=None, stream=None):
+                  scale=None, bias=None, colour=None, unanchored="key", out=None, stream=None, size=None):
         """The accumulated residual of the pictures last decoded into the slots
         (streams[k], slots[k]) -- each sample minus its origin in the key
         picture of its GOP -- as one ``(n, 1 | 2 | 3, rows, columns)`` torch
@@ -621,11 +654,13 @@ class Engine:
         (None: the whole MB-aligned picture), "uv" ``(ch / 2, cw / 2)``
         (``accres_desc``; a slot whose key is not held -- ``accres_held`` --
         reads as zeros).  Needs ``keep_accmv()`` and ``keep_accres()`` before
-        the decodes.  ``out`` and ``stream`` as for ``to_tensor``; the host is
-        never synchronised."""
-        return self._export_field("h264mi_engine_export_accres", "keep_accres", streams, slots, window,
-                                  lambda w: accres_desc(planes, w, dtype, scale, bias, colour, unanchored), out, stream,
-                                  uv=planes == "uv")
+        the decodes.  ``size`` = (oh, ow): each plane resized on the GPU as for
+        ``to_accmv`` -- the result is ``(n, 1 | 2 | 3, oh, ow)``.  ``out`` and
+        ``stream`` as for ``to_tensor``; the host is never synchronised."""
+        entry = "h264mi_engine_export_accres" if size is None else "h264mi_engine_export_accres_resized"
+        return self._export_field(entry, "keep_accres", streams, slots, window,
+                                  lambda w: accres_desc(planes, w, dtype, scale, bias, colour, unanchored, size), out,
+                                  stream, uv=planes == "uv")
 
     @property
     def device(self) -> int:

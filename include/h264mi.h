@@ -424,6 +424,40 @@ typedef struct {
 } h264mi_accres_desc;
 /* (The export is an engine-level call for now: h264mi_accres_device and
  * h264mi_engine_keep_accres / _export_accres below; there is no H264SwDec call.) */
+/* The two fields above resized on the GPU (field_resize.hip): the
+ * window's integer field filtered to oh x ow samples per channel or plane, so
+ * that motion and residual arrive at a network's input size the way the pixels
+ * do (h264mi_tensor_resize_desc).  `f` is the unresized export's descriptor.
+ * Source samples: s[y][x] is the integer v that export defines for the channel
+ * or plane on the window's own grid -- accmv: cw x ch samples, |v| <= 32767;
+ * accres Y / YUV / RGB: cw x ch samples, |v| <= 255, after the `unanchored`
+ * policy (a zeroed sample is a source sample 0); accres UV: the half-resolution
+ * grid, cw / 2 x ch / 2.  A picture without a key is all zeros.
+ * Per axis, n source samples -> m outputs, h264mi_tensor_resize_desc's taps:
+ * R = 2 max(m, n); output j has C = (2 j + 1) n - m; source sample k, 0 <= k <
+ * n, weighs w_k = R - |2 m k - C| where that is positive; q_k = (w_k * 16384 +
+ * W / 2) / W with W = sum w_k, and 16384 - sum q_k goes to the first tap of
+ * largest weight; at most 64 taps (n <= 32 m).
+ * Both axes, no intermediate rounding:
+ *   acc = sum_l qy_l * (sum_k qx_k * s[l][k])   (the inner sum is below 2^29 in
+ *         magnitude, acc below 2^43; exact integers, any order)
+ *   r   = (acc + 2^23) >> 24, an arithmetic shift: the filtered value in units
+ *         of 1 / 16, |r| < 2^19.
+ * Elements: H264MI_TENSOR_I16 (r + 8) >> 4, arithmetic (halves go up); F16 /
+ * BF16 / F32 fma((float)r * 0.0625f, scale[c], bias[c]) ((float)r * 0.0625f is
+ * exact), converted as for h264mi_tensor_desc; U8 is refused.  With (oh, ow) ==
+ * the grid every output has the single tap 16384, r = 16 s, and the bytes are
+ * the unresized export's.
+ * Rules: f's own; filter == H264MI_RESIZE_TRIANGLE; 1 <= ow, oh <= 16384; the
+ * source grid at most 16384 a side and at most 32 ow by 32 oh. */
+typedef struct { h264mi_accmv_desc  f; int ow, oh, filter; } h264mi_accmv_resize_desc;
+typedef struct { h264mi_accres_desc f; int ow, oh, filter; } h264mi_accres_resize_desc;
+/* H264SwDecLastPictureAccMotion with the resized field of `desc` (not NULL), as
+ * (nch, oh, ow) elements at d_dst; desc->f.cw == 0 and desc->f.ch == 0: the
+ * active SPS's crop window.  Retention comes from H264SwDecKeepAccMotion; the
+ * return codes are H264SwDecLastPictureAccMotion's. */
+H264SwDecRet H264SwDecLastPictureAccMotionResized(H264SwDecInst decInst, const h264mi_accmv_resize_desc *desc,
+                                                  void *d_dst, void *hip_stream);
 /* Extension (no reference counterpart): where an instance's time went, in
  * seconds since H264SwDecInit -- host parse (NAL extraction, headers, CAVLC /
  * MB layer, DPB, concealment), record upload + kernel launch, waiting for the
@@ -792,6 +826,29 @@ int  h264mi_engine_accres_held(h264mi_engine *e, int stream, int slot);
  * bad stream, slot or desc, or when d_out is not on the engine's device. */
 int  h264mi_engine_export_accres(h264mi_engine *e, int n, const int *streams, const int *slots,
                                  const h264mi_accres_desc *desc, void *d_out, size_t out_stride, void *hip_stream);
+/* h264mi_accmv_device and h264mi_accres_device with the resized fields of an
+ * h264mi_accmv_resize_desc / h264mi_accres_resize_desc: the same arguments,
+ * picture k's (nch | planes, oh, ow) elements, contiguous, at d_out + k *
+ * out_stride.  d_out and out_stride are multiples of the element size (the
+ * resized rows are short: there is no 16-byte rule); nothing else is written,
+ * and nothing outside the maps' words and the frames' planes is read (every
+ * pointer and offset a multiple of 4, as for the unresized calls).  -1 on a bad
+ * argument, nothing launched. */
+int  h264mi_accmv_resize_device(const void *d_maps, const size_t *map_offsets, int npics, int w_mbs, int h_mbs,
+                                const h264mi_accmv_resize_desc *desc, void *d_out, size_t out_stride,
+                                void *hip_stream);
+int  h264mi_accres_resize_device(const void *d_cur, const size_t *cur_offsets, const void *d_key,
+                                 const size_t *key_offsets, const void *d_maps, const size_t *map_offsets, int npics,
+                                 int w_mbs, int h_mbs, const h264mi_accres_resize_desc *desc, void *d_out,
+                                 size_t out_stride, void *hip_stream);
+/* h264mi_engine_export_accmv and h264mi_engine_export_accres with the resized
+ * fields: the same retention, ordering, held-key rule and return codes */
+int  h264mi_engine_export_accmv_resized(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                        const h264mi_accmv_resize_desc *desc, void *d_out, size_t out_stride,
+                                        void *hip_stream);
+int  h264mi_engine_export_accres_resized(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                         const h264mi_accres_resize_desc *desc, void *d_out, size_t out_stride,
+                                         void *hip_stream);
 int  h264mi_engine_sync(h264mi_engine *e);
 /* number of (launch, picture) slots flagged since the last call: residual
  * range errors (reference transform.c:181) or a bounded wait that expired;
