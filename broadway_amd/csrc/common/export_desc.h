@@ -1,5 +1,5 @@
 /* The descriptor rules of the device-tensor exports (include/h264mi.h), stated
- * once for the engine (hip/engine.hip) and the H264SwDec calls (host/api.c).
+ * once for the engine (hip/exports.hip) and the H264SwDec calls (host/api.c).
  * Each descriptor's rules come in two parts, because api.c refuses the first
  * before it looks for headers and the second before it takes a picture:
  *   *_fixed_ok    what does not depend on the picture (element type, channels,
@@ -18,7 +18,7 @@
 #define H264MI_RESIZE_MAX_DIM 16384     /* ow, oh, cw, ch of a resized export (resize.hip's RESIZE_MAX_DIM) */
 
 #ifdef __cplusplus
-#define EXPORT_CONSTEXPR constexpr      /* engine.hip checks it against the kernels' tensor_elem_size */
+#define EXPORT_CONSTEXPR constexpr      /* exports.hip checks it against the kernels' tensor_elem_size */
 #else
 #define EXPORT_CONSTEXPR
 #endif

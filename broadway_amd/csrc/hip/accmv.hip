@@ -27,6 +27,13 @@
 // or 4 consecutive map words, again 4-byte aligned) or one element; each item
 // reads its words once and stores every channel, non-temporally.
 
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../../include/h264mi_records.h"
+#include "crop.hip"
+#include "tensor.hip"
+#include "field_store.h"
 #define ACCMV_MAX_PICS 32           // pictures per export launch (their offsets travel in the kernel arguments)
 #define ACCMV_MAX_CH 8
 #define ACCMV_STEP_PICS 8           // pictures per step launch (their slot tables travel in the kernel arguments)

@@ -36,6 +36,15 @@
 // A picture without a key (key_off == ~0) is a uniform branch that stores
 // fma(0, scale, bias) and reads neither K nor anything else.
 
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "mb_shared.h"
+#include "color.hip"
+#include "crop.hip"
+#include "tensor.hip"
+#include "field_store.h"
+#include "accmv.hip"
 #define ACCRES_MAX_PICS 32          // pictures per launch (their offsets travel in the kernel arguments)
 
 enum { ACCRES_Y = 0, ACCRES_UV = 1, ACCRES_YUV = 2, ACCRES_RGB = 3 };

@@ -18,6 +18,10 @@
 // contiguous span (64 x 4 B of Y, 64 x 2 B of U or V, 64 x 16 B of RGBA),
 // two at a row end.
 
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "mb_shared.h"
 __device__ __forceinline__ uint32_t rgba_px(int y, int cr, int cg, int cb)
 {
     const int a0 = 1192 * (y - 16);

@@ -11,6 +11,7 @@
 // 8x8 samples.  Neighbour loads are sc1 (L2, past this CU's L1) and every
 // MB's stores drain before the next MB reads: a wave's own earlier stores
 // are what it reads.
+#pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -28,6 +28,10 @@
 // 4 x 8 bytes (row starts are 8 mod 16 in odd rows), and a row pair's last
 // group is 2 columns wide.
 
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "color.hip"
 typedef uint32_t crop_u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t crop_u32x2 __attribute__((ext_vector_type(2)));
 

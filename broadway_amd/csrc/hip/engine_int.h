@@ -5,7 +5,8 @@
  * public h264mi_engine_* ones (include/h264mi.h).  tests/null_device/
  * implements the same interface (and the HIP calls the adapter makes) on the
  * CPU, so that the adapter's threading runs under TSan / ASan without a GPU.
- * Not part of the C-ABI. */
+ * Not part of the C-ABI.  These functions live in engine.hip, the core unit;
+ * what engine.hip and exports.hip share between themselves is engine_priv.h. */
 #ifndef H264MI_ENGINE_INT_H
 #define H264MI_ENGINE_INT_H
 

@@ -42,6 +42,15 @@
 // A picture without a key (accres) skips the chunks: it reads nothing and
 // stores fma(0, scale, bias).
 
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "crop.hip"
+#include "tensor.hip"
+#include "resize.hip"
+#include "field_store.h"
+#include "accmv.hip"
+#include "accres.hip"
 #define FRESIZE_TPITCH (RESIZE_ROWS + 1)    // int32 per column of t
 #define FRESIZE_STAGE_DW 5120               // staging buffer: 4 rows of the widest tile (32 : 1, 1065 dwords a row), 16 rows of
                                             // 1080p -> 224 (293); with it accmv's 37.9 KB of LDS leave room for 4 workgroups per CU

@@ -1,8 +1,13 @@
 // What the four field exports (k_mbinfo, k_residual, k_accmv, k_accres: signed
 // values as int16 / fp16 / bf16 / fp32 with a per-channel fma) share: an
-// element's bits, an item's store and the launch for (dtype, v16).  Included
-// by engine.hip behind tensor.hip (tensor_float_bits, tensor_elem_size) and
-// crop.hip (crop_u32x4).
+// element's bits, an item's store and the launch for (dtype, v16).  From
+// tensor.hip it takes tensor_float_bits and tensor_elem_size, from crop.hip
+// crop_u32x4.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "crop.hip"
+#include "tensor.hip"
 
 // v as the element type's bits: int16 keeps v's low 16 bits, the float types
 // hold fma((float)v, s, b), converted as in tensor.hip

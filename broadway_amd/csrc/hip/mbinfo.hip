@@ -29,6 +29,13 @@
 // MBs) stay 2-way for every linear stride 24 .. 40, and the fill's ds_write_b32
 // become 2-way, which costs a store nothing.
 
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../../include/h264mi_records.h"
+#include "crop.hip"
+#include "tensor.hip"
+#include "field_store.h"
 #define MBINFO_MAX_PICS 32          // pictures per launch (their offsets travel in the kernel arguments)
 #define MBINFO_MAX_CH 16
 #define MBINFO_COLS 128             // window columns (4x4 blocks) per workgroup; a multiple of every item width

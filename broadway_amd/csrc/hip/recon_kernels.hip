@@ -17,12 +17,14 @@
 //              raster-equivalent order (h264bsdFilterPicture,
 //              deblocking.c:574-1736) and hand the final bottom rows to the
 //              row below through tagged-granule mailboxes.
+#pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../../include/h264mi_records.h"
 #include "../common/mc_window.h"
 #include "wgpp_variants.h"
 #include "deblock_lanes.h"
+#include "mb_shared.h"
 
 #define WAVE 64
 // profiling build: u64 stamps per MB (row waves [0..2], MC [3], intra [4..5])
@@ -145,8 +147,6 @@ struct ReconArgs {
 #define CHK_NODB    2048u   // a PD_NO_DEBLOCK picture holds an MB that filters (row_drain)
 
 __constant__ uint8_t cZigzag[16] = {0, 1, 4, 8, 5, 2, 3, 6, 9, 12, 13, 10, 7, 11, 14, 15};
-__constant__ uint8_t cLevelScale[6][3] = {
-    {10, 16, 13}, {11, 18, 14}, {13, 20, 16}, {14, 23, 18}, {16, 25, 20}, {18, 29, 23}};
 __constant__ uint8_t cAlpha[52] = {
     0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 4, 4, 5, 6, 7, 8, 9, 10,
     12, 13, 15, 17, 20, 22, 25, 28, 32, 36, 40, 45, 50, 56, 63, 71, 80, 90,
@@ -233,24 +233,13 @@ __device__ __forceinline__ void drain_vm() { asm volatile("s_waitcnt vmcnt(0)" :
 
 __device__ __forceinline__ int clip255(int v) { return min(max(v, 0), 255); }
 __device__ __forceinline__ int clip3(int lo, int hi, int v) { return min(max(v, lo), hi); }
-__device__ __forceinline__ int blk_x(int b) { return mcw_blk_x(b); }
-__device__ __forceinline__ int blk_y(int b) { return mcw_blk_y(b); }
+// (blk_x, blk_y: mb_shared.h)
 __device__ __forceinline__ int blk_of(int x4, int y4) { return ((y4 >> 1) * 2 + (x4 >> 1)) * 4 + (y4 & 1) * 2 + (x4 & 1); }
 
 // ---------------------------------------------------------------------------
 // residual: dequant + inverse transforms (transform.c:94-398) for one MB.
-// Residual hand-off k_prep -> k_wgpp, compact: only the 4x4 blocks that can
-// carry a residual travel, 32 B each, in cbits bit order, from the start of
-// the MB's 768-B slot.  res_mask: AC-coded blocks plus every block of a plane
-// whose DC transform is coded (I16 luma DC, chroma DC of that plane).
-__device__ __forceinline__ uint32_t res_mask(int type, uint32_t cbits)
-{
-    uint32_t m = cbits & 0xFFFFFFu;
-    if (type == MBT_I16 && ((cbits >> 24) & 1)) m |= 0xFFFFu;
-    if ((cbits >> 25) & 1) m |= 0xF0000u;
-    if ((cbits >> 26) & 1) m |= 0xF00000u;
-    return m;
-}
+// Residual hand-off k_prep -> k_wgpp: compact, the res_mask blocks
+// (mb_shared.h) of the MB.
 
 // res: the MB's compact residual slot (global, res_mask blocks in bit order,
 // 16 raster int16 each).  dc: LDS int32[24].
@@ -1008,10 +997,7 @@ __device__ __forceinline__ int absd(int a, int b) { return (int)__builtin_amdgcn
 // sinking them into exec-masked blocks (each costs more scalar work than it
 // saves)
 #define MATERIALIZE(x) asm volatile("" : "+v"(x))
-// median of three = clamp lo <= x <= hi for lo <= hi, in this form one
-// v_med3_i32 (min(max(x, lo), hi) is two instructions unless both bounds are
-// constants)
-__device__ __forceinline__ int med3i(int x, int lo, int hi) { return min(max(x, lo), max(min(x, lo), hi)); }
+// (med3i, the one-instruction clamp: mb_shared.h)
 // c - 2 * x in one v_mad_i32_i24 (the compiler emits a shift and a subtract)
 __device__ __forceinline__ int mad_m2(int x, int c)
 {

@@ -35,6 +35,14 @@
 // and stay 2-way for every even S (S * row mod 4 takes two values); an odd S
 // would misalign the 8-byte writes.
 
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../../include/h264mi_records.h"
+#include "mb_shared.h"
+#include "crop.hip"
+#include "tensor.hip"
+#include "field_store.h"
 #define RESID_MAX_PICS 32           // pictures per launch (their offsets travel in the kernel arguments)
 #define RESID_COLS 64               // luma window columns per workgroup: 4 MBs, a multiple of every item width
 #define RESID_LDS_MBS (RESID_COLS / 16 + 1)     // a window can start inside an MB

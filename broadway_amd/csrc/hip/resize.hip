@@ -34,6 +34,11 @@
 //   at the end: round, tensor_elem<DT>, one non-temporal store per element
 //   (rows are short and start on any element).
 
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "crop.hip"
+#include "tensor.hip"
 #define RESIZE_TW 32                // output columns of a tile
 #define RESIZE_TH 16                // output rows of a tile
 #define RESIZE_THREADS 256

@@ -22,6 +22,11 @@
 // Luma and chroma bytes come from aligned dwords through v_alignbyte, as in
 // crop.hip (x can be 2 mod 4, x / 2 odd, a picture can start on any byte).
 
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "color.hip"
+#include "crop.hip"
 #define TENSOR_MAX_PICS 32          // pictures per launch (their offsets travel in the kernel arguments)
 
 enum { TENSOR_RGB = 0, TENSOR_GRAY = 1 };

@@ -1,7 +1,8 @@
 // k_wgpp's instances and the choice among them, stated once.  Plain C++17, no
-// HIP: recon_kernels.hip takes the block size from here, engine.hip derives
-// from the list the kernels it emits, their addresses, LDS sizes and launch
-// attributes, and tests/wgpp_variant_check.cpp walks the selection on the CPU.
+// HIP: recon_kernels.hip takes the block size from here, engine.hip (the core
+// unit; exports.hip never sees this list) derives from the list the kernels it
+// emits, their addresses, LDS sizes and launch attributes, and
+// tests/wgpp_variant_check.cpp walks the selection on the CPU.
 #ifndef H264MI_WGPP_VARIANTS_H
 #define H264MI_WGPP_VARIANTS_H
 

@@ -1,4 +1,4 @@
-"""The descriptor rules the engine (engine.hip) and the H264SwDec calls (api.c)
+"""The descriptor rules the engine (exports.hip) and the H264SwDec calls (api.c)
 share, broadway_amd/csrc/common/export_desc.h, on the CPU: tests/export_desc_check.c
 walks each validator over a grid on a 6 x 4 MB picture under AddressSanitizer +
 UBSan and prints accept or refuse per row.  The expected column below is
