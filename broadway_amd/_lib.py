@@ -89,6 +89,11 @@ class TensorResizeDesc(C.Structure):
     _fields_ = [("t", TensorDesc), ("ow", C.c_int), ("oh", C.c_int), ("filter", C.c_int)]
 
 
+class Roi(C.Structure):
+    """h264mi_roi (include/h264mi.h)."""
+    _fields_ = [(n, C.c_int) for n in ("pic", "x", "y", "cw", "ch")]
+
+
 class MbInfoDesc(C.Structure):
     """h264mi_mbinfo_desc (include/h264mi.h)."""
     _fields_ = [(n, C.c_int) for n in ("bx", "by", "bw", "bh", "nch", "dtype")] + \
@@ -151,6 +156,7 @@ TENSOR_UNSPECIFIED = {"bt601": 0, "bt709": 1, "size": 2}
 TENSOR_COLOUR_SHIFT, TENSOR_UNSPEC_SHIFT = 8, 12
 RESIZE_TRIANGLE = 0
 RESIZE_MAX_DIM = 16384
+ROIS_MAX_PER_LAUNCH = 32
 TENSOR_U8, TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 0, 1, 2, 3
 
 HEADERS_CB = C.CFUNCTYPE(None, C.c_void_p)
@@ -282,6 +288,14 @@ def mi() -> C.CDLL:
         L.h264mi_engine_export_tensor_resized.restype = i32
         L.H264SwDecNextPictureTensorResized.argtypes = [vp, C.POINTER(H264SwDecPicture), u32, rd, vp, vp]
         L.H264SwDecNextPictureTensorResized.restype = i32
+    if hasattr(L, "h264mi_tensor_rois_device_pitch"):       # (optional, as above)
+        rd, ro = C.POINTER(TensorResizeDesc), C.POINTER(Roi)
+        L.h264mi_tensor_rois_device_pitch.argtypes = [vp, C.POINTER(sz), i32, i32, i32, i32, rd, ro, i32, vp, sz, vp]
+        L.h264mi_tensor_rois_device_pitch.restype = i32
+        L.h264mi_engine_export_tensor_rois.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), rd, ro, i32, vp, sz, vp]
+        L.h264mi_engine_export_tensor_rois.restype = i32
+        L.H264SwDecLastPictureTensorRois.argtypes = [vp, rd, ro, u32, vp, vp]
+        L.H264SwDecLastPictureTensorRois.restype = i32
     if hasattr(L, "h264mi_mbinfo_device"):                  # (optional, as above)
         md = C.POINTER(MbInfoDesc)
         L.h264mi_mbinfo_device.argtypes = [vp, C.POINTER(sz), i32, i32, i32, md, vp, sz, vp]

@@ -82,6 +82,21 @@ static inline int resize_window_ok(const h264mi_tensor_resize_desc *d, int width
            d->t.ch <= H264MI_RESIZE_MAX_DIM && d->t.cw <= 32 * d->ow && d->t.ch <= 32 * d->oh;
 }
 
+/* a list of h264mi_roi over npics pictures of width x height under d: at least
+ * one box, every pic in [0, npics), every box a window resize_window_ok accepts
+ * with d's (ow, oh), and d's own window reserved (all zero).  All or nothing. */
+static inline int rois_ok(const h264mi_tensor_resize_desc *d, const h264mi_roi *r, int nrois, int npics, int width,
+                          int height)
+{
+    if (nrois < 1 || !resize_desc_fixed_ok(d) || (d->t.x | d->t.y | d->t.cw | d->t.ch)) return 0;
+    for (int k = 0; k < nrois; k++) {
+        h264mi_tensor_resize_desc b = *d;
+        b.t.x = r[k].x; b.t.y = r[k].y; b.t.cw = r[k].cw; b.t.ch = r[k].ch;
+        if (r[k].pic < 0 || r[k].pic >= npics || !resize_window_ok(&b, width, height)) return 0;
+    }
+    return 1;
+}
+
 /* h264mi_mbinfo_desc: the window is in 4x4 blocks of a w_mbs x h_mbs picture */
 static inline int mbinfo_desc_fixed_ok(const h264mi_mbinfo_desc *d)
 {

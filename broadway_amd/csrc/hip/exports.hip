@@ -406,6 +406,54 @@ extern "C" int h264mi_tensor_resize_device_pitch(const void *d_in, const size_t 
                          (hipStream_t)stream);
 }
 
+// The resized export over a list of boxes (resize.hip k_tensor_resize with
+// ROIS): box r, the window rois[r].(x, y, cw, ch) of the picture that starts
+// in_offsets[rois[r].pic] bytes after d_in, filtered to desc->oh x desc->ow
+// samples per plane: its (planes, oh, ow) elements at d_out + r * out_stride.
+// desc->t's window is reserved (zero).  Everything is checked first (rois_ok:
+// one bad box refuses the call); then one launch per EXPORT_MAX_PICS boxes,
+// each with its rows' picture offsets and windows in the kernel arguments.
+// rois is host memory, read here.  -1 (nothing launched) on a bad argument.
+static_assert(H264MI_ROIS_MAX_PER_LAUNCH == TENSOR_MAX_PICS, "include/h264mi.h and tensor.hip name the same bound");
+
+static bool rois_desc_ok(const h264mi_tensor_resize_desc *d, const h264mi_roi *rois, int nrois, int npics, int width,
+                         int height)
+{
+    return d && rois && tensor_mode_ok(d->t.mode) && rois_ok(d, rois, nrois, npics, width, height);
+}
+
+extern "C" int h264mi_tensor_rois_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width,
+                                               int height, int cpitch, const h264mi_tensor_resize_desc *desc,
+                                               const h264mi_roi *rois, int nrois, void *d_out, size_t out_stride,
+                                               void *stream)
+{
+    if (!d_in || !in_offsets || !d_out || width <= 0 || height <= 0 || ((width | height) & 1) || npics < 1 ||
+        cpitch < width / 2 || !rois_desc_ok(desc, rois, nrois, npics, width, height))
+        return -1;
+    const h264mi_tensor_desc *t = &desc->t;
+    // (d_out is checked here too: a list is one lookup, and a host address would fault every launch of it)
+    if (!export_aligned(d_out, out_stride, export_elem_size(t->dtype)) || h264mi_pointer_device(d_out) < 0) return -1;
+    const int layout = H264MI_TENSOR_LAYOUT(t->mode), colour = H264MI_TENSOR_COLOUR(t->mode);
+    rois_args ra;
+    tensor_args &a = ra.r.t;
+    a.in = (const uint8_t *)d_in;
+    a.width = width; a.height = height; a.cpitch = cpitch;
+    a.x = a.y = a.cw = a.ch = 0;
+    a.out_stride = out_stride;
+    for (int p = 0; p < 3; p++) { a.scale[p] = t->scale[p]; a.bias[p] = t->bias[p]; }
+    a.col = tensor_colour_sets[colour];
+    ra.r.ow = desc->ow; ra.r.oh = desc->oh;
+    std::vector<size_t> off((size_t)nrois);
+    for (int r = 0; r < nrois; r++) off[r] = in_offsets[rois[r].pic];
+    return export_launches(nrois, off.data(), a.in_off, &a.out, d_out, out_stride, [&](int r0, int n) {
+        for (int r = 0; r < EXPORT_MAX_PICS; r++) {
+            const h264mi_roi &b = rois[r0 + (r < n ? r : 0)];
+            ra.win[r][0] = b.x; ra.win[r][1] = b.y; ra.win[r][2] = b.cw; ra.win[r][3] = b.ch;
+        }
+        rois_launch(layout, t->dtype, colour != 0, n, (hipStream_t)stream, ra);
+    });
+}
+
 // An export of the slots (streams[k], slots[k]), k < n, into the caller's
 // device memory with no host synchronisation: the engine's stream waits for
 // what `stream` (NULL: the null stream; ours is non-blocking, so that too goes
@@ -459,6 +507,23 @@ extern "C" int h264mi_engine_export_tensor_resized(h264mi_engine *e, int n, cons
                                                    size_t out_stride, void *stream)
 {
     return engine_export(e, n, streams, slots, desc ? &desc->t : NULL, desc, d_out, out_stride, stream);
+}
+
+// boxes over the frame slots (h264mi_tensor_rois_device_pitch; rois[r].pic
+// indexes the n slots): one ordering of the two streams for the whole list
+extern "C" int h264mi_engine_export_tensor_rois(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                                const h264mi_tensor_resize_desc *desc, const h264mi_roi *rois,
+                                                int nrois, void *d_out, size_t out_stride, void *stream)
+{
+    if (!e || n < 1 || !streams || !slots || !d_out) return -1;
+    const int width = e->w * 16, height = e->h * 16;
+    if (!rois_desc_ok(desc, rois, nrois, n, width, height)) return -1;
+    return export_ordered(e, n, streams, slots, d_out, out_stride, export_elem_size(desc->t.dtype), stream, [&] {
+        std::vector<size_t> off((size_t)n);
+        for (int k = 0; k < n; k++) off[k] = e->frame_bytes * ((size_t)streams[k] * e->nslots + slots[k]);
+        return h264mi_tensor_rois_device_pitch(e->d_frames, off.data(), n, width, height, e->cpitch, desc, rois, nrois,
+                                               d_out, out_stride, e->st);
+    });
 }
 
 // Motion vectors and MB side information as planar fields (mbinfo.hip): the

@@ -33,6 +33,10 @@
 //             accumulator in a register;
 //   at the end: round, tensor_elem<DT>, one non-temporal store per element
 //   (rows are short and start on any element).
+//
+// Regions of interest: with the kernel's ROIS flag a grid row is
+// a box -- the window is the row's own, from a table in the kernel arguments,
+// and box r is the resized tensor of its window.  Everything above is per row.
 
 #pragma once
 #include <hip/hip_runtime.h>
@@ -51,6 +55,13 @@
 struct resize_args {
     tensor_args t;
     int ow, oh;
+};
+
+// the same over a list of boxes: grid row r is box r, the window
+// win[r] = (x, y, cw, ch) of the picture at t.in_off[r]; t's own window is unused
+struct rois_args {
+    resize_args r;
+    int win[TENSOR_MAX_PICS][4];
 };
 
 // the taps of output j of an axis n -> m: q[k * qpitch], k < count, for source
@@ -95,10 +106,12 @@ __device__ __forceinline__ void resize_taps(uint32_t n, uint32_t m, uint32_t j, 
 // luma row are the next row's or the chroma planes'), its one chroma sample is
 // the upper byte of the pair that ends with it (the byte in front of a chroma
 // plane is the plane's in front of it); columns 2 and 3 of that group hold
-// garbage no tap reads.
+// garbage no tap reads.  The window's width is a.cw or, for a grid row with a
+// window of its own (win != NULL: k_tensor_resize's ROIS), win[2].
 template <int MODE, int NIT, bool COL>
-__device__ __forceinline__ void resize_stage(const tensor_args &a, const uint8_t *Y, const uint8_t *U, const uint8_t *V,
-                                             uint32_t *stage, int pitch, int ng, int nit, int xs0, int r0, int tid)
+__device__ __forceinline__ void resize_stage(const tensor_args &a, const int *win, const uint8_t *Y, const uint8_t *U,
+                                             const uint8_t *V, uint32_t *stage, int pitch, int ng, int nit, int xs0,
+                                             int r0, int tid)
 {
     uint32_t y0[NIT][1], y1[NIT][1], u[NIT], v[NIT];
     int so[NIT];
@@ -111,7 +124,7 @@ __device__ __forceinline__ void resize_stage(const tensor_args &a, const uint8_t
         tensor_load<1>(sy, y0[i]);
         tensor_load<1>(sy + a.width, y1[i]);
         if (MODE == TENSOR_RGB) {
-            const int part = c + 4 <= a.cw ? 0 : 1;
+            const int part = c + 4 <= (win ? win[2] : a.cw) ? 0 : 1;
             const size_t co = (size_t)(ry >> 1) * a.cpitch + (c >> 1) - part;
             u[i] = crop_load2(U + co) >> (8 * part);
             v[i] = crop_load2(V + co) >> (8 * part);
@@ -142,11 +155,20 @@ __device__ __forceinline__ void resize_stage(const tensor_args &a, const uint8_t
     }
 }
 
+// the arguments of k_tensor_resize<.., ROIS>, and their resize_args
+template <bool ROIS> struct resize_kernel_args { typedef resize_args type; };
+template <> struct resize_kernel_args<true> { typedef rois_args type; };
+__device__ __forceinline__ const resize_args &resize_part(const resize_args &a) { return a; }
+__device__ __forceinline__ const resize_args &resize_part(const rois_args &a) { return a.r; }
+
 // grid: (tiles of RESIZE_TW x RESIZE_TH outputs in raster order, pictures of
 // this launch), 256 threads; COL (RGB only): the pixels of the colour set
-// ra.t.col instead of the reference's
-template <int MODE, int DT, bool COL = false>
-__global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const resize_args ra)
+// ra.t.col instead of the reference's.  ROIS: a grid row is a box, and its
+// window is the row's own, ka.win[blockIdx.y] = (x, y, cw, ch), read from the
+// kernel arguments like ra.t's (uniform over the workgroup either way); the
+// tile's position depends on (oh, ow) only, so the rows share the grid's x extent.
+template <int MODE, int DT, bool COL = false, bool ROIS = false>
+__global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename resize_kernel_args<ROIS>::type ka)
 {
     constexpr int ES = tensor_elem_size(DT);
     constexpr int NP = MODE == TENSOR_RGB ? 3 : 1;
@@ -156,9 +178,13 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const resize_a
     __shared__ uint16_t qx[RESIZE_MAX_TAPS * RESIZE_TW], qy[RESIZE_MAX_TAPS * RESIZE_TH];
     __shared__ uint16_t tb[NP * RESIZE_TW * RESIZE_TPITCH];
     __shared__ int fx[RESIZE_TW], cx[RESIZE_TW], fy[RESIZE_TH], cy[RESIZE_TH];
+    const resize_args &ra = resize_part(ka);
+    const int *win = nullptr;
+    if constexpr (ROIS) win = ka.win[blockIdx.y];
     const tensor_args &a = ra.t;
     const int tid = (int)threadIdx.x;
-    const int width = a.width, cpitch = a.cpitch, cw = a.cw, ch = a.ch, ow = ra.ow, oh = ra.oh;
+    const int width = a.width, cpitch = a.cpitch, cw = ROIS ? win[2] : a.cw, ch = ROIS ? win[3] : a.ch;
+    const int ow = ra.ow, oh = ra.oh;
     const int ntx = (ow + RESIZE_TW - 1) / RESIZE_TW;
     const int ty = (int)blockIdx.x / ntx, tx = (int)blockIdx.x - ty * ntx;
     const int ox0 = tx * RESIZE_TW, oy0 = ty * RESIZE_TH;
@@ -186,10 +212,11 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const resize_a
     if ((pitch << lrc) > RESIZE_STAGE_DW) return;   // (not with n <= 32 m)
     const int rc = 1 << lrc;
 
+    const int x = ROIS ? win[0] : a.x, y = ROIS ? win[1] : a.y;
     const uint8_t *Y = a.in + a.in_off[blockIdx.y];
-    const uint8_t *U = Y + (size_t)width * a.height + (size_t)(a.y >> 1) * cpitch + (a.x >> 1);
+    const uint8_t *U = Y + (size_t)width * a.height + (size_t)(y >> 1) * cpitch + (x >> 1);
     const uint8_t *V = U + (size_t)cpitch * (a.height >> 1);
-    Y += (size_t)a.y * width + a.x;
+    Y += (size_t)y * width + x;
 
     uint32_t acc[NE];
 #pragma unroll
@@ -199,9 +226,9 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const resize_a
         const int nr = ye - r0 < rc ? ye - r0 : rc;         // source rows of this chunk
         // stage: (row pair, 4-column group) items, groups fastest, at most 3 per thread
         const int nit = ((nr + 1) >> 1) * ng;
-        if (nit <= RESIZE_THREADS) resize_stage<MODE, 1, COL>(a, Y, U, V, stage, pitch, ng, nit, xs0, r0, tid);
-        else if (nit <= 2 * RESIZE_THREADS) resize_stage<MODE, 2, COL>(a, Y, U, V, stage, pitch, ng, nit, xs0, r0, tid);
-        else resize_stage<MODE, 3, COL>(a, Y, U, V, stage, pitch, ng, nit, xs0, r0, tid);
+        if (nit <= RESIZE_THREADS) resize_stage<MODE, 1, COL>(a, win, Y, U, V, stage, pitch, ng, nit, xs0, r0, tid);
+        else if (nit <= 2 * RESIZE_THREADS) resize_stage<MODE, 2, COL>(a, win, Y, U, V, stage, pitch, ng, nit, xs0, r0, tid);
+        else resize_stage<MODE, 3, COL>(a, win, Y, U, V, stage, pitch, ng, nit, xs0, r0, tid);
         __syncthreads();
         // horizontal: (source row, output column) items, rows fastest
         for (int it = tid; it < (RESIZE_TW << lrc); it += RESIZE_THREADS) {
@@ -258,22 +285,38 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const resize_a
     }
 }
 
+// the twelve instantiations by (mode, dt, col) with ROIS as given, over NROWS
+// grid rows of the tiles of (OH, OW); A: the kernel's arguments
+#define RESIZE_LAUNCH(ROIS, NROWS, OW, OH, A)                                                           \
+    do {                                                                                                \
+        const unsigned ntx = (unsigned)((OW) + RESIZE_TW - 1) / RESIZE_TW;                              \
+        const unsigned nty = (unsigned)((OH) + RESIZE_TH - 1) / RESIZE_TH;                              \
+        const dim3 grid(ntx * nty, NROWS), block(RESIZE_THREADS);                                       \
+        RESIZE_COL_CASE(ROIS, TENSOR_U8, A) RESIZE_COL_CASE(ROIS, TENSOR_F16, A)                        \
+        RESIZE_COL_CASE(ROIS, TENSOR_BF16, A) RESIZE_COL_CASE(ROIS, TENSOR_F32, A)                      \
+        RESIZE_CASE(ROIS, TENSOR_RGB, TENSOR_U8, A) RESIZE_CASE(ROIS, TENSOR_RGB, TENSOR_F16, A)        \
+        RESIZE_CASE(ROIS, TENSOR_RGB, TENSOR_BF16, A) RESIZE_CASE(ROIS, TENSOR_RGB, TENSOR_F32, A)      \
+        RESIZE_CASE(ROIS, TENSOR_GRAY, TENSOR_U8, A) RESIZE_CASE(ROIS, TENSOR_GRAY, TENSOR_F16, A)      \
+        RESIZE_CASE(ROIS, TENSOR_GRAY, TENSOR_BF16, A) RESIZE_CASE(ROIS, TENSOR_GRAY, TENSOR_F32, A)    \
+    } while (0)
+#define RESIZE_CASE(ROIS, M, D, A) \
+    if (mode == M && dt == D) hipLaunchKernelGGL((k_tensor_resize<M, D, false, ROIS>), grid, block, 0, st, A);
+#define RESIZE_COL_CASE(ROIS, D, A)                                                                     \
+    if (mode == TENSOR_RGB && dt == D && col) {                                                         \
+        hipLaunchKernelGGL((k_tensor_resize<TENSOR_RGB, D, true, ROIS>), grid, block, 0, st, A);        \
+        return;                                                                                         \
+    }
+
 static void resize_launch(int mode, int dt, bool col, int npics, hipStream_t st, const resize_args &a)
 {
-    const unsigned ntx = (unsigned)(a.ow + RESIZE_TW - 1) / RESIZE_TW, nty = (unsigned)(a.oh + RESIZE_TH - 1) / RESIZE_TH;
-    const dim3 grid(ntx * nty, npics), block(RESIZE_THREADS);
-#define RESIZE_CASE(M, D) \
-    if (mode == M && dt == D) hipLaunchKernelGGL((k_tensor_resize<M, D>), grid, block, 0, st, a);
-#define RESIZE_COL_CASE(D)                                                                      \
-    if (mode == TENSOR_RGB && dt == D && col) {                                                 \
-        hipLaunchKernelGGL((k_tensor_resize<TENSOR_RGB, D, true>), grid, block, 0, st, a);      \
-        return;                                                                                 \
-    }
-    RESIZE_COL_CASE(TENSOR_U8) RESIZE_COL_CASE(TENSOR_F16) RESIZE_COL_CASE(TENSOR_BF16) RESIZE_COL_CASE(TENSOR_F32)
-#undef RESIZE_COL_CASE
-    RESIZE_CASE(TENSOR_RGB, TENSOR_U8) RESIZE_CASE(TENSOR_RGB, TENSOR_F16)
-    RESIZE_CASE(TENSOR_RGB, TENSOR_BF16) RESIZE_CASE(TENSOR_RGB, TENSOR_F32)
-    RESIZE_CASE(TENSOR_GRAY, TENSOR_U8) RESIZE_CASE(TENSOR_GRAY, TENSOR_F16)
-    RESIZE_CASE(TENSOR_GRAY, TENSOR_BF16) RESIZE_CASE(TENSOR_GRAY, TENSOR_F32)
-#undef RESIZE_CASE
+    RESIZE_LAUNCH(false, npics, a.ow, a.oh, a);
 }
+
+// nrois <= TENSOR_MAX_PICS boxes: a.win[r] and a.r.t.in_off[r], r < nrois
+static void rois_launch(int mode, int dt, bool col, int nrois, hipStream_t st, const rois_args &a)
+{
+    RESIZE_LAUNCH(true, nrois, a.r.ow, a.r.oh, a);
+}
+#undef RESIZE_LAUNCH
+#undef RESIZE_COL_CASE
+#undef RESIZE_CASE

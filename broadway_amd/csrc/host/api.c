@@ -443,6 +443,48 @@ H264SwDecRet H264SwDecLastPictureAccMotionResized(H264SwDecInst decInst, const h
     return H264SWDEC_PIC_RDY;
 }
 
+/* Boxes of the delivered picture as resized tensors (include/h264mi.h): like
+ * the call above a LastPicture call over one backend member, and it needs no
+ * retention (the frame slot is there until the next decode).  Box coordinates
+ * are the delivered window's: the SPS crop offset is added here, and
+ * H264MI_TENSOR_COLOUR_STREAM resolves from the delivered picture's VUI and the
+ * crop window's size, as the whole-picture tensor's does. */
+H264SwDecRet H264SwDecLastPictureTensorRois(H264SwDecInst decInst, const h264mi_tensor_resize_desc *desc,
+                                            const h264mi_roi *rois, u32 nrois, void *d_dst, void *hip_stream)
+{
+    if (decInst == NULL || desc == NULL || rois == NULL || d_dst == NULL) return H264SWDEC_PARAM_ERR;
+    DecContainer *c = (DecContainer *)decInst;
+    if (!c->dec.be.export_tensor_rois) return H264SWDEC_PARAM_ERR;
+    h264mi_tensor_resize_desc m = *desc;
+    if (nrois < 1 || nrois > 0x7FFFFFFF / sizeof(h264mi_roi) || h264mi_tensor_colour_resolve(m.t.mode, 2, 0, 2, 2) < 0 ||
+        !resize_desc_fixed_ok(&m) || (m.t.x | m.t.y | m.t.cw | m.t.ch) ||
+        !export_aligned(d_dst, 0, export_elem_size(m.t.dtype)))
+        return H264SWDEC_PARAM_ERR;
+    for (u32 k = 0; k < nrois; k++)
+        if (rois[k].pic != 0) return H264SWDEC_PARAM_ERR;
+    const Sps *s = h264dec_active_sps(&c->dec);
+    if (!s || !c->dec.last_out_slot1) return H264SWDEC_OK;      /* no picture delivered */
+    const export_window w = sps_crop_window(s);
+    h264mi_roi *b = (h264mi_roi *)malloc(nrois * sizeof(*b));
+    if (!b) return H264SWDEC_MEMFAIL;
+    int ok = 1;
+    for (u32 k = 0; k < nrois && ok; k++) {
+        b[k] = rois[k];
+        ok = b[k].x >= 0 && b[k].y >= 0 && b[k].cw >= 1 && b[k].ch >= 1 && b[k].cw <= w.cw - b[k].x &&
+             b[k].ch <= w.ch - b[k].y;
+        if (ok) { b[k].x += w.x; b[k].y += w.y; }
+    }
+    ok = ok && rois_ok(&m, b, (int)nrois, 1, 16 * s->w_mbs, 16 * s->h_mbs);
+    const int colour = h264mi_tensor_colour_resolve(m.t.mode, c->dec.last_out_vui_matrix, c->dec.last_out_vui_full, w.cw, w.ch);
+    if (H264MI_TENSOR_LAYOUT(m.t.mode) == H264MI_TENSOR_RGB) m.t.mode = H264MI_TENSOR_MODE(H264MI_TENSOR_RGB, colour, 0);
+    /* (a failure of the export itself: d_dst not on the decoder's GPU) */
+    ok = ok && !c->dec.be.export_tensor_rois(c->dec.be.ctx, c->dec.last_out_slot1 - 1, &m, b, (int)nrois, d_dst, hip_stream);
+    free(b);
+    if (!ok) return H264SWDEC_PARAM_ERR;
+    c->dec.last_tensor_colour1 = colour + 1;
+    return H264SWDEC_PIC_RDY;
+}
+
 H264SwDecRet H264SwDecGetTiming(H264SwDecInst decInst, double *parse_s, double *submit_s, double *wait_s,
                                 double *copy_s, u32 *pictures)
 {

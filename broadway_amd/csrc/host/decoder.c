@@ -715,6 +715,8 @@ static const uint8_t *next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr
     d->out_cropped = crop != NULL || tensor != NULL;
     if (rr < 0) return NULL;
     d->last_out_slot1 = o->slot + 1;
+    d->last_out_vui_matrix = o->vui_matrix;
+    d->last_out_vui_full = o->vui_full;
     if (pic_id) *pic_id = (uint32_t)o->pic_id;
     if (is_idr) *is_idr = (uint32_t)o->is_idr;
     /* rr > 0: the device flagged the reconstruction (a bounded wait that

@@ -73,6 +73,13 @@ typedef struct H264Backend {
      * the resized field of desc (a checked h264mi_accmv_resize_desc), like
      * export_field; NULL when the backend cannot */
     int  (*export_accmv_resized)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
+    /* optional: the nrois boxes rois (h264mi_roi, every pic 0, picture
+     * coordinates) of slot as resized tensors of desc (a checked
+     * h264mi_tensor_resize_desc whose window is zero), box r packed behind
+     * box r - 1 at d_dst, ordered like export_tensor; it needs no retention;
+     * 0 ok, -1 failure; NULL when the backend cannot */
+    int  (*export_tensor_rois)(void *ctx, int slot, const void *desc, const void *rois, int nrois, void *d_dst,
+                               void *hip_stream);
     /* optional: host memory for the output frames (pinned by the HIP
      * backend, so each picture's D2H copy runs at DMA speed); NULL: malloc */
     void *(*host_alloc)(void *ctx, size_t bytes);
@@ -154,6 +161,8 @@ typedef struct H264Dec {
      * kind delivered, plus one (0: none since the last H264SwDecDecode) */
     int      keep[H264_KEEP_KINDS];
     int      last_out_slot1;
+    /* that picture's colour signalling (DpbOut's), for H264SwDecLastPictureTensorRois */
+    int      last_out_vui_matrix, last_out_vui_full;
     /* the colour id of the last tensor delivered (include/h264mi.h), plus one (0: none yet) */
     int      last_tensor_colour1;
     /* statistics */

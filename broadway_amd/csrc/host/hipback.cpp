@@ -633,6 +633,35 @@ static int hb_export_accmv_resized(void *vctx, int slot, const void *desc, void 
     return hb_export(vctx, slot, h264mi_engine_export_accmv_resized, desc, d_dst, hip_stream);
 }
 
+// boxes of slot as resized tensors (a member of its own, with no retention):
+// the list travels through hb_export as one descriptor, box r's elements
+// packed behind box r - 1's
+extern "C" int h264mi_engine_export_tensor_rois(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                                const h264mi_tensor_resize_desc *desc, const h264mi_roi *rois,
+                                                int nrois, void *d_out, size_t out_stride,
+                                                void *hip_stream) __attribute__((weak));
+struct RoisCall {
+    const h264mi_tensor_resize_desc *desc;
+    const h264mi_roi *rois;
+    int nrois;
+};
+
+static int engine_export_rois(h264mi_engine *e, int n, const int *streams, const int *slots, const RoisCall *c,
+                              void *d_out, size_t, void *hip_stream)
+{
+    const size_t planes = H264MI_TENSOR_LAYOUT(c->desc->t.mode) == H264MI_TENSOR_GRAY ? 1 : 3;
+    return h264mi_engine_export_tensor_rois(e, n, streams, slots, c->desc, c->rois, c->nrois, d_out,
+                                            planes * c->desc->oh * c->desc->ow * export_elem_size(c->desc->t.dtype),
+                                            hip_stream);
+}
+
+static int hb_export_tensor_rois(void *vctx, int slot, const void *desc, const void *rois, int nrois, void *d_dst,
+                                 void *hip_stream)
+{
+    const RoisCall c = {(const h264mi_tensor_resize_desc *)desc, (const h264mi_roi *)rois, nrois};
+    return hb_export(vctx, slot, engine_export_rois, &c, d_dst, hip_stream);
+}
+
 // Pinned host blocks (decoder output frames) kept after free for the next
 // decoder instance: pinning tens of MB per instance is a large share of a
 // short stream's host time.  Exact-size reuse, at most H264MI_HOST_POOL_MB
@@ -781,6 +810,7 @@ extern "C" H264Backend h264mi_hip_backend_create(int device)
         be.field[k].export_field = have[k] ? hb_export_field : NULL;
     }
     be.export_accmv_resized = have[H264_KEEP_ACCMV] && h264mi_engine_export_accmv_resized ? hb_export_accmv_resized : NULL;
+    be.export_tensor_rois = h264mi_engine_export_tensor_rois ? hb_export_tensor_rois : NULL;
     be.host_alloc = hb_host_alloc;
     be.host_free = hb_host_free;
     be.records_wait = hb_records_wait;

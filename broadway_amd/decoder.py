@@ -82,6 +82,15 @@ of the wasm glue of Decoder/src/Decoder.c:44-162:
   (``H264SwDecLastPictureAccMotionResized``) and ``decoder.accmv`` is ``(C, oh,
   ow)``.
 
+* ``decoder.rois(boxes, size, ...)`` (an extension for device consumers; needs
+  torch; no option: callable in every output mode, inside ``onPictureDecoded``
+  and until the next ``decode``): boxes ``(x, y, cw, ch)`` of the delivered
+  picture, in the coordinates of the SPS crop window, each resized on the GPU
+  to ``size`` = (oh, ow) -- a new ``(K, planes, oh, ow)`` torch tensor on the
+  decoder's GPU, built by ``H264SwDecLastPictureTensorRois`` on torch's current
+  stream from one kernel launch per 32 boxes; the arguments of the ``tensor``
+  option.
+
 Unlike the reference module (a single global instance) every ``Decoder`` has
 its own H264SwDec instance, so several streams can be decoded side by side.
 Reconstruction always runs on the GPU through libh264mi.so; ``sliceMode``
@@ -130,6 +139,20 @@ _FIELDS = {
                     lambda d, x, y, cw, ch: (ch, cw), "origin maps", "the origin map",
                     "H264SwDecLastPictureAccMotionResized"),
 }
+
+
+def rois_args(boxes, size, width, height, **kw):
+    """``Decoder.rois``'s arguments as (descriptor, ``_lib.Roi`` array, planes,
+    torch dtype): ``boxes`` = [(x, y, cw, ch), ...] on a delivered picture of
+    width x height (0: no headers yet, so only the picture-independent rules
+    are checked here), all of picture 0; ``kw``: the ``tensor`` option's keys.
+    ValueError for anything the library would refuse."""
+    from .engine import rois_desc                # (imports torch)
+    try:
+        boxes = [(0,) + tuple(b) for b in boxes]
+    except TypeError:
+        raise ValueError(f"rois: boxes {boxes!r}: a list of (x, y, cw, ch)") from None
+    return rois_desc(boxes, size, 1, width or _lib.RESIZE_MAX_DIM, height or _lib.RESIZE_MAX_DIM, stream_ok=True, **kw)
 
 
 class Decoder:
@@ -316,6 +339,34 @@ class Decoder:
             infos[0]["finishDecoding"] = _now()
         self.infoAr = []
         self.onPictureDecoded(buf, w, h, infos)
+
+    def rois(self, boxes, size, mode="rgb", dtype=None, mean=None, std=None, scale=None, bias=None, colour=None,
+             unspecified=None):
+        """Boxes of the delivered picture as one new ``(K, planes, oh, ow)``
+        torch tensor on the decoder's GPU, on torch's current stream
+        (``H264SwDecLastPictureTensorRois``): ``boxes`` = [(x, y, cw, ch), ...]
+        in the coordinates of the picture ``onPictureDecoded`` receives with
+        ``crop`` or ``tensor`` (the SPS crop window; the whole picture where
+        the stream has none), every box even, inside it and resized to ``size``
+        = (oh, ow).  Callable inside ``onPictureDecoded`` and until the next
+        ``decode``, in every output mode; needs torch.  The other arguments
+        are those of the ``tensor`` option; ``colour="stream"`` gives every
+        box the set the whole-picture tensor of that picture gets, and
+        ``tensor_colour`` names it.  ValueError for a bad argument,
+        RuntimeError before a picture was delivered."""
+        _, _, cw, ch = self._crop_window()
+        desc, arr, planes, dtype = rois_args(boxes, size, cw, ch, mode=mode, dtype=dtype, mean=mean, std=std, scale=scale,
+                                             bias=bias, colour=colour, unspecified=unspecified)
+        if not hasattr(self, "_device"):
+            self._device = int(os.environ.get("H264MI_DEVICE") or 0)
+        out, st = self._device_empty((len(arr), planes, desc.oh, desc.ow), dtype)
+        last = getattr(self._L, "H264SwDecLastPictureTensorRois", None)
+        ret = last(self._inst, C.byref(desc), arr, len(arr), out.data_ptr(), st) if last else _lib.H264SWDEC_PARAM_ERR
+        if ret == _lib.H264SWDEC_OK:
+            raise RuntimeError("rois: no picture has been delivered since the last decode")
+        if ret != _lib.H264SWDEC_PIC_RDY:
+            raise RuntimeError(f"rois: the backend cannot export the boxes ({ret}; there is no host fallback)")
+        return out
 
     @property
     def tensor_colour(self) -> Optional[str]:

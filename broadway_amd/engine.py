@@ -134,6 +134,59 @@ def tensor_desc(window, mode="rgb", dtype=None, scale=None, bias=None, mean=None
     return d, planes, dtype
 
 
+def snap_rois(boxes, width: int, height: int):
+    """Corner boxes ``(k, x0, y0, x1, y1)`` (floats or ints, as detectors emit
+    them; k indexes a picture list) as the ``(k, x, y, cw, ch)`` boxes of
+    ``Engine.to_tensor(rois=)`` on pictures of width x height: each box is
+    rounded outward to even coordinates and clipped to the picture, and a box
+    that is empty after clipping is dropped.  Returns ``(rois, kept)``, kept[i]
+    being the index in ``boxes`` of rois[i]."""
+    import math
+    width, height = int(width) & ~1, int(height) & ~1
+    rois, kept = [], []
+    for i, (k, x0, y0, x1, y1) in enumerate(boxes):
+        x0, y0 = max(2 * math.floor(x0 / 2), 0), max(2 * math.floor(y0 / 2), 0)
+        x1, y1 = min(2 * math.ceil(x1 / 2), width), min(2 * math.ceil(y1 / 2), height)
+        if x1 > x0 and y1 > y0:
+            rois.append((int(k), x0, y0, x1 - x0, y1 - y0))
+            kept.append(i)
+    return rois, kept
+
+
+def rois_desc(rois, size, npics, width, height, mode="rgb", dtype=None, scale=None, bias=None, mean=None, std=None,
+              colour=None, unspecified=None, stream_ok=False):
+    """(``_lib.TensorResizeDesc`` with a zero window, ``_lib.Roi`` array, planes,
+    torch dtype) of a region-of-interest export (Engine.to_tensor(rois=),
+    Decoder.rois): ``rois`` = [(k, x, y, cw, ch), ...] over ``npics`` pictures
+    of width x height, every box to ``size`` = (oh, ow).  The rules of
+    include/h264mi.h: a non-empty list, k in [0, npics), every box even,
+    inside the picture, at most 16384 a side and 32 source samples per output
+    and axis.  ValueError otherwise."""
+    if size is None:
+        raise ValueError("rois: goes with size=(oh, ow)")
+    desc, planes, dtype = tensor_desc((0, 0, 0, 0), mode, dtype, scale, bias, mean, std, size, colour, unspecified,
+                                      stream_ok)
+    try:
+        given = [tuple(b) for b in rois]
+        boxes = [tuple(int(v) for v in b) for b in given]
+        if any(len(b) != 5 for b in boxes) or boxes != given:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"rois {rois!r}: a list of (k, x, y, cw, ch) integers") from None
+    if not boxes:
+        raise ValueError("rois: an empty list")
+    for k, x, y, cw, ch in boxes:
+        if not 0 <= k < npics:
+            raise ValueError(f"rois: box {(k, x, y, cw, ch)}: picture {k} of {npics}")
+        if (x | y | cw | ch) & 1 or x < 0 or y < 0 or cw < 2 or ch < 2 or cw > width - x or ch > height - y:
+            raise ValueError(f"rois: box {(k, x, y, cw, ch)}: even and inside {width} x {height}")
+        if cw > _lib.RESIZE_MAX_DIM or ch > _lib.RESIZE_MAX_DIM or cw > 32 * desc.ow or ch > 32 * desc.oh:
+            raise ValueError(f"rois: box {(k, x, y, cw, ch)}: at most {_lib.RESIZE_MAX_DIM} a side and 32 times "
+                             f"the size {(desc.oh, desc.ow)} on each axis")
+    arr = (_lib.Roi * len(boxes))(*[_lib.Roi(*b) for b in boxes])
+    return desc, arr, planes, dtype
+
+
 def _field_channels(channels, table, max_ch):
     """The ids of ``channels`` (a name or names of ``table``, 1..max_ch of them)."""
     if isinstance(channels, str):
@@ -491,7 +544,8 @@ class Engine:
         return out
 
     def to_tensor(self, streams: Sequence[int], slots: Sequence[int], window=None, mode: str = "rgb", dtype=None,
-                  scale=None, bias=None, mean=None, std=None, out=None, stream=None, size=None, colour=None):
+                  scale=None, bias=None, mean=None, std=None, out=None, stream=None, size=None, colour=None,
+                  rois=None):
         """The slots (streams[k], slots[k]) as one ``(n, planes, ch, cw)``
         torch tensor on ``cuda:{self.device}``, built on the GPU and never
         copied to the host: planes R, G, B (``mode="rgb"``, the values of
@@ -510,6 +564,17 @@ class Engine:
         read_rgba), "bt601-full", "bt709" or "bt709-full" (DESIGN 3.5f); the
         resize works on the samples of that set.
 
+        ``rois`` = [(k, x, y, cw, ch), ...] (with ``size``, without
+        ``window``): a list of boxes instead of one window, box r the window
+        (x, y, cw, ch) of picture k of the list (streams[k], slots[k]), every
+        one resized to ``size`` -- the result is ``(len(rois), planes, oh,
+        ow)``, box r holding the bytes ``window=(x, y, cw, ch), size=size``
+        gives for that picture, from one kernel launch per 32 boxes and one
+        ordering of the streams for the whole list.  Each box is
+        even, inside the picture and at most 32 times ``size`` on each axis
+        (``snap_rois`` makes such boxes from a detector's corners); a bad box,
+        an empty list or a k out of range is a ValueError.
+
         The export is ordered on ``stream`` (a torch.cuda.Stream; default:
         torch's current stream of the device): it starts after the work queued
         there and after every launch queued on the engine, later work on
@@ -519,6 +584,18 @@ class Engine:
         new ``torch.empty``.  The result is an ordinary torch tensor, so DLPack
         consumers (``torch.utils.dlpack`` / ``__dlpack__``) need nothing further."""
         n, c_streams, c_slots = self._pictures(streams, slots)
+        if rois is not None:
+            if window is not None:
+                raise ValueError("rois: not combinable with window (each box is one)")
+            desc, boxes, planes, dtype = rois_desc(rois, size, n, self.w_mbs * 16, self.h_mbs * 16, mode, dtype, scale,
+                                                   bias, mean, std, colour)
+            out, st = self._out((len(boxes), planes, desc.oh, desc.ow), dtype, out, stream)
+            if not hasattr(self._L, "h264mi_engine_export_tensor_rois") or \
+                    self._L.h264mi_engine_export_tensor_rois(self._h, n, c_streams, c_slots, C.byref(desc), boxes,
+                                                             len(boxes), out.data_ptr(),
+                                                             planes * desc.oh * desc.ow * out.element_size(), st) != 0:
+                raise RuntimeError("h264mi_engine_export_tensor_rois failed (stream or slot out of range?)")
+            return out
         if window is None:
             window = (0, 0, self.w_mbs * 16, self.h_mbs * 16)
         desc, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std, size, colour)

@@ -216,6 +216,31 @@ H264SwDecRet H264SwDecNextPictureTensorResized(H264SwDecInst decInst, H264SwDecP
  * picture is taken from the DPB.  The colour id, 0..3, of the last tensor
  * either call delivered (GRAY: 0); -1 before the first one. */
 int H264SwDecLastTensorColour(H264SwDecInst decInst);
+/* Regions of interest (resize.hip): a list of boxes, each a
+ * window (x, y, cw, ch) of picture `pic` of a call's picture list, every one
+ * resized to the same (oh, ow) as the resized tensor above: box r is the
+ * resized tensor of its window, (3 | 1, oh, ow) elements.  The descriptor's
+ * own window (t.x, t.y, t.cw, t.ch) is reserved: all zero.  Each box follows
+ * the resized tensor's window rules (even, inside the picture, at most 16384 a
+ * side and 32 source samples per output and axis; upscaling allowed); one bad
+ * box refuses the whole list.  H264MI_ROIS_MAX_PER_LAUNCH boxes go into one
+ * kernel launch; a longer list takes several. */
+#define H264MI_ROIS_MAX_PER_LAUNCH 32
+typedef struct { int pic, x, y, cw, ch; } h264mi_roi;
+/* Boxes of the picture the last H264SwDecNextPicture* call of any kind
+ * delivered, valid until the next H264SwDecDecode; the DPB is not touched.
+ * Every pic is 0; box coordinates are in the delivered (SPS crop) window --
+ * the call adds the crop offset -- and a box lies inside it.  Box r's
+ * (planes, oh, ow) elements at d_dst + r * planes * oh * ow elements, ordered
+ * on `hip_stream` like H264SwDecNextPictureTensor.  Colour ids 0..3 are taken
+ * as they are; H264MI_TENSOR_COLOUR_STREAM resolves from the delivered
+ * picture's own VUI, by size from the crop window's size (every box gets the
+ * colour the whole-picture tensor gets); H264SwDecLastTensorColour reports it.
+ * H264SWDEC_PARAM_ERR for anything the export can refuse (checked before
+ * anything is queued) and when the backend cannot export; H264SWDEC_OK when no
+ * picture has been delivered; H264SWDEC_PIC_RDY on success. */
+H264SwDecRet H264SwDecLastPictureTensorRois(H264SwDecInst decInst, const h264mi_tensor_resize_desc *desc,
+                                            const h264mi_roi *rois, u32 nrois, void *d_dst, void *hip_stream);
 /* Motion vectors and MB side information as a device tensor (mbinfo.hip, DESIGN
  * 3.5d; elsewhere: ffmpeg's export_mvs).  The field lives on the luma 4x4-block
  * grid of the MB-aligned picture, BW = 4 * w_mbs columns by BH = 4 * h_mbs
@@ -665,6 +690,22 @@ int  h264mi_tensor_resize_device_pitch(const void *d_in, const size_t *in_offset
 int  h264mi_engine_export_tensor_resized(h264mi_engine *e, int n, const int *streams, const int *slots,
                                          const h264mi_tensor_resize_desc *desc, void *d_out, size_t out_stride,
                                          void *hip_stream);
+/* the resized export over a list of regions of interest (h264mi_roi above):
+ * box r, the window rois[r].(x, y, cw, ch) of picture rois[r].pic of the
+ * picture list (in_offsets, or streams / slots), resized to desc->(oh, ow):
+ * its (planes, oh, ow) elements at d_out + r * out_stride, nothing else
+ * written.  The bytes of box r are those h264mi_tensor_resize_device_pitch
+ * gives for the same window and size.  desc->t's window is reserved (all zero);
+ * `rois` is a host array, read before the call returns.  One kernel launch per
+ * H264MI_ROIS_MAX_PER_LAUNCH boxes, and for the engine call one ordering of the
+ * two streams however many boxes there are.  -1, nothing launched, when any
+ * box or anything else is bad, d_out in no device's memory included. */
+int  h264mi_tensor_rois_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width, int height,
+                                     int cpitch, const h264mi_tensor_resize_desc *desc, const h264mi_roi *rois,
+                                     int nrois, void *d_out, size_t out_stride, void *hip_stream);
+int  h264mi_engine_export_tensor_rois(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                      const h264mi_tensor_resize_desc *desc, const h264mi_roi *rois, int nrois,
+                                      void *d_out, size_t out_stride, void *hip_stream);
 /* the MB side-information field (h264mi_mbinfo_desc above) of npics record
  * batches of w_mbs * h_mbs MbRec each, batch k starting rec_offsets[k] bytes (a
  * host array of multiples of 96; any order, repeats allowed) after d_recs
