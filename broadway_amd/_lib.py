@@ -94,6 +94,11 @@ class Roi(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("pic", "x", "y", "cw", "ch")]
 
 
+class TensorFitDesc(C.Structure):
+    """h264mi_tensor_fit_desc (include/h264mi.h)."""
+    _fields_ = [("r", TensorResizeDesc), ("fit", C.c_int), ("pad", C.c_ubyte * 4)]
+
+
 class MbInfoDesc(C.Structure):
     """h264mi_mbinfo_desc (include/h264mi.h)."""
     _fields_ = [(n, C.c_int) for n in ("bx", "by", "bw", "bh", "nch", "dtype")] + \
@@ -157,6 +162,7 @@ TENSOR_COLOUR_SHIFT, TENSOR_UNSPEC_SHIFT = 8, 12
 RESIZE_TRIANGLE = 0
 RESIZE_MAX_DIM = 16384
 ROIS_MAX_PER_LAUNCH = 32
+TENSOR_FIT = {"stretch": 0, "letterbox": 1, "topleft": 2}
 TENSOR_U8, TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 0, 1, 2, 3
 
 HEADERS_CB = C.CFUNCTYPE(None, C.c_void_p)
@@ -296,6 +302,22 @@ def mi() -> C.CDLL:
         L.h264mi_engine_export_tensor_rois.restype = i32
         L.H264SwDecLastPictureTensorRois.argtypes = [vp, rd, ro, u32, vp, vp]
         L.H264SwDecLastPictureTensorRois.restype = i32
+    if hasattr(L, "h264mi_tensor_fit_device_pitch"):        # (optional, as above)
+        fd, ro = C.POINTER(TensorFitDesc), C.POINTER(Roi)
+        L.h264mi_letterbox_fit.argtypes = [i32, i32, i32, i32, i32, C.POINTER(i32)]
+        L.h264mi_letterbox_fit.restype = i32
+        L.h264mi_tensor_fit_device_pitch.argtypes = [vp, C.POINTER(sz), i32, i32, i32, i32, fd, vp, sz, vp]
+        L.h264mi_tensor_fit_device_pitch.restype = i32
+        L.h264mi_tensor_rois_fit_device_pitch.argtypes = [vp, C.POINTER(sz), i32, i32, i32, i32, fd, ro, i32, vp, sz, vp]
+        L.h264mi_tensor_rois_fit_device_pitch.restype = i32
+        L.h264mi_engine_export_tensor_fit.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), fd, vp, sz, vp]
+        L.h264mi_engine_export_tensor_fit.restype = i32
+        L.h264mi_engine_export_tensor_rois_fit.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), fd, ro, i32, vp, sz, vp]
+        L.h264mi_engine_export_tensor_rois_fit.restype = i32
+        L.H264SwDecNextPictureTensorFit.argtypes = [vp, C.POINTER(H264SwDecPicture), u32, fd, vp, vp]
+        L.H264SwDecNextPictureTensorFit.restype = i32
+        L.H264SwDecLastPictureTensorRoisFit.argtypes = [vp, fd, ro, u32, vp, vp]
+        L.H264SwDecLastPictureTensorRoisFit.restype = i32
     if hasattr(L, "h264mi_mbinfo_device"):                  # (optional, as above)
         md = C.POINTER(MbInfoDesc)
         L.h264mi_mbinfo_device.argtypes = [vp, C.POINTER(sz), i32, i32, i32, md, vp, sz, vp]

@@ -97,6 +97,65 @@ static inline int rois_ok(const h264mi_tensor_resize_desc *d, const h264mi_roi *
     return 1;
 }
 
+/* The fit of a cw x ch window into an ow x oh canvas (include/h264mi.h, DESIGN
+ * 3.5l), all four at least 1: out = (rw, rh, px, py), the content's size and
+ * its place in the canvas.  The major axis fills the canvas; the minor axis
+ * is the nearest integer to the exact size (halves up), but at least
+ * ceil(n / 32) -- 47 rows at exactly 32 : 1 would round to 1 row, 47 source
+ * samples for one output -- and at least 1.  Stated here once: the exports,
+ * the H264SwDec calls and h264mi_letterbox_fit all come through it. */
+static inline int letterbox_minor(int64_t n_minor, int64_t n_major, int64_t m_major)
+{
+    const int64_t m = (2 * n_minor * m_major + n_major) / (2 * n_major), least = (n_minor + 31) / 32;
+    return (int)(m > least ? (m > 1 ? m : 1) : (least > 1 ? least : 1));
+}
+
+static inline void letterbox_fit(int cw, int ch, int ow, int oh, int fit, int out[4])
+{
+    int rw = ow, rh = oh;
+    if (fit != H264MI_FIT_STRETCH) {
+        if ((int64_t)cw * oh >= (int64_t)ch * ow) rh = letterbox_minor(ch, cw, ow);
+        else rw = letterbox_minor(cw, ch, oh);
+    }
+    out[0] = rw; out[1] = rh;
+    out[2] = fit == H264MI_FIT_LETTERBOX ? (ow - rw) / 2 : 0;
+    out[3] = fit == H264MI_FIT_LETTERBOX ? (oh - rh) / 2 : 0;
+}
+
+/* h264mi_tensor_fit_desc: the resize descriptor's rules with the window judged
+ * against its content size, a known fit, and the reserved pad byte zero */
+static inline int fit_desc_fixed_ok(const h264mi_tensor_fit_desc *d)
+{
+    return resize_desc_fixed_ok(&d->r) && d->fit >= H264MI_FIT_STRETCH && d->fit <= H264MI_FIT_LETTERBOX_TOPLEFT &&
+           d->pad[3] == 0;
+}
+
+/* (after fit_desc_fixed_ok) place, not NULL: the window's (rw, rh, px, py) */
+static inline int fit_window_ok(const h264mi_tensor_fit_desc *d, int width, int height, int place[4])
+{
+    const h264mi_tensor_desc *t = &d->r.t;
+    int f[4];
+    if (!tensor_window_ok(t, width, height) || t->cw > H264MI_RESIZE_MAX_DIM || t->ch > H264MI_RESIZE_MAX_DIM) return 0;
+    letterbox_fit(t->cw, t->ch, d->r.ow, d->r.oh, d->fit, f);
+    if (place) { place[0] = f[0]; place[1] = f[1]; place[2] = f[2]; place[3] = f[3]; }
+    /* (a content larger than the canvas: only behind a major axis beyond 32 : 1) */
+    return f[0] <= d->r.ow && f[1] <= d->r.oh && t->cw <= 32 * f[0] && t->ch <= 32 * f[1];
+}
+
+/* rois_ok for a fit descriptor: every box is a window fit_window_ok accepts
+ * with its own fit into d's canvas.  All or nothing. */
+static inline int rois_fit_ok(const h264mi_tensor_fit_desc *d, const h264mi_roi *r, int nrois, int npics, int width,
+                              int height)
+{
+    if (nrois < 1 || !fit_desc_fixed_ok(d) || (d->r.t.x | d->r.t.y | d->r.t.cw | d->r.t.ch)) return 0;
+    for (int k = 0; k < nrois; k++) {
+        h264mi_tensor_fit_desc b = *d;
+        b.r.t.x = r[k].x; b.r.t.y = r[k].y; b.r.t.cw = r[k].cw; b.r.t.ch = r[k].ch;
+        if (r[k].pic < 0 || r[k].pic >= npics || !fit_window_ok(&b, width, height, NULL)) return 0;
+    }
+    return 1;
+}
+
 /* h264mi_mbinfo_desc: the window is in 4x4 blocks of a w_mbs x h_mbs picture */
 static inline int mbinfo_desc_fixed_ok(const h264mi_mbinfo_desc *d)
 {

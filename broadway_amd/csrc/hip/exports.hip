@@ -422,19 +422,21 @@ static bool rois_desc_ok(const h264mi_tensor_resize_desc *d, const h264mi_roi *r
     return d && rois && tensor_mode_ok(d->t.mode) && rois_ok(d, rois, nrois, npics, width, height);
 }
 
-extern "C" int h264mi_tensor_rois_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width,
-                                               int height, int cpitch, const h264mi_tensor_resize_desc *desc,
-                                               const h264mi_roi *rois, int nrois, void *d_out, size_t out_stride,
-                                               void *stream)
+// The launches of the list exports, behind their checks (the descriptor's and
+// the pictures').  fit != NULL (desc = &fit->r): every box fitted into the canvas (oh, ow) by
+// letterbox_fit, the rest of the canvas fit->pad; whole != NULL:
+// the list is `whole` of every picture (the single-window form) and rois is unused
+static int rois_device(const void *d_in, const size_t *in_offsets, int npics, int width, int height, int cpitch,
+                       const h264mi_tensor_resize_desc *desc, const h264mi_tensor_fit_desc *fit,
+                       const h264mi_tensor_desc *whole, const h264mi_roi *rois, int nrois, void *d_out,
+                       size_t out_stride, void *stream)
 {
-    if (!d_in || !in_offsets || !d_out || width <= 0 || height <= 0 || ((width | height) & 1) || npics < 1 ||
-        cpitch < width / 2 || !rois_desc_ok(desc, rois, nrois, npics, width, height))
-        return -1;
     const h264mi_tensor_desc *t = &desc->t;
     // (d_out is checked here too: a list is one lookup, and a host address would fault every launch of it)
     if (!export_aligned(d_out, out_stride, export_elem_size(t->dtype)) || h264mi_pointer_device(d_out) < 0) return -1;
     const int layout = H264MI_TENSOR_LAYOUT(t->mode), colour = H264MI_TENSOR_COLOUR(t->mode);
-    rois_args ra;
+    fit_args fa;
+    rois_args &ra = fa;
     tensor_args &a = ra.r.t;
     a.in = (const uint8_t *)d_in;
     a.width = width; a.height = height; a.cpitch = cpitch;
@@ -443,15 +445,95 @@ extern "C" int h264mi_tensor_rois_device_pitch(const void *d_in, const size_t *i
     for (int p = 0; p < 3; p++) { a.scale[p] = t->scale[p]; a.bias[p] = t->bias[p]; }
     a.col = tensor_colour_sets[colour];
     ra.r.ow = desc->ow; ra.r.oh = desc->oh;
+    if (fit)
+        for (int p = 0; p < 3; p++) fa.pad[p] = fit->pad[p];
     std::vector<size_t> off((size_t)nrois);
-    for (int r = 0; r < nrois; r++) off[r] = in_offsets[rois[r].pic];
+    for (int r = 0; r < nrois; r++) off[r] = in_offsets[whole ? r : rois[r].pic];
     return export_launches(nrois, off.data(), a.in_off, &a.out, d_out, out_stride, [&](int r0, int n) {
         for (int r = 0; r < EXPORT_MAX_PICS; r++) {
-            const h264mi_roi &b = rois[r0 + (r < n ? r : 0)];
+            const h264mi_roi w = {0, t->x, t->y, t->cw, t->ch};
+            const h264mi_roi &b = whole ? w : rois[r0 + (r < n ? r : 0)];
             ra.win[r][0] = b.x; ra.win[r][1] = b.y; ra.win[r][2] = b.cw; ra.win[r][3] = b.ch;
+            if (fit) {
+                int f[4];
+                letterbox_fit(b.cw, b.ch, desc->ow, desc->oh, fit->fit, f);
+                fa.place[r][0] = f[2]; fa.place[r][1] = f[3]; fa.place[r][2] = f[0]; fa.place[r][3] = f[1];
+            }
         }
-        rois_launch(layout, t->dtype, colour != 0, n, (hipStream_t)stream, ra);
+        if (fit) fit_launch(layout, t->dtype, colour != 0, n, (hipStream_t)stream, fa);
+        else rois_launch(layout, t->dtype, colour != 0, n, (hipStream_t)stream, ra);
     });
+}
+
+// what every stateless tensor export asks of its pictures
+static bool tensor_pics_ok(const void *d_in, const size_t *in_offsets, int npics, int width, int height, int cpitch,
+                           const void *d_out)
+{
+    return d_in && in_offsets && d_out && width > 0 && height > 0 && !((width | height) & 1) && npics >= 1 &&
+           cpitch >= width / 2;
+}
+
+extern "C" int h264mi_tensor_rois_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width,
+                                               int height, int cpitch, const h264mi_tensor_resize_desc *desc,
+                                               const h264mi_roi *rois, int nrois, void *d_out, size_t out_stride,
+                                               void *stream)
+{
+    if (!tensor_pics_ok(d_in, in_offsets, npics, width, height, cpitch, d_out) ||
+        !rois_desc_ok(desc, rois, nrois, npics, width, height))
+        return -1;
+    return rois_device(d_in, in_offsets, npics, width, height, cpitch, desc, NULL, NULL, rois, nrois, d_out, out_stride,
+                       stream);
+}
+
+// The letterboxed exports (include/h264mi.h): picture k's window
+// desc->r.t, or box r of a list as above, scaled with its aspect ratio kept
+// into the canvas desc->r.oh x desc->r.ow -- the content (rw, rh) at (px, py)
+// from letterbox_fit, resolved here per row and handed to the kernel --, the
+// rest of the canvas the element of desc->pad.  Both are the table form of the
+// kernel: the single-window call's table has one row per picture.  -1 (nothing
+// launched) on a bad argument.
+extern "C" int h264mi_letterbox_fit(int cw, int ch, int ow, int oh, int fit, int out[4])
+{
+    if (!out || cw < 1 || ch < 1 || ow < 1 || oh < 1 || cw > H264MI_RESIZE_MAX_DIM || ch > H264MI_RESIZE_MAX_DIM ||
+        ow > H264MI_RESIZE_MAX_DIM || oh > H264MI_RESIZE_MAX_DIM || fit < H264MI_FIT_STRETCH ||
+        fit > H264MI_FIT_LETTERBOX_TOPLEFT)
+        return -1;
+    letterbox_fit(cw, ch, ow, oh, fit, out);
+    return 0;
+}
+
+// a fit descriptor h264mi_tensor_fit_device_pitch accepts
+static bool fit_desc_ok(const h264mi_tensor_fit_desc *d, int width, int height)
+{
+    return d && tensor_mode_ok(d->r.t.mode) && fit_desc_fixed_ok(d) && fit_window_ok(d, width, height, NULL);
+}
+
+static bool rois_fit_desc_ok(const h264mi_tensor_fit_desc *d, const h264mi_roi *rois, int nrois, int npics, int width,
+                             int height)
+{
+    return d && rois && tensor_mode_ok(d->r.t.mode) && rois_fit_ok(d, rois, nrois, npics, width, height);
+}
+
+extern "C" int h264mi_tensor_fit_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width,
+                                              int height, int cpitch, const h264mi_tensor_fit_desc *desc, void *d_out,
+                                              size_t out_stride, void *stream)
+{
+    if (!tensor_pics_ok(d_in, in_offsets, npics, width, height, cpitch, d_out) || !fit_desc_ok(desc, width, height))
+        return -1;
+    return rois_device(d_in, in_offsets, npics, width, height, cpitch, &desc->r, desc, &desc->r.t, NULL, npics, d_out,
+                       out_stride, stream);
+}
+
+extern "C" int h264mi_tensor_rois_fit_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width,
+                                                   int height, int cpitch, const h264mi_tensor_fit_desc *desc,
+                                                   const h264mi_roi *rois, int nrois, void *d_out, size_t out_stride,
+                                                   void *stream)
+{
+    if (!tensor_pics_ok(d_in, in_offsets, npics, width, height, cpitch, d_out) ||
+        !rois_fit_desc_ok(desc, rois, nrois, npics, width, height))
+        return -1;
+    return rois_device(d_in, in_offsets, npics, width, height, cpitch, &desc->r, desc, NULL, rois, nrois, d_out,
+                       out_stride, stream);
 }
 
 // An export of the slots (streams[k], slots[k]), k < n, into the caller's
@@ -524,6 +606,41 @@ extern "C" int h264mi_engine_export_tensor_rois(h264mi_engine *e, int n, const i
         return h264mi_tensor_rois_device_pitch(e->d_frames, off.data(), n, width, height, e->cpitch, desc, rois, nrois,
                                                d_out, out_stride, e->st);
     });
+}
+
+// the frame slots, or boxes over them, letterboxed (h264mi_tensor_fit_device_pitch,
+// h264mi_tensor_rois_fit_device_pitch; rois == NULL: desc's window of every slot)
+static int engine_export_fit(h264mi_engine *e, int n, const int *streams, const int *slots,
+                             const h264mi_tensor_fit_desc *desc, const h264mi_roi *rois, int nrois, void *d_out,
+                             size_t out_stride, void *stream)
+{
+    if (!e || n < 1 || !streams || !slots || !d_out) return -1;
+    const int width = e->w * 16, height = e->h * 16;
+    if (rois ? !rois_fit_desc_ok(desc, rois, nrois, n, width, height) : !fit_desc_ok(desc, width, height)) return -1;
+    return export_ordered(e, n, streams, slots, d_out, out_stride, export_elem_size(desc->r.t.dtype), stream, [&] {
+        std::vector<size_t> off((size_t)n);
+        for (int k = 0; k < n; k++) off[k] = e->frame_bytes * ((size_t)streams[k] * e->nslots + slots[k]);
+        if (!rois)
+            return h264mi_tensor_fit_device_pitch(e->d_frames, off.data(), n, width, height, e->cpitch, desc, d_out,
+                                                  out_stride, e->st);
+        return h264mi_tensor_rois_fit_device_pitch(e->d_frames, off.data(), n, width, height, e->cpitch, desc, rois,
+                                                   nrois, d_out, out_stride, e->st);
+    });
+}
+
+extern "C" int h264mi_engine_export_tensor_fit(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                               const h264mi_tensor_fit_desc *desc, void *d_out, size_t out_stride,
+                                               void *stream)
+{
+    return engine_export_fit(e, n, streams, slots, desc, NULL, 0, d_out, out_stride, stream);
+}
+
+extern "C" int h264mi_engine_export_tensor_rois_fit(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                                    const h264mi_tensor_fit_desc *desc, const h264mi_roi *rois,
+                                                    int nrois, void *d_out, size_t out_stride, void *stream)
+{
+    if (!rois) return -1;
+    return engine_export_fit(e, n, streams, slots, desc, rois, nrois, d_out, out_stride, stream);
 }
 
 // Motion vectors and MB side information as planar fields (mbinfo.hip): the

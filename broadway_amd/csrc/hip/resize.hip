@@ -37,6 +37,13 @@
 // Regions of interest: with the kernel's ROIS flag a grid row is
 // a box -- the window is the row's own, from a table in the kernel arguments,
 // and box r is the resized tensor of its window.  Everything above is per row.
+//
+// Letterboxing: with the FIT flag (on top of ROIS) the grid's
+// tiles are those of a canvas, and the row's resized tensor, rw x rh outputs,
+// lies at (px, py) of it -- the placement comes with the row, from the host's
+// letterbox_fit.  A tile resizes its part of the content (the axes' outputs are
+// the content's: j = canvas column - px over m = rw) and stores the pad element
+// in the rest; a tile with no content stores pad elements and is done.
 
 #pragma once
 #include <hip/hip_runtime.h>
@@ -62,6 +69,13 @@ struct resize_args {
 struct rois_args {
     resize_args r;
     int win[TENSOR_MAX_PICS][4];
+};
+
+// and fitted into a canvas: r.ow x r.oh is the canvas, row r's
+// content place[r] = (px, py, rw, rh) inside it, pad[p] plane p's sample outside
+struct fit_args : rois_args {
+    int place[TENSOR_MAX_PICS][4];
+    uint32_t pad[3];
 };
 
 // the taps of output j of an axis n -> m: q[k * qpitch], k < count, for source
@@ -155,9 +169,20 @@ __device__ __forceinline__ void resize_stage(const tensor_args &a, const int *wi
     }
 }
 
-// the arguments of k_tensor_resize<.., ROIS>, and their resize_args
-template <bool ROIS> struct resize_kernel_args { typedef resize_args type; };
-template <> struct resize_kernel_args<true> { typedef rois_args type; };
+// the bits v of an element as element o of the output at O: one non-temporal store
+template <int DT>
+__device__ __forceinline__ void resize_store(uint8_t *O, size_t o, uint32_t v)
+{
+    constexpr int ES = tensor_elem_size(DT);
+    if (ES == 1) __builtin_nontemporal_store((uint8_t)v, O + o);
+    else if (ES == 2) __builtin_nontemporal_store((uint16_t)v, (uint16_t *)O + o);
+    else __builtin_nontemporal_store(v, (uint32_t *)O + o);
+}
+
+// the arguments of k_tensor_resize<.., ROIS, FIT>, and their resize_args
+template <bool ROIS, bool FIT> struct resize_kernel_args { typedef resize_args type; };
+template <> struct resize_kernel_args<true, false> { typedef rois_args type; };
+template <> struct resize_kernel_args<true, true> { typedef fit_args type; };
 __device__ __forceinline__ const resize_args &resize_part(const resize_args &a) { return a; }
 __device__ __forceinline__ const resize_args &resize_part(const rois_args &a) { return a.r; }
 
@@ -167,10 +192,14 @@ __device__ __forceinline__ const resize_args &resize_part(const rois_args &a) { 
 // window is the row's own, ka.win[blockIdx.y] = (x, y, cw, ch), read from the
 // kernel arguments like ra.t's (uniform over the workgroup either way); the
 // tile's position depends on (oh, ow) only, so the rows share the grid's x extent.
-template <int MODE, int DT, bool COL = false, bool ROIS = false>
-__global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename resize_kernel_args<ROIS>::type ka)
+// FIT (with ROIS): (oh, ow) is a canvas, and the row's outputs are the rw x rh
+// at (px, py) of it, ka.place[blockIdx.y] = (px, py, rw, rh); a tile holds the
+// content's columns [jx0, jx1) and rows [iy0, iy1) of its own (without FIT: all
+// of the tile), the rest of it is ka.pad.
+template <int MODE, int DT, bool COL = false, bool ROIS = false, bool FIT = false>
+__global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename resize_kernel_args<ROIS, FIT>::type ka)
 {
-    constexpr int ES = tensor_elem_size(DT);
+    static_assert(ROIS || !FIT, "the placement is a per-row table, like the window");
     constexpr int NP = MODE == TENSOR_RGB ? 3 : 1;
     constexpr int NE = NP * RESIZE_TW * RESIZE_TH / RESIZE_THREADS;     // outputs per thread
     static_assert(RESIZE_TW == 32 && RESIZE_TH * RESIZE_TW == 2 * RESIZE_THREADS, "item -> (plane, row, column) below");
@@ -189,14 +218,37 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
     const int ty = (int)blockIdx.x / ntx, tx = (int)blockIdx.x - ty * ntx;
     const int ox0 = tx * RESIZE_TW, oy0 = ty * RESIZE_TH;
     const int nx = ow - ox0 < RESIZE_TW ? ow - ox0 : RESIZE_TW, ny = oh - oy0 < RESIZE_TH ? oh - oy0 : RESIZE_TH;
+    // the axes' outputs: the content's (FIT) or the tile's grid's
+    int px0 = 0, py0 = 0, rw = ow, rh = oh, jx0 = 0, jx1 = nx, iy0 = 0, iy1 = ny;
+    if constexpr (FIT) {
+        const int *pl = ka.place[blockIdx.y];
+        px0 = pl[0]; py0 = pl[1]; rw = pl[2]; rh = pl[3];
+        jx0 = px0 > ox0 ? px0 - ox0 : 0;
+        jx1 = px0 + rw - ox0 < nx ? px0 + rw - ox0 : nx;
+        iy0 = py0 > oy0 ? py0 - oy0 : 0;
+        iy1 = py0 + rh - oy0 < ny ? py0 + rh - oy0 : ny;
+        if (jx0 >= jx1 || iy0 >= iy1) {             // all bar (uniform over the workgroup)
+            uint8_t *O = a.out + blockIdx.y * a.out_stride;
+#pragma unroll
+            for (int e = 0; e < NE; e++) {
+                const int p = e >> 1, i = (tid >> 5) + 8 * (e & 1), j = tid & 31;
+                if (i >= ny || j >= nx) continue;
+                const uint32_t v = tensor_elem<DT>(ka.pad[p], a.scale[p], a.bias[p]);
+                const size_t o = ((size_t)p * oh + (size_t)(oy0 + i)) * ow + (size_t)(ox0 + j);
+                resize_store<DT>(O, o, v);
+            }
+            return;
+        }
+    }
 
     if (tid < RESIZE_TW + RESIZE_TH) {
         const bool isx = tid < RESIZE_TW;
         const int l = isx ? tid : tid - RESIZE_TW;
         int f = 0, c = 0;
-        if (l < (isx ? nx : ny))
-            resize_taps((uint32_t)(isx ? cw : ch), (uint32_t)(isx ? ow : oh), (uint32_t)((isx ? ox0 : oy0) + l),
-                        (isx ? qx : qy) + l, isx ? RESIZE_TW : RESIZE_TH, f, c);
+        if (l >= (isx ? jx0 : iy0) && l < (isx ? jx1 : iy1))
+            resize_taps((uint32_t)(isx ? cw : ch), (uint32_t)(isx ? rw : rh),
+                        (uint32_t)((isx ? ox0 - px0 : oy0 - py0) + l), (isx ? qx : qy) + l,
+                        isx ? RESIZE_TW : RESIZE_TH, f, c);
         (isx ? fx : fy)[l] = f;
         (isx ? cx : cy)[l] = c;
     }
@@ -205,8 +257,8 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
     // the tile's source columns [xs0, xs0 + segw) (4-column groups of the
     // window) and rows [ys0, ye) (row pairs): first taps and tap ends grow with
     // the output index
-    const int xs0 = fx[0] & ~3, segw = (fx[nx - 1] + cx[nx - 1] - xs0 + 3) & ~3, pitch = segw | 1, ng = segw >> 2;
-    const int ys0 = fy[0] & ~1, ye = fy[ny - 1] + cy[ny - 1];
+    const int xs0 = fx[jx0] & ~3, segw = (fx[jx1 - 1] + cx[jx1 - 1] - xs0 + 3) & ~3, pitch = segw | 1, ng = segw >> 2;
+    const int ys0 = fy[iy0] & ~1, ye = fy[iy1 - 1] + cy[iy1 - 1];
     int lrc = 4;                                    // log2 of the chunk's rows
     while (lrc > 1 && (pitch << lrc) > RESIZE_STAGE_DW) lrc--;
     if ((pitch << lrc) > RESIZE_STAGE_DW) return;   // (not with n <= 32 m)
@@ -233,7 +285,7 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
         // horizontal: (source row, output column) items, rows fastest
         for (int it = tid; it < (RESIZE_TW << lrc); it += RESIZE_THREADS) {
             const int r = it & (rc - 1), j = it >> lrc;
-            if (r >= nr || j >= nx) continue;
+            if (r >= nr || j < jx0 || j >= jx1) continue;
             const uint32_t *s = stage + r * pitch + (fx[j] - xs0);
             const int n = cx[j];
             uint32_t h[NP];
@@ -262,7 +314,7 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
 #pragma unroll
         for (int e = 0; e < NE; e++) {
             const int p = e >> 1, i = (tid >> 5) + 8 * (e & 1), j = tid & 31;
-            if (i >= ny || j >= nx) continue;
+            if (i < iy0 || i >= iy1 || j < jx0 || j >= jx1) continue;
             const int f = fy[i];
             const int lo = f > r0 ? f : r0, hi = f + cy[i] < r0 + nr ? f + cy[i] : r0 + nr;
             const uint16_t *t = tb + (p * RESIZE_TW + j) * RESIZE_TPITCH;
@@ -277,45 +329,52 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
     for (int e = 0; e < NE; e++) {
         const int p = e >> 1, i = (tid >> 5) + 8 * (e & 1), j = tid & 31;
         if (i >= ny || j >= nx) continue;
-        const uint32_t v = tensor_elem<DT>((acc[e] + (1u << 19)) >> 20, a.scale[p], a.bias[p]);
+        uint32_t c = (acc[e] + (1u << 19)) >> 20;
+        if constexpr (FIT)
+            if (i < iy0 || i >= iy1 || j < jx0 || j >= jx1) c = ka.pad[p];
+        const uint32_t v = tensor_elem<DT>(c, a.scale[p], a.bias[p]);
         const size_t o = ((size_t)p * oh + (size_t)(oy0 + i)) * ow + (size_t)(ox0 + j);
-        if (ES == 1) __builtin_nontemporal_store((uint8_t)v, O + o);
-        else if (ES == 2) __builtin_nontemporal_store((uint16_t)v, (uint16_t *)O + o);
-        else __builtin_nontemporal_store(v, (uint32_t *)O + o);
+        resize_store<DT>(O, o, v);
     }
 }
 
-// the twelve instantiations by (mode, dt, col) with ROIS as given, over NROWS
+// the twelve instantiations by (mode, dt, col) with ROIS and FIT as given, over NROWS
 // grid rows of the tiles of (OH, OW); A: the kernel's arguments
-#define RESIZE_LAUNCH(ROIS, NROWS, OW, OH, A)                                                           \
-    do {                                                                                                \
-        const unsigned ntx = (unsigned)((OW) + RESIZE_TW - 1) / RESIZE_TW;                              \
-        const unsigned nty = (unsigned)((OH) + RESIZE_TH - 1) / RESIZE_TH;                              \
-        const dim3 grid(ntx * nty, NROWS), block(RESIZE_THREADS);                                       \
-        RESIZE_COL_CASE(ROIS, TENSOR_U8, A) RESIZE_COL_CASE(ROIS, TENSOR_F16, A)                        \
-        RESIZE_COL_CASE(ROIS, TENSOR_BF16, A) RESIZE_COL_CASE(ROIS, TENSOR_F32, A)                      \
-        RESIZE_CASE(ROIS, TENSOR_RGB, TENSOR_U8, A) RESIZE_CASE(ROIS, TENSOR_RGB, TENSOR_F16, A)        \
-        RESIZE_CASE(ROIS, TENSOR_RGB, TENSOR_BF16, A) RESIZE_CASE(ROIS, TENSOR_RGB, TENSOR_F32, A)      \
-        RESIZE_CASE(ROIS, TENSOR_GRAY, TENSOR_U8, A) RESIZE_CASE(ROIS, TENSOR_GRAY, TENSOR_F16, A)      \
-        RESIZE_CASE(ROIS, TENSOR_GRAY, TENSOR_BF16, A) RESIZE_CASE(ROIS, TENSOR_GRAY, TENSOR_F32, A)    \
+#define RESIZE_LAUNCH(ROIS, FIT, NROWS, OW, OH, A)                                                                  \
+    do {                                                                                                            \
+        const unsigned ntx = (unsigned)((OW) + RESIZE_TW - 1) / RESIZE_TW;                                          \
+        const unsigned nty = (unsigned)((OH) + RESIZE_TH - 1) / RESIZE_TH;                                          \
+        const dim3 grid(ntx * nty, NROWS), block(RESIZE_THREADS);                                                   \
+        RESIZE_COL_CASE(ROIS, FIT, TENSOR_U8, A) RESIZE_COL_CASE(ROIS, FIT, TENSOR_F16, A)                          \
+        RESIZE_COL_CASE(ROIS, FIT, TENSOR_BF16, A) RESIZE_COL_CASE(ROIS, FIT, TENSOR_F32, A)                        \
+        RESIZE_CASE(ROIS, FIT, TENSOR_RGB, TENSOR_U8, A) RESIZE_CASE(ROIS, FIT, TENSOR_RGB, TENSOR_F16, A)          \
+        RESIZE_CASE(ROIS, FIT, TENSOR_RGB, TENSOR_BF16, A) RESIZE_CASE(ROIS, FIT, TENSOR_RGB, TENSOR_F32, A)        \
+        RESIZE_CASE(ROIS, FIT, TENSOR_GRAY, TENSOR_U8, A) RESIZE_CASE(ROIS, FIT, TENSOR_GRAY, TENSOR_F16, A)        \
+        RESIZE_CASE(ROIS, FIT, TENSOR_GRAY, TENSOR_BF16, A) RESIZE_CASE(ROIS, FIT, TENSOR_GRAY, TENSOR_F32, A)      \
     } while (0)
-#define RESIZE_CASE(ROIS, M, D, A) \
-    if (mode == M && dt == D) hipLaunchKernelGGL((k_tensor_resize<M, D, false, ROIS>), grid, block, 0, st, A);
-#define RESIZE_COL_CASE(ROIS, D, A)                                                                     \
-    if (mode == TENSOR_RGB && dt == D && col) {                                                         \
-        hipLaunchKernelGGL((k_tensor_resize<TENSOR_RGB, D, true, ROIS>), grid, block, 0, st, A);        \
-        return;                                                                                         \
+#define RESIZE_CASE(ROIS, FIT, M, D, A)                                                                             \
+    if (mode == M && dt == D) hipLaunchKernelGGL((k_tensor_resize<M, D, false, ROIS, FIT>), grid, block, 0, st, A);
+#define RESIZE_COL_CASE(ROIS, FIT, D, A)                                                                            \
+    if (mode == TENSOR_RGB && dt == D && col) {                                                                     \
+        hipLaunchKernelGGL((k_tensor_resize<TENSOR_RGB, D, true, ROIS, FIT>), grid, block, 0, st, A);               \
+        return;                                                                                                     \
     }
 
 static void resize_launch(int mode, int dt, bool col, int npics, hipStream_t st, const resize_args &a)
 {
-    RESIZE_LAUNCH(false, npics, a.ow, a.oh, a);
+    RESIZE_LAUNCH(false, false, npics, a.ow, a.oh, a);
 }
 
 // nrois <= TENSOR_MAX_PICS boxes: a.win[r] and a.r.t.in_off[r], r < nrois
 static void rois_launch(int mode, int dt, bool col, int nrois, hipStream_t st, const rois_args &a)
 {
-    RESIZE_LAUNCH(true, nrois, a.r.ow, a.r.oh, a);
+    RESIZE_LAUNCH(true, false, nrois, a.r.ow, a.r.oh, a);
+}
+
+// the same, row r fitted into the canvas (a.r.oh, a.r.ow) at a.place[r]
+static void fit_launch(int mode, int dt, bool col, int nrois, hipStream_t st, const fit_args &a)
+{
+    RESIZE_LAUNCH(true, true, nrois, a.r.ow, a.r.oh, a);
 }
 #undef RESIZE_LAUNCH
 #undef RESIZE_COL_CASE

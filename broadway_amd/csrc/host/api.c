@@ -254,23 +254,27 @@ H264SwDecRet H264SwDecNextPictureCropped(H264SwDecInst decInst, H264SwDecPicture
     return H264SWDEC_PIC_RDY;
 }
 
-/* H264SwDecNextPictureTensor (desc: an h264mi_tensor_desc) and, resized,
- * ...TensorResized (an h264mi_tensor_resize_desc); a window with cw == 0 is the
- * active SPS's crop window.  Everything the export can refuse is checked
+/* H264SwDecNextPictureTensor (desc: an h264mi_tensor_desc), resized == 1
+ * ...TensorResized (an h264mi_tensor_resize_desc) and resized == 2 ...TensorFit
+ * (an h264mi_tensor_fit_desc); a window with cw == 0 is the active SPS's crop
+ * window.  Everything the export can refuse is checked
  * before a picture is taken from the DPB. */
 static H264SwDecRet next_picture_tensor(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
                                         const void *desc, int resized, void *d_dst, void *hip_stream)
 {
     if (decInst == NULL || pOutput == NULL || d_dst == NULL || desc == NULL) return H264SWDEC_PARAM_ERR;
     DecContainer *c = (DecContainer *)decInst;
-    if (!(resized ? c->dec.be.export_tensor_resized : c->dec.be.export_tensor)) return H264SWDEC_PARAM_ERR;
-    h264mi_tensor_resize_desc r;
-    memset(&r, 0, sizeof(r));
-    if (resized) r = *(const h264mi_tensor_resize_desc *)desc;
-    else r.t = *(const h264mi_tensor_desc *)desc;
-    h264mi_tensor_desc *t = &r.t;
+    if (!(resized == 2 ? c->dec.be.export_tensor_fit : resized ? c->dec.be.export_tensor_resized : c->dec.be.export_tensor))
+        return H264SWDEC_PARAM_ERR;
+    h264mi_tensor_fit_desc f;
+    memset(&f, 0, sizeof(f));
+    if (resized == 2) f = *(const h264mi_tensor_fit_desc *)desc;
+    else if (resized) f.r = *(const h264mi_tensor_resize_desc *)desc;
+    else f.r.t = *(const h264mi_tensor_desc *)desc;
+    h264mi_tensor_resize_desc *r = &f.r;
+    h264mi_tensor_desc *t = &r->t;
     if (h264mi_tensor_colour_resolve(t->mode, 2, 0, 2, 2) < 0 ||
-        !(resized ? resize_desc_fixed_ok(&r) : tensor_desc_fixed_ok(t)) ||
+        !(resized == 2 ? fit_desc_fixed_ok(&f) : resized ? resize_desc_fixed_ok(r) : tensor_desc_fixed_ok(t)) ||
         !export_aligned(d_dst, 0, export_elem_size(t->dtype)))
         return H264SWDEC_PARAM_ERR;
     if (flushBuffer) h264dec_flush(&c->dec);
@@ -281,11 +285,13 @@ static H264SwDecRet next_picture_tensor(H264SwDecInst decInst, H264SwDecPicture 
         t->x = w.x; t->y = w.y; t->cw = w.cw; t->ch = w.ch;
     }
     const int width = 16 * s->w_mbs, height = 16 * s->h_mbs;
-    if (!(resized ? resize_window_ok(&r, width, height) : tensor_window_ok(t, width, height))) return H264SWDEC_PARAM_ERR;
+    if (!(resized == 2 ? fit_window_ok(&f, width, height, NULL)
+          : resized    ? resize_window_ok(r, width, height) : tensor_window_ok(t, width, height)))
+        return H264SWDEC_PARAM_ERR;
     uint32_t id, idr, em;
     int failed = 0;
-    /* (a resize descriptor starts with its h264mi_tensor_desc) */
-    const uint8_t *pic = h264dec_next_output_tensor(&c->dec, &id, &idr, &em, &r, resized, d_dst, hip_stream, &failed);
+    /* (a fit descriptor starts with its resize descriptor, and that with its h264mi_tensor_desc) */
+    const uint8_t *pic = h264dec_next_output_tensor(&c->dec, &id, &idr, &em, &f, resized, d_dst, hip_stream, &failed);
     if (failed) return H264SWDEC_PARAM_ERR;         /* (d_dst not on the decoder's GPU) */
     if (!pic) return H264SWDEC_OK;
     pOutput->pOutputPicture = (u32 *)(void *)pic;
@@ -317,7 +323,14 @@ H264SwDecRet H264SwDecNextPictureTensorResized(H264SwDecInst decInst, H264SwDecP
     return next_picture_tensor(decInst, pOutput, flushBuffer, desc, 1, d_dst, hip_stream);
 }
 
-/* the colour id of the last tensor either call above delivered; -1: none yet */
+/* NextPictureTensorResized letterboxed (include/h264mi.h) */
+H264SwDecRet H264SwDecNextPictureTensorFit(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
+                                           const h264mi_tensor_fit_desc *desc, void *d_dst, void *hip_stream)
+{
+    return next_picture_tensor(decInst, pOutput, flushBuffer, desc, 2, d_dst, hip_stream);
+}
+
+/* the colour id of the last tensor a call above delivered; -1: none yet */
 int H264SwDecLastTensorColour(H264SwDecInst decInst)
 {
     if (decInst == NULL) return -1;
@@ -448,17 +461,24 @@ H264SwDecRet H264SwDecLastPictureAccMotionResized(H264SwDecInst decInst, const h
  * retention (the frame slot is there until the next decode).  Box coordinates
  * are the delivered window's: the SPS crop offset is added here, and
  * H264MI_TENSOR_COLOUR_STREAM resolves from the delivered picture's VUI and the
- * crop window's size, as the whole-picture tensor's does. */
-H264SwDecRet H264SwDecLastPictureTensorRois(H264SwDecInst decInst, const h264mi_tensor_resize_desc *desc,
-                                            const h264mi_roi *rois, u32 nrois, void *d_dst, void *hip_stream)
+ * crop window's size, as the whole-picture tensor's does.  fit != NULL (desc
+ * = &fit->r): every box letterboxed into the canvas. */
+static H264SwDecRet last_picture_rois(H264SwDecInst decInst, const h264mi_tensor_resize_desc *desc,
+                                      const h264mi_tensor_fit_desc *fit, const h264mi_roi *rois, u32 nrois, void *d_dst,
+                                      void *hip_stream)
 {
     if (decInst == NULL || desc == NULL || rois == NULL || d_dst == NULL) return H264SWDEC_PARAM_ERR;
     DecContainer *c = (DecContainer *)decInst;
-    if (!c->dec.be.export_tensor_rois) return H264SWDEC_PARAM_ERR;
-    h264mi_tensor_resize_desc m = *desc;
-    if (nrois < 1 || nrois > 0x7FFFFFFF / sizeof(h264mi_roi) || h264mi_tensor_colour_resolve(m.t.mode, 2, 0, 2, 2) < 0 ||
-        !resize_desc_fixed_ok(&m) || (m.t.x | m.t.y | m.t.cw | m.t.ch) ||
-        !export_aligned(d_dst, 0, export_elem_size(m.t.dtype)))
+    if (!(fit ? c->dec.be.export_tensor_rois_fit : c->dec.be.export_tensor_rois)) return H264SWDEC_PARAM_ERR;
+    /* (without fit: desc stretched, which has rois_ok's rules) */
+    h264mi_tensor_fit_desc mf;
+    memset(&mf, 0, sizeof(mf));
+    if (fit) mf = *fit;
+    else mf.r = *desc;
+    h264mi_tensor_resize_desc *m = &mf.r;
+    if (nrois < 1 || nrois > 0x7FFFFFFF / sizeof(h264mi_roi) || h264mi_tensor_colour_resolve(m->t.mode, 2, 0, 2, 2) < 0 ||
+        !fit_desc_fixed_ok(&mf) || (m->t.x | m->t.y | m->t.cw | m->t.ch) ||
+        !export_aligned(d_dst, 0, export_elem_size(m->t.dtype)))
         return H264SWDEC_PARAM_ERR;
     for (u32 k = 0; k < nrois; k++)
         if (rois[k].pic != 0) return H264SWDEC_PARAM_ERR;
@@ -474,15 +494,31 @@ H264SwDecRet H264SwDecLastPictureTensorRois(H264SwDecInst decInst, const h264mi_
              b[k].ch <= w.ch - b[k].y;
         if (ok) { b[k].x += w.x; b[k].y += w.y; }
     }
-    ok = ok && rois_ok(&m, b, (int)nrois, 1, 16 * s->w_mbs, 16 * s->h_mbs);
-    const int colour = h264mi_tensor_colour_resolve(m.t.mode, c->dec.last_out_vui_matrix, c->dec.last_out_vui_full, w.cw, w.ch);
-    if (H264MI_TENSOR_LAYOUT(m.t.mode) == H264MI_TENSOR_RGB) m.t.mode = H264MI_TENSOR_MODE(H264MI_TENSOR_RGB, colour, 0);
+    ok = ok && rois_fit_ok(&mf, b, (int)nrois, 1, 16 * s->w_mbs, 16 * s->h_mbs);
+    const int colour = h264mi_tensor_colour_resolve(m->t.mode, c->dec.last_out_vui_matrix, c->dec.last_out_vui_full, w.cw, w.ch);
+    if (H264MI_TENSOR_LAYOUT(m->t.mode) == H264MI_TENSOR_RGB) m->t.mode = H264MI_TENSOR_MODE(H264MI_TENSOR_RGB, colour, 0);
     /* (a failure of the export itself: d_dst not on the decoder's GPU) */
-    ok = ok && !c->dec.be.export_tensor_rois(c->dec.be.ctx, c->dec.last_out_slot1 - 1, &m, b, (int)nrois, d_dst, hip_stream);
+    ok = ok && !(fit ? c->dec.be.export_tensor_rois_fit(c->dec.be.ctx, c->dec.last_out_slot1 - 1, &mf, b, (int)nrois, d_dst,
+                                                        hip_stream)
+                     : c->dec.be.export_tensor_rois(c->dec.be.ctx, c->dec.last_out_slot1 - 1, m, b, (int)nrois, d_dst,
+                                                    hip_stream));
     free(b);
     if (!ok) return H264SWDEC_PARAM_ERR;
     c->dec.last_tensor_colour1 = colour + 1;
     return H264SWDEC_PIC_RDY;
+}
+
+H264SwDecRet H264SwDecLastPictureTensorRois(H264SwDecInst decInst, const h264mi_tensor_resize_desc *desc,
+                                            const h264mi_roi *rois, u32 nrois, void *d_dst, void *hip_stream)
+{
+    return last_picture_rois(decInst, desc, NULL, rois, nrois, d_dst, hip_stream);
+}
+
+/* the same, every box letterboxed into the canvas (include/h264mi.h) */
+H264SwDecRet H264SwDecLastPictureTensorRoisFit(H264SwDecInst decInst, const h264mi_tensor_fit_desc *desc,
+                                               const h264mi_roi *rois, u32 nrois, void *d_dst, void *hip_stream)
+{
+    return last_picture_rois(decInst, desc ? &desc->r : NULL, desc, rois, nrois, d_dst, hip_stream);
 }
 
 H264SwDecRet H264SwDecGetTiming(H264SwDecInst decInst, double *parse_s, double *submit_s, double *wait_s,

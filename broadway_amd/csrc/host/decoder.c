@@ -657,8 +657,8 @@ const uint8_t *h264dec_next_output_crop(H264Dec *d, uint32_t *pic_id, uint32_t *
 const uint8_t *h264dec_next_output_tensor(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
                                           const void *desc, int resized, void *d_dst, void *hip_stream, int *failed)
 {
-    TensorOut t = {desc, d_dst, hip_stream, 0, resized != 0};
-    /* (a resize descriptor starts with its h264mi_tensor_desc) */
+    TensorOut t = {desc, d_dst, hip_stream, 0, resized};
+    /* (a resize or fit descriptor starts with its h264mi_tensor_desc) */
     const int mode_ok = desc && h264mi_tensor_colour_resolve(((const h264mi_tensor_desc *)desc)->mode, 2, 0, 2, 2) >= 0;
     const uint8_t *r = d_dst && mode_ok ? next_output(d, pic_id, is_idr, err_mbs, NULL, NULL, 0, &t) : NULL;
     if (failed) *failed = t.failed;
@@ -672,7 +672,9 @@ static const uint8_t *next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr
                                   uint8_t *crop, int crop_rgba, TensorOut *tensor)
 {
     if (rgba && !d->be.read_rgba) return NULL;
-    if (tensor && !(tensor->resized ? d->be.export_tensor_resized : d->be.export_tensor)) return NULL;
+    if (tensor && !(tensor->resized == 2 ? d->be.export_tensor_fit
+                    : tensor->resized ? d->be.export_tensor_resized : d->be.export_tensor))
+        return NULL;
     const Sps *sps = crop ? h264dec_active_sps(d) : NULL;
     if (crop && (!d->be.read_crop || !sps)) return NULL;
     const DpbOut *o = dpb_next_output(&d->dpb);
@@ -693,14 +695,18 @@ static const uint8_t *next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr
     int rr;
     if (tensor) {
         /* the backend gets the colour id of this picture's own SPS in place of STREAM */
-        h264mi_tensor_resize_desc r;
-        memset(&r, 0, sizeof(r));
-        if (tensor->resized) r = *(const h264mi_tensor_resize_desc *)tensor->desc;
-        else r.t = *(const h264mi_tensor_desc *)tensor->desc;
-        const int colour = h264mi_tensor_colour_resolve(r.t.mode, o->vui_matrix, o->vui_full, r.t.cw, r.t.ch);
-        if (H264MI_TENSOR_LAYOUT(r.t.mode) == H264MI_TENSOR_RGB) r.t.mode = H264MI_TENSOR_MODE(H264MI_TENSOR_RGB, colour, 0);
-        rr = tensor->resized ? d->be.export_tensor_resized(d->be.ctx, o->slot, &r, tensor->d_dst, tensor->hip_stream)
-                             : d->be.export_tensor(d->be.ctx, o->slot, &r.t, tensor->d_dst, tensor->hip_stream);
+        h264mi_tensor_fit_desc f;
+        memset(&f, 0, sizeof(f));
+        if (tensor->resized == 2) f = *(const h264mi_tensor_fit_desc *)tensor->desc;
+        else if (tensor->resized) f.r = *(const h264mi_tensor_resize_desc *)tensor->desc;
+        else f.r.t = *(const h264mi_tensor_desc *)tensor->desc;
+        h264mi_tensor_desc *t = &f.r.t;
+        /* (by size: the export window's, never a canvas's) */
+        const int colour = h264mi_tensor_colour_resolve(t->mode, o->vui_matrix, o->vui_full, t->cw, t->ch);
+        if (H264MI_TENSOR_LAYOUT(t->mode) == H264MI_TENSOR_RGB) t->mode = H264MI_TENSOR_MODE(H264MI_TENSOR_RGB, colour, 0);
+        rr = tensor->resized == 2 ? d->be.export_tensor_fit(d->be.ctx, o->slot, &f, tensor->d_dst, tensor->hip_stream)
+             : tensor->resized    ? d->be.export_tensor_resized(d->be.ctx, o->slot, &f.r, tensor->d_dst, tensor->hip_stream)
+                                  : d->be.export_tensor(d->be.ctx, o->slot, t, tensor->d_dst, tensor->hip_stream);
         tensor->failed = rr < 0;
         if (rr >= 0) d->last_tensor_colour1 = colour + 1;
     } else if (crop) {

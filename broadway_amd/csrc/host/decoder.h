@@ -80,6 +80,12 @@ typedef struct H264Backend {
      * 0 ok, -1 failure; NULL when the backend cannot */
     int  (*export_tensor_rois)(void *ctx, int slot, const void *desc, const void *rois, int nrois, void *d_dst,
                                void *hip_stream);
+    /* optional: export_tensor_resized and export_tensor_rois letterboxed (desc:
+     * a checked h264mi_tensor_fit_desc; the list form's window is zero); NULL
+     * when the backend cannot */
+    int  (*export_tensor_fit)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
+    int  (*export_tensor_rois_fit)(void *ctx, int slot, const void *desc, const void *rois, int nrois, void *d_dst,
+                                   void *hip_stream);
     /* optional: host memory for the output frames (pinned by the HIP
      * backend, so each picture's D2H copy runs at DMA speed); NULL: malloc */
     void *(*host_alloc)(void *ctx, size_t bytes);
@@ -201,8 +207,9 @@ const uint8_t *h264dec_next_output_rgba(H264Dec *d, uint32_t *pic_id, uint32_t *
 const uint8_t *h264dec_next_output_crop(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
                                         uint8_t *dst, int rgba);
 /* the same, the picture exported by the backend's export_tensor (desc: an
- * h264mi_tensor_desc) or, with resized != 0, export_tensor_resized (an
- * h264mi_tensor_resize_desc); returns d_dst, a device pointer; *failed = 1
+ * h264mi_tensor_desc), with resized == 1 export_tensor_resized (an
+ * h264mi_tensor_resize_desc) or with resized == 2 export_tensor_fit (an
+ * h264mi_tensor_fit_desc); returns d_dst, a device pointer; *failed = 1
  * when the export of the picture taken from the DPB failed */
 const uint8_t *h264dec_next_output_tensor(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
                                           const void *desc, int resized, void *d_dst, void *hip_stream, int *failed);

@@ -662,6 +662,42 @@ static int hb_export_tensor_rois(void *vctx, int slot, const void *desc, const v
     return hb_export(vctx, slot, engine_export_rois, &c, d_dst, hip_stream);
 }
 
+// the two letterboxed exports (members of their own, like the ones above)
+extern "C" int h264mi_engine_export_tensor_fit(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                               const h264mi_tensor_fit_desc *desc, void *d_out, size_t out_stride,
+                                               void *hip_stream) __attribute__((weak));
+extern "C" int h264mi_engine_export_tensor_rois_fit(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                                    const h264mi_tensor_fit_desc *desc, const h264mi_roi *rois,
+                                                    int nrois, void *d_out, size_t out_stride,
+                                                    void *hip_stream) __attribute__((weak));
+struct RoisFitCall {
+    const h264mi_tensor_fit_desc *desc;
+    const h264mi_roi *rois;
+    int nrois;
+};
+
+static int hb_export_tensor_fit(void *vctx, int slot, const void *desc, void *d_dst, void *hip_stream)
+{
+    if (hb_export(vctx, slot, h264mi_engine_export_tensor_fit, desc, d_dst, hip_stream)) return -1;
+    return slot_flagged((HipBackendCtx *)vctx, slot, false);
+}
+
+static int engine_export_rois_fit(h264mi_engine *e, int n, const int *streams, const int *slots, const RoisFitCall *c,
+                                  void *d_out, size_t, void *hip_stream)
+{
+    const h264mi_tensor_resize_desc &r = c->desc->r;
+    const size_t planes = H264MI_TENSOR_LAYOUT(r.t.mode) == H264MI_TENSOR_GRAY ? 1 : 3;
+    return h264mi_engine_export_tensor_rois_fit(e, n, streams, slots, c->desc, c->rois, c->nrois, d_out,
+                                                planes * r.oh * r.ow * export_elem_size(r.t.dtype), hip_stream);
+}
+
+static int hb_export_tensor_rois_fit(void *vctx, int slot, const void *desc, const void *rois, int nrois, void *d_dst,
+                                     void *hip_stream)
+{
+    const RoisFitCall c = {(const h264mi_tensor_fit_desc *)desc, (const h264mi_roi *)rois, nrois};
+    return hb_export(vctx, slot, engine_export_rois_fit, &c, d_dst, hip_stream);
+}
+
 // Pinned host blocks (decoder output frames) kept after free for the next
 // decoder instance: pinning tens of MB per instance is a large share of a
 // short stream's host time.  Exact-size reuse, at most H264MI_HOST_POOL_MB
@@ -811,6 +847,8 @@ extern "C" H264Backend h264mi_hip_backend_create(int device)
     }
     be.export_accmv_resized = have[H264_KEEP_ACCMV] && h264mi_engine_export_accmv_resized ? hb_export_accmv_resized : NULL;
     be.export_tensor_rois = h264mi_engine_export_tensor_rois ? hb_export_tensor_rois : NULL;
+    be.export_tensor_fit = h264mi_engine_export_tensor_fit ? hb_export_tensor_fit : NULL;
+    be.export_tensor_rois_fit = h264mi_engine_export_tensor_rois_fit ? hb_export_tensor_rois_fit : NULL;
     be.host_alloc = hb_host_alloc;
     be.host_free = hb_host_free;
     be.records_wait = hb_records_wait;

@@ -36,7 +36,10 @@ of the wasm glue of Decoder/src/Decoder.c:44-162:
   SPS crop window, built by ``H264SwDecNextPictureTensor`` on torch's current
   stream -- the arguments of ``Engine.to_tensor`` (default: RGB, float16,
   scale 1/255).  With ``size`` the crop window is resized on the GPU
-  (``H264SwDecNextPictureTensorResized``): the tensor is ``(planes, oh, ow)``
+  (``H264SwDecNextPictureTensorResized``; with ``"fit": "letterbox" |
+  "topleft" | "stretch"`` and ``"pad": 114 | (r, g, b)`` it is fitted into
+  the canvas ``size`` with its aspect ratio kept and the rest padded,
+  ``H264SwDecNextPictureTensorFit``): the tensor is ``(planes, oh, ow)``
   and the callback's width and height are ``ow`` and ``oh``.  It combines with
   neither ``rgb`` nor ``crop`` (ValueError).  ``colour`` picks the colour set
   of the R, G, B samples: "reference" (the default: BT.601 limited range, the
@@ -163,17 +166,26 @@ class Decoder:
         self._rgb = bool(self.options.get("rgb"))
         self._crop = bool(self.options.get("crop"))
         self._tensor = self.options.get("tensor") or None
-        self._resized = False
+        self._resized = self._fitted = False
         if self._tensor is not None:
             if self._rgb or self._crop:
                 raise ValueError("tensor: not combinable with rgb or crop (mode='rgb' and the SPS window are part of it)")
             opts = {} if self._tensor is True else dict(self._tensor)
-            unknown = set(opts) - {"dtype", "mode", "mean", "std", "scale", "bias", "size", "colour", "unspecified"}
+            unknown = set(opts) - {"dtype", "mode", "mean", "std", "scale", "bias", "size", "colour", "unspecified",
+                                   "fit", "pad"}
             if unknown:
                 raise ValueError(f"tensor: unknown keys {sorted(unknown)}")
-            from .engine import tensor_desc          # (imports torch)
+            from .engine import fit_desc, tensor_desc       # (imports torch)
+            fit, pad = opts.pop("fit", None), opts.pop("pad", None)
             self._tensor = tensor_desc(None, stream_ok=True, **opts)
             self._resized = opts.get("size") is not None
+            self._fitted = fit is not None or pad is not None
+            if self._fitted:
+                if not self._resized:
+                    raise ValueError("tensor: fit and pad go with size=(oh, ow), the canvas")
+                desc, planes, dtype = self._tensor
+                self._tensor = (fit_desc(desc, planes, "letterbox" if fit is None else fit, 114 if pad is None else pad),
+                                planes, dtype)
             self._device = int(os.environ.get("H264MI_DEVICE") or 0)     # the GPU H264SwDecInit takes (api.c)
         self._fields = {}           # option -> (descriptor, channels or planes, torch dtype) of the fields asked for
         for name, f in _FIELDS.items():
@@ -248,8 +260,10 @@ class Decoder:
                     desc, planes, dtype = self._tensor
                     w, h = self._out_size()
                     out, st = self._device_empty((planes, h, w), dtype)
-                    nxt = L.H264SwDecNextPictureTensorResized if self._resized else L.H264SwDecNextPictureTensor
-                    ret = nxt(self._inst, C.byref(self._pic), 0, C.byref(desc), out.data_ptr(), st)
+                    nxt = getattr(L, "H264SwDecNextPictureTensorFit" if self._fitted else
+                                  "H264SwDecNextPictureTensorResized" if self._resized else "H264SwDecNextPictureTensor", None)
+                    ret = nxt(self._inst, C.byref(self._pic), 0, C.byref(desc), out.data_ptr(), st) if nxt else \
+                        _lib.H264SWDEC_PARAM_ERR
                     if ret == _lib.H264SWDEC_PARAM_ERR:
                         raise RuntimeError("tensor: the backend cannot export device tensors "
                                            "(there is no host fallback)")
@@ -289,7 +303,8 @@ class Decoder:
         """(width, height) of the pictures handed to onPictureDecoded."""
         i = self._info
         if self._tensor is not None and self._resized:
-            return self._tensor[0].ow, self._tensor[0].oh
+            r = self._tensor[0].r if self._fitted else self._tensor[0]
+            return r.ow, r.oh
         if (self._crop or self._tensor is not None) and i.croppingFlag:
             return i.cropParams.cropOutWidth, i.cropParams.cropOutHeight
         return i.picWidth, i.picHeight
@@ -341,7 +356,7 @@ class Decoder:
         self.onPictureDecoded(buf, w, h, infos)
 
     def rois(self, boxes, size, mode="rgb", dtype=None, mean=None, std=None, scale=None, bias=None, colour=None,
-             unspecified=None):
+             unspecified=None, fit=None, pad=None):
         """Boxes of the delivered picture as one new ``(K, planes, oh, ow)``
         torch tensor on the decoder's GPU, on torch's current stream
         (``H264SwDecLastPictureTensorRois``): ``boxes`` = [(x, y, cw, ch), ...]
@@ -352,15 +367,20 @@ class Decoder:
         ``decode``, in every output mode; needs torch.  The other arguments
         are those of the ``tensor`` option; ``colour="stream"`` gives every
         box the set the whole-picture tensor of that picture gets, and
-        ``tensor_colour`` names it.  ValueError for a bad argument,
+        ``tensor_colour`` names it.  With ``fit`` ("letterbox", "topleft" or
+        "stretch") and ``pad`` every box is fitted into ``size`` with its
+        aspect ratio kept (``H264SwDecLastPictureTensorRoisFit``), as for
+        ``Engine.to_tensor``.  ValueError for a bad argument,
         RuntimeError before a picture was delivered."""
         _, _, cw, ch = self._crop_window()
         desc, arr, planes, dtype = rois_args(boxes, size, cw, ch, mode=mode, dtype=dtype, mean=mean, std=std, scale=scale,
-                                             bias=bias, colour=colour, unspecified=unspecified)
+                                             bias=bias, colour=colour, unspecified=unspecified, fit=fit, pad=pad)
         if not hasattr(self, "_device"):
             self._device = int(os.environ.get("H264MI_DEVICE") or 0)
-        out, st = self._device_empty((len(arr), planes, desc.oh, desc.ow), dtype)
-        last = getattr(self._L, "H264SwDecLastPictureTensorRois", None)
+        fitted = fit is not None or pad is not None
+        r = desc.r if fitted else desc
+        out, st = self._device_empty((len(arr), planes, r.oh, r.ow), dtype)
+        last = getattr(self._L, "H264SwDecLastPictureTensorRoisFit" if fitted else "H264SwDecLastPictureTensorRois", None)
         ret = last(self._inst, C.byref(desc), arr, len(arr), out.data_ptr(), st) if last else _lib.H264SWDEC_PARAM_ERR
         if ret == _lib.H264SWDEC_OK:
             raise RuntimeError("rois: no picture has been delivered since the last decode")

@@ -134,6 +134,70 @@ def tensor_desc(window, mode="rgb", dtype=None, scale=None, bias=None, mean=None
     return d, planes, dtype
 
 
+def letterbox_fit(cw: int, ch: int, size, fit: str = "letterbox"):
+    """``(rw, rh, px, py)``: the content size and position of a cw x ch window
+    fitted into the canvas ``size`` = (oh, ow) with its aspect ratio kept --
+    ``h264mi_letterbox_fit``'s arithmetic (include/h264mi.h) in Python
+    integers.  The major axis fills the canvas, the minor axis is the nearest
+    integer (halves up) but at least ceil(n / 32) and 1; "letterbox" centres
+    the content (floored), "topleft" puts it at (0, 0), "stretch" is (ow, oh,
+    0, 0)."""
+    oh, ow = _resize_size(size)
+    if fit not in _lib.TENSOR_FIT:
+        raise ValueError(f"fit {fit!r}: one of {sorted(_lib.TENSOR_FIT)}")
+    try:
+        given, (cw, ch) = (cw, ch), (int(cw), int(ch))
+        if (cw, ch) != given or not (1 <= cw <= _lib.RESIZE_MAX_DIM and 1 <= ch <= _lib.RESIZE_MAX_DIM):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"window size {(cw, ch)!r}: integers 1..{_lib.RESIZE_MAX_DIM}") from None
+    rw, rh = ow, oh
+    if fit != "stretch":
+        if cw * oh >= ch * ow:
+            rh = max((2 * ch * ow + cw) // (2 * cw), (ch + 31) // 32, 1)
+        else:
+            rw = max((2 * cw * oh + ch) // (2 * ch), (cw + 31) // 32, 1)
+    if fit == "letterbox":
+        return rw, rh, (ow - rw) // 2, (oh - rh) // 2
+    return rw, rh, 0, 0
+
+
+def unletterbox(boxes, window, size, fit: str = "letterbox"):
+    """A detector's corner boxes ``(k, x0, y0, x1, y1)`` (floats) in the
+    coordinates of a canvas ``size`` = (oh, ow) that holds ``window`` = (x, y,
+    cw, ch) fitted by ``fit``, back in picture coordinates: minus the content's
+    position, times cw / rw and ch / rh, plus the window's origin.  The result
+    is in ``snap_rois``' format (it clips, so a box that reaches into the bars
+    needs nothing more)."""
+    x, y, cw, ch = window
+    rw, rh, px, py = letterbox_fit(cw, ch, size, fit)
+    sx, sy = cw / rw, ch / rh
+    return [(k, x + (x0 - px) * sx, y + (y0 - py) * sy, x + (x1 - px) * sx, y + (y1 - py) * sy)
+            for k, x0, y0, x1, y1 in boxes]
+
+
+def fit_desc(desc, planes, fit="letterbox", pad=114):
+    """The ``_lib.TensorFitDesc`` of the resize descriptor ``desc`` letterboxed
+    (Engine.to_tensor(fit=), the Decoder's ``tensor`` option, Decoder.rois):
+    ``fit`` "letterbox", "topleft" or "stretch"; ``pad`` one uint8 sample for
+    every plane or one per plane, in the tensor's own domain (R, G, B or
+    luma).  ValueError for anything else."""
+    if fit not in _lib.TENSOR_FIT:
+        raise ValueError(f"fit {fit!r}: one of {sorted(_lib.TENSOR_FIT)}")
+    try:
+        given = tuple(pad) if hasattr(pad, "__len__") else (pad,) * planes
+        samples = tuple(int(v) for v in given)
+        if len(samples) != planes or samples != given or any(isinstance(v, bool) for v in given) or \
+                not all(0 <= v <= 255 for v in samples):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"pad {pad!r}: an integer 0..255, or {planes} of them (one per plane)") from None
+    d = _lib.TensorFitDesc()
+    d.r, d.fit = desc, _lib.TENSOR_FIT[fit]
+    d.pad[:] = samples + (0,) * (4 - planes)
+    return d
+
+
 def snap_rois(boxes, width: int, height: int):
     """Corner boxes ``(k, x0, y0, x1, y1)`` (floats or ints, as detectors emit
     them; k indexes a picture list) as the ``(k, x, y, cw, ch)`` boxes of
@@ -154,18 +218,25 @@ def snap_rois(boxes, width: int, height: int):
 
 
 def rois_desc(rois, size, npics, width, height, mode="rgb", dtype=None, scale=None, bias=None, mean=None, std=None,
-              colour=None, unspecified=None, stream_ok=False):
+              colour=None, unspecified=None, stream_ok=False, fit=None, pad=None):
     """(``_lib.TensorResizeDesc`` with a zero window, ``_lib.Roi`` array, planes,
     torch dtype) of a region-of-interest export (Engine.to_tensor(rois=),
     Decoder.rois): ``rois`` = [(k, x, y, cw, ch), ...] over ``npics`` pictures
     of width x height, every box to ``size`` = (oh, ow).  The rules of
     include/h264mi.h: a non-empty list, k in [0, npics), every box even,
     inside the picture, at most 16384 a side and 32 source samples per output
-    and axis.  ValueError otherwise."""
+    and axis.  With ``fit`` (or ``pad``) the descriptor is the
+    ``_lib.TensorFitDesc`` of the letterboxed export (``fit_desc``): every box
+    gets its own fit into ``size``, and the 32 samples per output are judged
+    against its content size.  ValueError otherwise."""
     if size is None:
         raise ValueError("rois: goes with size=(oh, ow)")
     desc, planes, dtype = tensor_desc((0, 0, 0, 0), mode, dtype, scale, bias, mean, std, size, colour, unspecified,
                                       stream_ok)
+    oh, ow = desc.oh, desc.ow
+    if fit is not None or pad is not None:
+        fit = "letterbox" if fit is None else fit
+        desc = fit_desc(desc, planes, fit, 114 if pad is None else pad)
     try:
         given = [tuple(b) for b in rois]
         boxes = [tuple(int(v) for v in b) for b in given]
@@ -180,9 +251,11 @@ def rois_desc(rois, size, npics, width, height, mode="rgb", dtype=None, scale=No
             raise ValueError(f"rois: box {(k, x, y, cw, ch)}: picture {k} of {npics}")
         if (x | y | cw | ch) & 1 or x < 0 or y < 0 or cw < 2 or ch < 2 or cw > width - x or ch > height - y:
             raise ValueError(f"rois: box {(k, x, y, cw, ch)}: even and inside {width} x {height}")
-        if cw > _lib.RESIZE_MAX_DIM or ch > _lib.RESIZE_MAX_DIM or cw > 32 * desc.ow or ch > 32 * desc.oh:
-            raise ValueError(f"rois: box {(k, x, y, cw, ch)}: at most {_lib.RESIZE_MAX_DIM} a side and 32 times "
-                             f"the size {(desc.oh, desc.ow)} on each axis")
+        if cw > _lib.RESIZE_MAX_DIM or ch > _lib.RESIZE_MAX_DIM:
+            raise ValueError(f"rois: box {(k, x, y, cw, ch)}: at most {_lib.RESIZE_MAX_DIM} a side")
+        rw, rh = (ow, oh) if fit is None else letterbox_fit(cw, ch, (oh, ow), fit)[:2]
+        if cw > 32 * rw or ch > 32 * rh or rw > ow or rh > oh:
+            raise ValueError(f"rois: box {(k, x, y, cw, ch)}: at most 32 times the size {(rh, rw)} on each axis")
     arr = (_lib.Roi * len(boxes))(*[_lib.Roi(*b) for b in boxes])
     return desc, arr, planes, dtype
 
@@ -545,7 +618,7 @@ class Engine:
 
     def to_tensor(self, streams: Sequence[int], slots: Sequence[int], window=None, mode: str = "rgb", dtype=None,
                   scale=None, bias=None, mean=None, std=None, out=None, stream=None, size=None, colour=None,
-                  rois=None):
+                  rois=None, fit=None, pad=None):
         """The slots (streams[k], slots[k]) as one ``(n, planes, ch, cw)``
         torch tensor on ``cuda:{self.device}``, built on the GPU and never
         copied to the host: planes R, G, B (``mode="rgb"``, the values of
@@ -575,6 +648,15 @@ class Engine:
         (``snap_rois`` makes such boxes from a detector's corners); a bad box,
         an empty list or a k out of range is a ValueError.
 
+        ``fit`` = "letterbox", "topleft" or "stretch" (with ``size``, with or
+        without ``rois``): ``size`` is a canvas, and the window -- or every box
+        on its own -- is scaled with its aspect ratio kept
+        (``letterbox_fit``), centred ("letterbox") or at the top left, the rest
+        of the canvas being the element of the sample ``pad`` (default 114;
+        one value, or one per plane) under the same scale and bias, all in
+        the one launch.  "stretch" gives the bytes of ``size``
+        alone.  ``engine.unletterbox`` maps a detector's boxes back.
+
         The export is ordered on ``stream`` (a torch.cuda.Stream; default:
         torch's current stream of the device): it starts after the work queued
         there and after every launch queued on the engine, later work on
@@ -584,21 +666,33 @@ class Engine:
         new ``torch.empty``.  The result is an ordinary torch tensor, so DLPack
         consumers (``torch.utils.dlpack`` / ``__dlpack__``) need nothing further."""
         n, c_streams, c_slots = self._pictures(streams, slots)
+        fitted = fit is not None or pad is not None
+        if fitted and size is None:
+            raise ValueError("fit and pad go with size=(oh, ow), the canvas")
         if rois is not None:
             if window is not None:
                 raise ValueError("rois: not combinable with window (each box is one)")
             desc, boxes, planes, dtype = rois_desc(rois, size, n, self.w_mbs * 16, self.h_mbs * 16, mode, dtype, scale,
-                                                   bias, mean, std, colour)
-            out, st = self._out((len(boxes), planes, desc.oh, desc.ow), dtype, out, stream)
-            if not hasattr(self._L, "h264mi_engine_export_tensor_rois") or \
-                    self._L.h264mi_engine_export_tensor_rois(self._h, n, c_streams, c_slots, C.byref(desc), boxes,
-                                                             len(boxes), out.data_ptr(),
-                                                             planes * desc.oh * desc.ow * out.element_size(), st) != 0:
-                raise RuntimeError("h264mi_engine_export_tensor_rois failed (stream or slot out of range?)")
+                                                   bias, mean, std, colour, fit=fit, pad=pad)
+            name = "h264mi_engine_export_tensor_rois_fit" if fitted else "h264mi_engine_export_tensor_rois"
+            oh, ow = (desc.r.oh, desc.r.ow) if fitted else (desc.oh, desc.ow)
+            out, st = self._out((len(boxes), planes, oh, ow), dtype, out, stream)
+            if not hasattr(self._L, name) or \
+                    getattr(self._L, name)(self._h, n, c_streams, c_slots, C.byref(desc), boxes, len(boxes),
+                                           out.data_ptr(), planes * oh * ow * out.element_size(), st) != 0:
+                raise RuntimeError(f"{name} failed (stream or slot out of range?)")
             return out
         if window is None:
             window = (0, 0, self.w_mbs * 16, self.h_mbs * 16)
         desc, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std, size, colour)
+        if fitted:
+            fd = fit_desc(desc, planes, "letterbox" if fit is None else fit, 114 if pad is None else pad)
+            out, st = self._out((n, planes, desc.oh, desc.ow), dtype, out, stream)
+            if not hasattr(self._L, "h264mi_engine_export_tensor_fit") or \
+                    self._L.h264mi_engine_export_tensor_fit(self._h, n, c_streams, c_slots, C.byref(fd), out.data_ptr(),
+                                                            planes * desc.oh * desc.ow * out.element_size(), st) != 0:
+                raise RuntimeError("h264mi_engine_export_tensor_fit failed (stream, slot, window or size out of range?)")
+            return out
         shape = (n, planes, desc.ch, desc.cw) if size is None else (n, planes, desc.oh, desc.ow)
         if out is None and min(shape) < 1:
             raise ValueError(f"window {tuple(window)}")

@@ -241,6 +241,38 @@ typedef struct { int pic, x, y, cw, ch; } h264mi_roi;
  * picture has been delivered; H264SWDEC_PIC_RDY on success. */
 H264SwDecRet H264SwDecLastPictureTensorRois(H264SwDecInst decInst, const h264mi_tensor_resize_desc *desc,
                                             const h264mi_roi *rois, u32 nrois, void *d_dst, void *hip_stream);
+/* Letterboxed tensors (resize.hip): the window scaled with its
+ * aspect ratio kept and placed in a canvas of r.oh x r.ow (the output's shape,
+ * as for the resized tensor), the rest of the canvas a constant.  The fit of a
+ * cw x ch window into ow x oh is the content size and position (rw, rh, px,
+ * py), in integers with 64-bit intermediates:
+ *   width-bound (cw oh >= ch ow)  rw = ow, rh = (2 ch ow + cw) / (2 cw) --
+ *       nearest, halves up --, raised to max(rh, ceil(ch / 32), 1), which keeps
+ *       the minor axis within the resize's 32 source samples per output;
+ *   height-bound (otherwise)      the same with the axes swapped;
+ *   H264MI_FIT_LETTERBOX          px = (ow - rw) / 2, py = (oh - rh) / 2, floored;
+ *   H264MI_FIT_LETTERBOX_TOPLEFT  px = py = 0;
+ *   H264MI_FIT_STRETCH            (ow, oh, 0, 0): the resized tensor's bytes.
+ * Inside the content rectangle the output is the resized tensor of the window
+ * at (rh, rw), byte for byte; everywhere else the element a sample of value
+ * pad[p] of plane p (R, G, B or luma; GRAY uses pad[0]) becomes under scale[p]
+ * and bias[p].  pad[3] is reserved: 0.  Rules: the resized tensor's, with the
+ * window judged against its content size (cw <= 32 rw, ch <= 32 rh), fit one of
+ * the three, pad[3] == 0. */
+enum { H264MI_FIT_STRETCH = 0, H264MI_FIT_LETTERBOX = 1, H264MI_FIT_LETTERBOX_TOPLEFT = 2 };
+typedef struct { h264mi_tensor_resize_desc r; int fit; unsigned char pad[4]; } h264mi_tensor_fit_desc;
+/* (rw, rh, px, py) of a cw x ch window in an ow x oh canvas into out; -1 for a
+ * size below 1 or above 16384, or an unknown fit.  A pure function. */
+int h264mi_letterbox_fit(int cw, int ch, int ow, int oh, int fit, int out[4]);
+/* NextPictureTensorResized and LastPictureTensorRois, letterboxed: the
+ * window (desc->r.t.cw == 0: the crop window), or every box, gets its own fit
+ * into the canvas.  H264MI_TENSOR_COLOUR_STREAM resolves as for those calls
+ * (by size: from the export window, never from the canvas), and
+ * H264SwDecLastTensorColour reports it.  Return codes are theirs. */
+H264SwDecRet H264SwDecNextPictureTensorFit(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
+                                           const h264mi_tensor_fit_desc *desc, void *d_dst, void *hip_stream);
+H264SwDecRet H264SwDecLastPictureTensorRoisFit(H264SwDecInst decInst, const h264mi_tensor_fit_desc *desc,
+                                               const h264mi_roi *rois, u32 nrois, void *d_dst, void *hip_stream);
 /* Motion vectors and MB side information as a device tensor (mbinfo.hip, DESIGN
  * 3.5d; elsewhere: ffmpeg's export_mvs).  The field lives on the luma 4x4-block
  * grid of the MB-aligned picture, BW = 4 * w_mbs columns by BH = 4 * h_mbs
@@ -706,6 +738,28 @@ int  h264mi_tensor_rois_device_pitch(const void *d_in, const size_t *in_offsets,
 int  h264mi_engine_export_tensor_rois(h264mi_engine *e, int n, const int *streams, const int *slots,
                                       const h264mi_tensor_resize_desc *desc, const h264mi_roi *rois, int nrois,
                                       void *d_out, size_t out_stride, void *hip_stream);
+/* the letterboxed exports (h264mi_tensor_fit_desc above): picture k's window
+ * desc->r.t, or box r of the list (desc->r.t's window reserved, all zero),
+ * fitted into the canvas desc->r.(oh, ow): (planes, oh, ow) elements at d_out +
+ * k (or r) * out_stride, every one of them written -- the content rectangle
+ * with the bytes h264mi_tensor_resize_device_pitch gives for that window at
+ * the content size, the rest with the pad element -- and nothing else.  One
+ * kernel launch per H264MI_ROIS_MAX_PER_LAUNCH pictures or boxes; for the
+ * engine calls one ordering of the two streams per call.  -1, nothing
+ * launched, when any box or anything else is bad, d_out in no device's memory
+ * included. */
+int  h264mi_tensor_fit_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width, int height,
+                                    int cpitch, const h264mi_tensor_fit_desc *desc, void *d_out, size_t out_stride,
+                                    void *hip_stream);
+int  h264mi_tensor_rois_fit_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width, int height,
+                                         int cpitch, const h264mi_tensor_fit_desc *desc, const h264mi_roi *rois,
+                                         int nrois, void *d_out, size_t out_stride, void *hip_stream);
+int  h264mi_engine_export_tensor_fit(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                     const h264mi_tensor_fit_desc *desc, void *d_out, size_t out_stride,
+                                     void *hip_stream);
+int  h264mi_engine_export_tensor_rois_fit(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                          const h264mi_tensor_fit_desc *desc, const h264mi_roi *rois, int nrois,
+                                          void *d_out, size_t out_stride, void *hip_stream);
 /* the MB side-information field (h264mi_mbinfo_desc above) of npics record
  * batches of w_mbs * h_mbs MbRec each, batch k starting rec_offsets[k] bytes (a
  * host array of multiples of 96; any order, repeats allowed) after d_recs
