@@ -164,6 +164,11 @@ __constant__ uint8_t cTc0[52][3] = {
     {2, 3, 4}, {2, 3, 4}, {3, 3, 5}, {3, 4, 6}, {3, 4, 6}, {4, 5, 7}, {4, 5, 8},
     {4, 6, 9}, {5, 7, 10}, {6, 8, 11}, {6, 8, 13}, {7, 10, 14}, {8, 11, 16},
     {9, 12, 18}, {10, 13, 20}, {11, 15, 23}, {13, 17, 25}};
+// QPc of qPI (table 8-15; the reference's h264bsdQpC)
+__constant__ uint8_t cQpC[52] = {
+    0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19,
+    20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 29, 30, 31, 32, 32, 33, 34, 34,
+    35, 35, 36, 36, 37, 37, 37, 38, 38, 38, 39, 39, 39, 39};
 
 // Per-wave register tables: lane i holds entry i, looked up with
 // ds_bpermute (an LDS-crossbar lane shuffle: LDS latency, no VMEM).  A
@@ -172,7 +177,7 @@ __constant__ uint8_t cTc0[52][3] = {
 // reference-window load issued before it.  Lookups run with all lanes active.
 struct Tabs {
     uint32_t ab;    // lane i < 52: alpha[i] | beta[i] << 8 | tc0[i][0] << 16 | tc0[i][1] << 24
-    uint32_t c2;    // lane i < 52: tc0[i][2]
+    uint32_t c2;    // lane i < 52: tc0[i][2] | QpC[i] << 8
     uint32_t ls;    // lane i < 18: levelScale[i / 3][i % 3]
 };
 __device__ __forceinline__ Tabs load_tabs(int lane)
@@ -180,7 +185,7 @@ __device__ __forceinline__ Tabs load_tabs(int lane)
     Tabs t;
     const int i = lane < 52 ? lane : 0;
     t.ab = cAlpha[i] | (uint32_t)cBeta[i] << 8 | (uint32_t)cTc0[i][0] << 16 | (uint32_t)cTc0[i][1] << 24;
-    t.c2 = cTc0[i][2];
+    t.c2 = cTc0[i][2] | (uint32_t)cQpC[i] << 8;
     t.ls = lane < 18 ? cLevelScale[lane / 3][lane % 3] : 0;
     return t;
 }
@@ -524,10 +529,21 @@ __device__ void mb_dbrec(int lane, uint8_t *s_db, const uint32_t *srec, const Ta
     const bool chroma = k >= 3;
     const int cls = chroma ? k - 3 : k;
     const MbRec *PN = (const MbRec *)(srec + ((cls == 1 && fl) ? 24 : (cls == 2 && ft) ? 48 : 0));
-    const int qpp = chroma ? PN->qpc : PN->qp, qq = chroma ? Q->qpc : Q->qp;
+    int qpp = chroma ? PN->qpc : PN->qp;
+    const int qq = chroma ? Q->qpc : Q->qp;
+    // chroma: both sides' QPY through this (q-side) MB's chroma QP offset
+    // (GetChromaEdgeThresholds, deblocking.c:1478-1514).  That is the
+    // neighbour's own qpc unless it carries another offset -- a concealed MB
+    // carries 0 whatever the PPS says -- and only then (wave-uniform: the
+    // lookup runs with all lanes active) its QPY goes through the table
+    const bool other = thr && chroma && ((PN->dbf ^ Q->dbf) >> DBF_CQO_SHIFT) != 0;
+    if (__builtin_amdgcn_ballot_w64(other) != 0) {
+        const int c = (int)(tab_at(T.c2, clip3(0, 51, PN->qp + DBF_CQO_OF(Q->dbf))) >> 8);
+        if (other) qpp = c;
+    }
     const int qpav = (qpp + qq + 1) >> 1;
     const int ia = clip3(0, 51, qpav + Q->offA), ib = clip3(0, 51, qpav + Q->offB);
-    const uint32_t wa = tab_at(T.ab, ia), wb = tab_at(T.ab, ib), t2 = tab_at(T.c2, ia);
+    const uint32_t wa = tab_at(T.ab, ia), wb = tab_at(T.ab, ib), t2 = tab_at(T.c2, ia) & 255u;
     const uint32_t al = wa & 255, be = (wb >> 8) & 255, t0 = (wa >> 16) & 255, t1 = wa >> 24;
     // bS: lanes 0..31 = (dir, line segment kk, edge e)
     int bS = 0;

@@ -116,7 +116,10 @@ void h264dec_conceal_mb_intra(uint8_t *img, int w, int h, int row, int col, cons
 }
 
 /* fields every concealed MB gets (:300-308): filtered as intra, QP 40,
- * deblocking idc 0 -- left / top MB edges wherever the neighbour exists */
+ * deblocking idc 0 -- left / top MB edges wherever the neighbour exists --
+ * and chroma QP offset 0 (copy_record / pcm_record leave DBF_CQO at 0), which
+ * the loop filter also applies to the QPY of the decoded MB across each of
+ * this MB's left and top edges */
 static void conceal_fields(MbRec *r, int w, int mb)
 {
     r->qp = CONCEAL_QP;

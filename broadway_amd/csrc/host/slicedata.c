@@ -147,7 +147,7 @@ static void finish_rec(PicBuild *pb, int cur, const SliceHdr *sh, const Pps *pps
     r->offB = (int8_t)(sh->off_b_div2 * 2);
     r->qpc = kQpChroma[clip3(0, 51, r->qp + pps->chroma_qp_offset)];
     r->slice = tag;
-    r->dbf = 0;
+    r->dbf = DBF_CQO(pps->chroma_qp_offset);
     r->refidx = 0;
     if (r->type == MBT_INTER)
         for (int i = 0; i < 4; i++) r->refidx |= (uint16_t)((pc->mb[cur].refidx[i] & 15) << (4 * i));
@@ -458,7 +458,7 @@ static void failed_mb(PicBuild *pb, int cur)
     r->cbits = 0;
     memset(r->mv, 0, sizeof(r->mv));
     for (int i = 0; i < 4; i++) r->ref[i] = (uint8_t)pb->cur_slot;
-    r->dbf = intra ? DBF_INTRA : 0;
+    r->dbf = (uint8_t)((r->dbf & ~DBF_INTRA) | (intra ? DBF_INTRA : 0));
     pb->decoded[cur] = 1;
 }
 

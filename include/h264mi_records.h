@@ -13,7 +13,8 @@
  *   - cbits/coef    <- residual_t.level/totalCoeff: only coded blocks travel,
  *                      each as 16 int16 levels in scan order
  *   - qp            <- mbStorage_t.qpY (0 for I_PCM, macroblock_layer.c:1003)
- *   - dbf/offA/offB <- mbStorage_t.disableDeblockingFilterIdc/filterOffsetA/B
+ *   - dbf/offA/offB <- mbStorage_t.disableDeblockingFilterIdc/filterOffsetA/B;
+ *                      dbf also carries mbStorage_t.chromaQpIndexOffset
  *   - slice         <- mbStorage_t.sliceId
  *
  * Coefficient blocks (int16[16] each) referenced by a record are stored
@@ -57,15 +58,28 @@ enum {
      * (h264bsd_conceal.c:300-308) while P concealment copies the co-located
      * MB of a reference picture (:310-332) */
     DBF_INTRA = 1,
+    /* bits 1, 2 unused.  Bits 3..7: the MB's chroma_qp_index_offset
+     * (mbStorage_t.chromaQpIndexOffset: its PPS's, -12..12; 0 for a concealed
+     * MB, h264bsd_conceal.c:308) as a signed 5-bit value, DBF_CQO / DBF_CQO_OF.
+     * The loop filter takes the chroma QP of both sides of a chroma edge from
+     * their QPY through the offset of the MB that owns the edge, the q side
+     * (GetChromaEdgeThresholds, h264bsd_deblocking.c:1478-1514) -- which is
+     * MbRec.qpc only for an MB with that same offset: the p side's qpc is
+     * used where the two offsets are equal, else QpChroma of its QPY through
+     * the q side's offset. */
+    DBF_CQO_SHIFT = 3,
 };
+#define DBF_CQO(off)    ((uint8_t)((unsigned)(off) << DBF_CQO_SHIFT))
+#define DBF_CQO_OF(dbf) ((int)(int8_t)(dbf) >> DBF_CQO_SHIFT)
 
 typedef struct MbRec {
     uint8_t  type;      /* MBT_* */
     uint8_t  qp;        /* QPY (I_PCM: 0) */
-    uint8_t  qpc;       /* QPc = QpChroma[clip3(0,51,QPY+chroma_qp_index_offset)] */
+    uint8_t  qpc;       /* QPc = QpChroma[clip3(0,51,QPY+chroma_qp_index_offset)]: the MB's own,
+                           for its residual; the loop filter derives its own (DBF_CQO) */
     uint8_t  avail;     /* AV_* | DB_* */
     uint8_t  pred;      /* I16: mode (bits 0-1); chroma mode bits 4-5 */
-    uint8_t  dbf;       /* DBF_* */
+    uint8_t  dbf;       /* DBF_* | DBF_CQO(chroma_qp_index_offset) */
     int8_t   offA;      /* FilterOffsetA = slice_alpha_c0_offset_div2 << 1 */
     int8_t   offB;      /* FilterOffsetB */
     uint32_t cbits;     /* coded-block mask, see above */

@@ -530,7 +530,12 @@ static void deblock_mb(Planes *pl, const MbRec *rec, int w_mbs, int mbx, int mby
             }
             /* chroma: edges 0 and 2 of luma map to chroma edges 0 and 1 */
             if (e & 1) continue;
-            int qpc_av = (p->qpc + q->qpc + 1) >> 1;
+            /* both sides' QPY through the q-side MB's chroma QP offset
+             * (GetChromaEdgeThresholds, deblocking.c:1478-1514): p->qpc
+             * unless p carries another offset (a concealed MB's is 0) */
+            const int cqo = DBF_CQO_OF(q->dbf);
+            const int qpc_p = DBF_CQO_OF(p->dbf) == cqo ? p->qpc : kQpChroma[clip3(0, 51, p->qp + cqo)];
+            int qpc_av = (qpc_p + q->qpc + 1) >> 1;
             int ca = clip3(0, 51, qpc_av + q->offA), cb = clip3(0, 51, qpc_av + q->offB);
             int calpha = kAlpha[ca], cbeta = kBeta[cb];
             for (int comp = 0; comp < 2; comp++) {

@@ -50,6 +50,7 @@ CASES = {
 # Their fixtures also hold every output picture's (picId, isIdr, nbrOfErrMBs)
 # as DecTestBench prints it.
 _B = dict(nframes=12, w_mbs=11, h_mbs=9, crop_bottom=0, slices=3, gop=6)
+_MIX = dict(err_range_pct=20, drop_slice_pct=15, trunc_slice_pct=15, drop_pic_pct=10)
 ERR_CASES = {
     # I slices: includes an error on a slice's second MB, which the
     # reference's un-marking does not reach (slice_data.c:322-338)
@@ -68,6 +69,24 @@ ERR_CASES = {
     # 00 00 02 inside a slice NAL without any 00 00 03 (patched in, see
     # find_patch): no emulation check, the slice fails to parse instead
     "err_000002_no_epb": (1, 12, dict(nframes=3, w_mbs=12, h_mbs=6, slices=1), False),
+    # A PPS with a chroma QP offset under every damage kind: a concealed MB
+    # has offset 0 (conceal.c:308), and a chroma edge takes both sides' QP
+    # through the offset of the MB that owns it (deblocking.c:1478-1514), so
+    # the edges between concealed and decoded MBs tell a per-edge offset from
+    # one chroma QP per MB.  Seeds chosen so that, with one chroma QP per MB
+    # averaged over the edge (the oracle before this rule), the oracle differs
+    # from the reference in 11 of 11, 10 of 10, 12 of 12, 4 of 10, 11 of 11
+    # and 8 of 11 pictures (checked on the CPU).  Dropped pictures alone lose
+    # or keep whole pictures; with RefPicList0 modification over two
+    # reference frames some slices of a picture name the missing one.
+    "err_range_cqo12_11x9": (2, 2, dict(_B, chroma_qp_offset=12, err_range_pct=60), False),
+    "err_drop_slice_cqo12_11x9": (2, 2, dict(_B, chroma_qp_offset=12, drop_slice_pct=25), False),
+    "err_trunc_slice_cqo12_11x9": (2, 4, dict(_B, chroma_qp_offset=12, trunc_slice_pct=25), False),
+    "err_drop_pic_gaps_cqo12_11x9": (2, 17, dict(_B, chroma_qp_offset=12, drop_pic_pct=20, gaps_allowed=1,
+                                                 num_ref_frames=2, ref_mod_pct=50), False),
+    "err_mixed_cqom12_11x9": (2, 6, dict(_B, chroma_qp_offset=-12, **_MIX), False),
+    # I pictures only: neighbour-based concealment
+    "err_mixed_i_cqo3_11x9": (2, 7, dict(_B, gop=1, chroma_qp_offset=3, **_MIX), False),
 }
 PATCHED = {"err_000002_no_epb"}
 CASES.update(ERR_CASES)

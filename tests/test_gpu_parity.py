@@ -541,3 +541,31 @@ def test_swdec_pooled_engines_vs_reference(monkeypatch):
     reused2, created2 = C.c_ulonglong(), C.c_ulonglong()
     L.h264mi_engine_pool_stats(C.byref(reused2), C.byref(created2))
     assert reused2.value == reused1.value and created2.value - created1.value == 2
+
+
+def test_sweep_sample_vs_oracle():
+    """16 clean and 32 damaged streams of the differential sweep
+    (tests/_sweep.py: every generator knob drawn at once; pictures up to 7x3
+    MBs) through H264SwDec*: every output picture, picture id, IDR flag and
+    nbrOfErrMBs equals the CPU oracle's, which tests/test_reference_sweep.py
+    pins to the reference decoder on the same streams.  At least 8 of the
+    damaged streams conceal MBs under a PPS with a chroma QP offset: the
+    chroma edges between concealed and decoded MBs take their QP through the
+    q-side MB's offset (k_prep, mb_dbrec)."""
+    import _sweep
+    L = _lib.mi()
+    concealed_with_offset = 0
+    try:
+        for damaged, n in ((False, 16), (True, 32)):
+            for seed in _sweep.small_sample(damaged, n):
+                ov, nr = _sweep.draw(seed, damaged)
+                s = gen.generate(2, seed, **ov)
+                want, _, _, _, _, want_pics = O.decode(s, no_reorder=nr, info=True)
+                frames, _, pics = swdec_decode(s, no_reorder=nr, info=True)
+                assert want, (seed, ov)
+                assert pics == want_pics, (seed, ov, nr)
+                assert md5s(frames) == md5s(want), (seed, ov, nr)
+                concealed_with_offset += bool(damaged and ov["chroma_qp_offset"] and any(p[2] for p in pics))
+    finally:
+        L.h264mi_pool_drain()       # engines of five picture sizes: leave the pool as an empty one
+    assert concealed_with_offset >= 8, concealed_with_offset
