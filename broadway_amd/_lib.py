@@ -99,6 +99,11 @@ class TensorFitDesc(C.Structure):
     _fields_ = [("r", TensorResizeDesc), ("fit", C.c_int), ("pad", C.c_ubyte * 4)]
 
 
+class TensorLayoutDesc(C.Structure):
+    """h264mi_tensor_layout_desc (include/h264mi.h)."""
+    _fields_ = [("f", TensorFitDesc), ("layout", C.c_int)]
+
+
 class MbInfoDesc(C.Structure):
     """h264mi_mbinfo_desc (include/h264mi.h)."""
     _fields_ = [(n, C.c_int) for n in ("bx", "by", "bw", "bh", "nch", "dtype")] + \
@@ -164,6 +169,8 @@ RESIZE_MAX_DIM = 16384
 ROIS_MAX_PER_LAUNCH = 32
 TENSOR_FIT = {"stretch": 0, "letterbox": 1, "topleft": 2}
 TENSOR_U8, TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 0, 1, 2, 3
+# TensorLayoutDesc.layout by the name of the torch memory format it gives
+TENSOR_LAYOUTS = {"nchw": 0, "nhwc": 1}
 
 HEADERS_CB = C.CFUNCTYPE(None, C.c_void_p)
 PICTURE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32)
@@ -318,6 +325,16 @@ def mi() -> C.CDLL:
         L.H264SwDecNextPictureTensorFit.restype = i32
         L.H264SwDecLastPictureTensorRoisFit.argtypes = [vp, fd, ro, u32, vp, vp]
         L.H264SwDecLastPictureTensorRoisFit.restype = i32
+    if hasattr(L, "h264mi_tensor_layout_device_pitch"):     # (optional, as above)
+        ld, ro = C.POINTER(TensorLayoutDesc), C.POINTER(Roi)
+        L.h264mi_tensor_layout_device_pitch.argtypes = [vp, C.POINTER(sz), i32, i32, i32, i32, ld, ro, i32, vp, sz, vp]
+        L.h264mi_tensor_layout_device_pitch.restype = i32
+        L.h264mi_engine_export_tensor_layout.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), ld, ro, i32, vp, sz, vp]
+        L.h264mi_engine_export_tensor_layout.restype = i32
+        L.H264SwDecNextPictureTensorLayout.argtypes = [vp, C.POINTER(H264SwDecPicture), u32, ld, vp, vp]
+        L.H264SwDecNextPictureTensorLayout.restype = i32
+        L.H264SwDecLastPictureTensorRoisLayout.argtypes = [vp, ld, ro, u32, vp, vp]
+        L.H264SwDecLastPictureTensorRoisLayout.restype = i32
     if hasattr(L, "h264mi_mbinfo_device"):                  # (optional, as above)
         md = C.POINTER(MbInfoDesc)
         L.h264mi_mbinfo_device.argtypes = [vp, C.POINTER(sz), i32, i32, i32, md, vp, sz, vp]

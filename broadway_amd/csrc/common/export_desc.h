@@ -156,6 +156,35 @@ static inline int rois_fit_ok(const h264mi_tensor_fit_desc *d, const h264mi_roi 
     return 1;
 }
 
+/* h264mi_tensor_layout_desc: a known layout over either the unresized export
+ * (no size: the tensor descriptor's rules, and nothing of the fit set) or the
+ * fit descriptor with its own rules (STRETCH: the resized export) */
+static inline int layout_unresized(const h264mi_tensor_layout_desc *d)
+{
+    return d->f.r.ow == 0 && d->f.r.oh == 0;
+}
+
+static inline int layout_desc_fixed_ok(const h264mi_tensor_layout_desc *d)
+{
+    if (d->layout != H264MI_LAYOUT_PLANAR && d->layout != H264MI_LAYOUT_INTERLEAVED) return 0;
+    if (!layout_unresized(d)) return fit_desc_fixed_ok(&d->f);
+    return tensor_desc_fixed_ok(&d->f.r.t) && d->f.fit == H264MI_FIT_STRETCH && d->f.r.filter == 0 &&
+           !(d->f.pad[0] | d->f.pad[1] | d->f.pad[2] | d->f.pad[3]);
+}
+
+/* (after layout_desc_fixed_ok) */
+static inline int layout_window_ok(const h264mi_tensor_layout_desc *d, int width, int height)
+{
+    return layout_unresized(d) ? tensor_window_ok(&d->f.r.t, width, height) : fit_window_ok(&d->f, width, height, NULL);
+}
+
+/* rois_fit_ok under a layout descriptor: boxes require a size */
+static inline int rois_layout_ok(const h264mi_tensor_layout_desc *d, const h264mi_roi *r, int nrois, int npics,
+                                 int width, int height)
+{
+    return layout_desc_fixed_ok(d) && !layout_unresized(d) && rois_fit_ok(&d->f, r, nrois, npics, width, height);
+}
+
 /* h264mi_mbinfo_desc: the window is in 4x4 blocks of a w_mbs x h_mbs picture */
 static inline int mbinfo_desc_fixed_ok(const h264mi_mbinfo_desc *d)
 {

@@ -347,10 +347,12 @@ static int export_launches(int npics, const size_t *offsets, unsigned long long 
 }
 
 // Both tensor exports (r != NULL: resized, t = &r->t): one check and one fill
-// of what their kernels share, resize_args::t
+// of what their kernels share, resize_args::t.  hwc (unresized RGB only, from
+// h264mi_tensor_layout_device_pitch): the elements interleaved, and a row is
+// 3 cw elements
 static int tensor_device(const void *d_in, const size_t *in_offsets, int npics, int width, int height, int cpitch,
                          const h264mi_tensor_desc *t, const h264mi_tensor_resize_desc *r, void *d_out,
-                         size_t out_stride, hipStream_t stream)
+                         size_t out_stride, hipStream_t stream, bool hwc = false)
 {
     static_assert(H264MI_TENSOR_RGB == TENSOR_RGB && H264MI_TENSOR_GRAY == TENSOR_GRAY &&
                       H264MI_TENSOR_U8 == TENSOR_U8 && H264MI_TENSOR_F16 == TENSOR_F16 &&
@@ -362,8 +364,9 @@ static int tensor_device(const void *d_in, const size_t *in_offsets, int npics, 
         return -1;
     const size_t es = export_elem_size(t->dtype);
     if (!export_aligned(d_out, out_stride, es)) return -1;
-    const bool v16 = export_v16(d_out, out_stride, (size_t)t->cw * es);
+    const bool v16 = export_v16(d_out, out_stride, (size_t)t->cw * es * (hwc ? 3 : 1));
     const int layout = H264MI_TENSOR_LAYOUT(t->mode), colour = H264MI_TENSOR_COLOUR(t->mode);
+    if (hwc && (r || layout != H264MI_TENSOR_RGB)) return -1;
     resize_args ra;
     tensor_args &a = ra.t;
     a.in = (const uint8_t *)d_in;
@@ -375,7 +378,7 @@ static int tensor_device(const void *d_in, const size_t *in_offsets, int npics, 
     if (r) { ra.ow = r->ow; ra.oh = r->oh; }
     return export_launches(npics, in_offsets, a.in_off, &a.out, d_out, out_stride, [&](int, int n) {
         if (r) resize_launch(layout, t->dtype, colour != 0, n, stream, ra);
-        else tensor_launch(layout, t->dtype, v16, colour != 0, n, stream, a);
+        else tensor_launch(layout, t->dtype, v16, colour != 0, hwc, n, stream, a);
     });
 }
 
@@ -425,13 +428,15 @@ static bool rois_desc_ok(const h264mi_tensor_resize_desc *d, const h264mi_roi *r
 // The launches of the list exports, behind their checks (the descriptor's and
 // the pictures').  fit != NULL (desc = &fit->r): every box fitted into the canvas (oh, ow) by
 // letterbox_fit, the rest of the canvas fit->pad; whole != NULL:
-// the list is `whole` of every picture (the single-window form) and rois is unused
+// the list is `whole` of every picture (the single-window form) and rois is unused;
+// hwc (RGB, fit != NULL, from h264mi_tensor_layout_device_pitch): the elements interleaved
 static int rois_device(const void *d_in, const size_t *in_offsets, int npics, int width, int height, int cpitch,
                        const h264mi_tensor_resize_desc *desc, const h264mi_tensor_fit_desc *fit,
                        const h264mi_tensor_desc *whole, const h264mi_roi *rois, int nrois, void *d_out,
-                       size_t out_stride, void *stream)
+                       size_t out_stride, void *stream, bool hwc = false)
 {
     const h264mi_tensor_desc *t = &desc->t;
+    if (hwc && (!fit || H264MI_TENSOR_LAYOUT(t->mode) != H264MI_TENSOR_RGB)) return -1;
     // (d_out is checked here too: a list is one lookup, and a host address would fault every launch of it)
     if (!export_aligned(d_out, out_stride, export_elem_size(t->dtype)) || h264mi_pointer_device(d_out) < 0) return -1;
     const int layout = H264MI_TENSOR_LAYOUT(t->mode), colour = H264MI_TENSOR_COLOUR(t->mode);
@@ -460,7 +465,8 @@ static int rois_device(const void *d_in, const size_t *in_offsets, int npics, in
                 fa.place[r][0] = f[2]; fa.place[r][1] = f[3]; fa.place[r][2] = f[0]; fa.place[r][3] = f[1];
             }
         }
-        if (fit) fit_launch(layout, t->dtype, colour != 0, n, (hipStream_t)stream, fa);
+        if (hwc) fit_hwc_launch(t->dtype, colour != 0, n, (hipStream_t)stream, fa);
+        else if (fit) fit_launch(layout, t->dtype, colour != 0, n, (hipStream_t)stream, fa);
         else rois_launch(layout, t->dtype, colour != 0, n, (hipStream_t)stream, ra);
     });
 }
@@ -534,6 +540,41 @@ extern "C" int h264mi_tensor_rois_fit_device_pitch(const void *d_in, const size_
         return -1;
     return rois_device(d_in, in_offsets, npics, width, height, cpitch, &desc->r, desc, NULL, rois, nrois, d_out,
                        out_stride, stream);
+}
+
+// The four pixel exports under a layout descriptor (include/h264mi.h, DESIGN
+// §3.5m): one check (common/export_desc.h), then the path of the call it
+// mirrors.  PLANAR and GRAY are that call; INTERLEAVED RGB is tensor_device's
+// unresized launch with its interleaved kernels, or -- every resized form, a
+// stretch included -- the table form of the fit kernel with interleaved stores.
+// rois == NULL (then nrois == 0): desc's window of every picture.
+static bool layout_desc_ok(const h264mi_tensor_layout_desc *d, const h264mi_roi *rois, int nrois, int npics, int width,
+                           int height)
+{
+    if (!d || !tensor_mode_ok(d->f.r.t.mode) || (rois ? nrois < 1 : nrois != 0)) return false;
+    if (rois) return rois_layout_ok(d, rois, nrois, npics, width, height);
+    return layout_desc_fixed_ok(d) && layout_window_ok(d, width, height);
+}
+
+extern "C" int h264mi_tensor_layout_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width,
+                                                 int height, int cpitch, const h264mi_tensor_layout_desc *desc,
+                                                 const h264mi_roi *rois, int nrois, void *d_out, size_t out_stride,
+                                                 void *stream)
+{
+    if (!tensor_pics_ok(d_in, in_offsets, npics, width, height, cpitch, d_out) ||
+        !layout_desc_ok(desc, rois, nrois, npics, width, height))
+        return -1;
+    const h264mi_tensor_fit_desc *f = &desc->f;
+    const bool hwc = desc->layout == H264MI_LAYOUT_INTERLEAVED && H264MI_TENSOR_LAYOUT(f->r.t.mode) == H264MI_TENSOR_RGB;
+    if (layout_unresized(desc))
+        return tensor_device(d_in, in_offsets, npics, width, height, cpitch, &f->r.t, NULL, d_out, out_stride,
+                             (hipStream_t)stream, hwc);
+    const bool stretch = f->fit == H264MI_FIT_STRETCH;
+    if (!rois && stretch && !hwc)
+        return tensor_device(d_in, in_offsets, npics, width, height, cpitch, &f->r.t, &f->r, d_out, out_stride,
+                             (hipStream_t)stream);
+    return rois_device(d_in, in_offsets, npics, width, height, cpitch, &f->r, stretch && !hwc ? NULL : f,
+                       rois ? NULL : &f->r.t, rois, rois ? nrois : npics, d_out, out_stride, stream, hwc);
 }
 
 // An export of the slots (streams[k], slots[k]), k < n, into the caller's
@@ -641,6 +682,23 @@ extern "C" int h264mi_engine_export_tensor_rois_fit(h264mi_engine *e, int n, con
 {
     if (!rois) return -1;
     return engine_export_fit(e, n, streams, slots, desc, rois, nrois, d_out, out_stride, stream);
+}
+
+// the frame slots, or boxes over them, under a layout descriptor
+// (h264mi_tensor_layout_device_pitch): one ordering of the two streams per call
+extern "C" int h264mi_engine_export_tensor_layout(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                                  const h264mi_tensor_layout_desc *desc, const h264mi_roi *rois,
+                                                  int nrois, void *d_out, size_t out_stride, void *stream)
+{
+    if (!e || n < 1 || !streams || !slots || !d_out) return -1;
+    const int width = e->w * 16, height = e->h * 16;
+    if (!layout_desc_ok(desc, rois, nrois, n, width, height)) return -1;
+    return export_ordered(e, n, streams, slots, d_out, out_stride, export_elem_size(desc->f.r.t.dtype), stream, [&] {
+        std::vector<size_t> off((size_t)n);
+        for (int k = 0; k < n; k++) off[k] = e->frame_bytes * ((size_t)streams[k] * e->nslots + slots[k]);
+        return h264mi_tensor_layout_device_pitch(e->d_frames, off.data(), n, width, height, e->cpitch, desc, rois, nrois,
+                                                 d_out, out_stride, e->st);
+    });
 }
 
 // Motion vectors and MB side information as planar fields (mbinfo.hip): the

@@ -179,6 +179,15 @@ __device__ __forceinline__ void resize_store(uint8_t *O, size_t o, uint32_t v)
     else __builtin_nontemporal_store(v, (uint32_t *)O + o);
 }
 
+// element (p, i, j) of a picture of (NP, oh, ow) elements: planar, or (HWC,
+// DESIGN §3.5m) interleaved, (oh, ow, NP)
+template <bool HWC, int NP>
+__device__ __forceinline__ size_t resize_out_index(int p, int i, int j, int oh, int ow)
+{
+    if constexpr (HWC) return ((size_t)i * ow + (size_t)j) * NP + p;
+    return ((size_t)p * oh + (size_t)i) * ow + (size_t)j;
+}
+
 // the arguments of k_tensor_resize<.., ROIS, FIT>, and their resize_args
 template <bool ROIS, bool FIT> struct resize_kernel_args { typedef resize_args type; };
 template <> struct resize_kernel_args<true, false> { typedef rois_args type; };
@@ -195,11 +204,14 @@ __device__ __forceinline__ const resize_args &resize_part(const rois_args &a) { 
 // FIT (with ROIS): (oh, ow) is a canvas, and the row's outputs are the rw x rh
 // at (px, py) of it, ka.place[blockIdx.y] = (px, py, rw, rh); a tile holds the
 // content's columns [jx0, jx1) and rows [iy0, iy1) of its own (without FIT: all
-// of the tile), the rest of it is ka.pad.
-template <int MODE, int DT, bool COL = false, bool ROIS = false, bool FIT = false>
+// of the tile), the rest of it is ka.pad.  HWC (RGB, with FIT -- the table form
+// serves every interleaved resized export, a stretch being a content that
+// fills the canvas): every store's index is the interleaved one, nothing else.
+template <int MODE, int DT, bool COL = false, bool ROIS = false, bool FIT = false, bool HWC = false>
 __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename resize_kernel_args<ROIS, FIT>::type ka)
 {
     static_assert(ROIS || !FIT, "the placement is a per-row table, like the window");
+    static_assert(!HWC || (FIT && MODE == TENSOR_RGB), "interleaved: RGB, and the table form only");
     constexpr int NP = MODE == TENSOR_RGB ? 3 : 1;
     constexpr int NE = NP * RESIZE_TW * RESIZE_TH / RESIZE_THREADS;     // outputs per thread
     static_assert(RESIZE_TW == 32 && RESIZE_TH * RESIZE_TW == 2 * RESIZE_THREADS, "item -> (plane, row, column) below");
@@ -234,7 +246,7 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
                 const int p = e >> 1, i = (tid >> 5) + 8 * (e & 1), j = tid & 31;
                 if (i >= ny || j >= nx) continue;
                 const uint32_t v = tensor_elem<DT>(ka.pad[p], a.scale[p], a.bias[p]);
-                const size_t o = ((size_t)p * oh + (size_t)(oy0 + i)) * ow + (size_t)(ox0 + j);
+                const size_t o = resize_out_index<HWC, NP>(p, oy0 + i, ox0 + j, oh, ow);
                 resize_store<DT>(O, o, v);
             }
             return;
@@ -333,7 +345,7 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
         if constexpr (FIT)
             if (i < iy0 || i >= iy1 || j < jx0 || j >= jx1) c = ka.pad[p];
         const uint32_t v = tensor_elem<DT>(c, a.scale[p], a.bias[p]);
-        const size_t o = ((size_t)p * oh + (size_t)(oy0 + i)) * ow + (size_t)(ox0 + j);
+        const size_t o = resize_out_index<HWC, NP>(p, oy0 + i, ox0 + j, oh, ow);
         resize_store<DT>(O, o, v);
     }
 }
@@ -375,6 +387,20 @@ static void rois_launch(int mode, int dt, bool col, int nrois, hipStream_t st, c
 static void fit_launch(int mode, int dt, bool col, int nrois, hipStream_t st, const fit_args &a)
 {
     RESIZE_LAUNCH(true, true, nrois, a.r.ow, a.r.oh, a);
+}
+
+// the same with the elements interleaved (RGB)
+static void fit_hwc_launch(int dt, bool col, int nrois, hipStream_t st, const fit_args &a)
+{
+    const unsigned ntx = (unsigned)(a.r.ow + RESIZE_TW - 1) / RESIZE_TW, nty = (unsigned)(a.r.oh + RESIZE_TH - 1) / RESIZE_TH;
+    const dim3 grid(ntx * nty, nrois), block(RESIZE_THREADS);
+#define RESIZE_HWC_CASE(D, C)                                                                                       \
+    if (dt == D && col == C)                                                                                        \
+        hipLaunchKernelGGL((k_tensor_resize<TENSOR_RGB, D, C, true, true, true>), grid, block, 0, st, a);
+    RESIZE_HWC_CASE(TENSOR_U8, false) RESIZE_HWC_CASE(TENSOR_F16, false) RESIZE_HWC_CASE(TENSOR_BF16, false)
+    RESIZE_HWC_CASE(TENSOR_F32, false) RESIZE_HWC_CASE(TENSOR_U8, true) RESIZE_HWC_CASE(TENSOR_F16, true)
+    RESIZE_HWC_CASE(TENSOR_BF16, true) RESIZE_HWC_CASE(TENSOR_F32, true)
+#undef RESIZE_HWC_CASE
 }
 #undef RESIZE_LAUNCH
 #undef RESIZE_COL_CASE

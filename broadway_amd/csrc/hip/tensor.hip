@@ -19,6 +19,8 @@
 //   else  NG = 1 and every element is stored on its own (a row can start on
 //         any element, and a row pair's last group is 2 columns wide when
 //         cw = 2 mod 4).
+// HWC (RGB): the same elements interleaved, (ch, cw, 3): an item's
+// row is 12 * NG contiguous elements, with V16 three 16-byte stores per row.
 // Luma and chroma bytes come from aligned dwords through v_alignbyte, as in
 // crop.hip (x can be 2 mod 4, x / 2 odd, a picture can start on any byte).
 
@@ -141,13 +143,71 @@ __device__ __forceinline__ void tensor_store(const uint32_t (&c)[N], int n, floa
     }
 }
 
+// one row of an RGB item interleaved: the samples c[p][0 .. n)
+// of the three planes as elements r0 g0 b0 r1 ... at d, each under its own
+// plane's s[p], b[p].  V16: n = N = 16 / element size, the row's 3 * N elements
+// are 48 bytes and d is 16-byte aligned: three stores.  Element k of the row is
+// plane k % 3 of column k / 3, so the two halves of a 16-bit pair are of
+// different planes, and a u8 dword holds four samples of three planes.
+template <int DT, int N, bool V16>
+__device__ __forceinline__ void tensor_store_hwc(const uint32_t (&c)[3][N], int n, const float (&s)[3],
+                                                 const float (&b)[3], uint8_t *d)
+{
+    constexpr int ES = tensor_elem_size(DT);
+    if constexpr (V16) {
+        static_assert(N * ES == 16, "a lane stores 48 bytes");
+        constexpr int PER = 4 / ES;                 // elements per dword
+        uint32_t w[12];
+#pragma unroll
+        for (int j = 0; j < 12; j++) {
+            if constexpr (ES == 2) {
+                const int k0 = 2 * j, k1 = 2 * j + 1;
+                const tensor_f32x2 f = {__builtin_fmaf((float)c[k0 % 3][k0 / 3], s[k0 % 3], b[k0 % 3]),
+                                        __builtin_fmaf((float)c[k1 % 3][k1 / 3], s[k1 % 3], b[k1 % 3])};
+                if constexpr (DT == TENSOR_F16) w[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(f, tensor_f16x2));
+                else w[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(f, tensor_bf16x2));
+            } else {
+                w[j] = 0;
+#pragma unroll
+                for (int i = 0; i < PER; i++) {
+                    const int k = PER * j + i;
+                    uint32_t v = tensor_elem<DT>(c[k % 3][k / 3], s[k % 3], b[k % 3]);
+                    // (opaque, as in tensor_store: v_ashr_pk_u8_i32 keeps its destination's upper half)
+                    if constexpr (DT == TENSOR_U8) asm("" : "+v"(v));
+                    w[j] |= v << (8 * ES * i);
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            const crop_u32x4 o = {w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]};
+            __builtin_nontemporal_store(o, (crop_u32x4 *)d + q);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; i++) {
+            if (i >= n) break;
+#pragma unroll
+            for (int p = 0; p < 3; p++) {
+                const uint32_t v = tensor_elem<DT>(c[p][i], s[p], b[p]);
+                if (ES == 1) __builtin_nontemporal_store((uint8_t)v, d + 3 * i + p);
+                else if (ES == 2) __builtin_nontemporal_store((uint16_t)v, (uint16_t *)d + 3 * i + p);
+                else __builtin_nontemporal_store(v, (uint32_t *)d + 3 * i + p);
+            }
+        }
+    }
+}
+
 // grid: (ceil(items / 128) blocks of 64 threads, pictures of this launch),
 // items = the window's (row pair, 4 * NG-column group) pairs in raster order;
 // COL (RGB only): the pixels of a.col (rgba_group_px_set) instead of the
-// reference's literal constants
-template <int MODE, int DT, bool V16, bool COL = false>
+// reference's literal constants; HWC (RGB only): the picture's elements
+// interleaved, (ch, cw, 3) -- V16 then asks for rows of 3 * cw elements that
+// start on multiples of 16 bytes, which makes cw a multiple of NC as before
+template <int MODE, int DT, bool V16, bool COL = false, bool HWC = false>
 __global__ __launch_bounds__(64) void k_tensor(const tensor_args a)
 {
+    static_assert(!HWC || MODE == TENSOR_RGB, "one plane has one order");
     constexpr int ES = tensor_elem_size(DT);
     constexpr int NG = V16 ? 4 / ES : 1;            // 4-column groups per item
     constexpr int NC = 4 * NG;                      // columns per item
@@ -215,6 +275,12 @@ __global__ __launch_bounds__(64) void k_tensor(const tensor_args a)
             }
         }
         const int n = full ? NC : 2;
+        if constexpr (HWC) {
+            uint8_t *d = O + ((size_t)(2 * y2) * cw + NC * g) * (3 * ES);
+            tensor_store_hwc<DT, NC, V16>(c[0], n, a.scale, a.bias, d);
+            tensor_store_hwc<DT, NC, V16>(c[1], n, a.scale, a.bias, d + (size_t)cw * (3 * ES));
+            continue;
+        }
         uint8_t *d = O + ((size_t)(2 * y2) * cw + NC * g) * ES;
 #pragma unroll
         for (int p = 0; p < NP; p++) {
@@ -225,12 +291,22 @@ __global__ __launch_bounds__(64) void k_tensor(const tensor_args a)
 }
 
 // launch for (mode, dtype, v16); items per row pair as in the kernel; col: the
-// RGB pixels of a.col
-static void tensor_launch(int mode, int dt, bool v16, bool col, int npics, hipStream_t st, const tensor_args &a)
+// RGB pixels of a.col; hwc (RGB only): interleaved
+static void tensor_launch(int mode, int dt, bool v16, bool col, bool hwc, int npics, hipStream_t st, const tensor_args &a)
 {
     const int nc = v16 ? 16 / tensor_elem_size(dt) : 4;
     const int nf = ((a.cw + nc - 1) / nc) * (a.ch >> 1);
     const dim3 grid((nf + 127) >> 7, npics), block(64);
+#define TENSOR_HWC_CASE(D, C)                                                                            \
+    if (mode == TENSOR_RGB && dt == D && col == C && hwc) {                                               \
+        if (v16) hipLaunchKernelGGL((k_tensor<TENSOR_RGB, D, true, C, true>), grid, block, 0, st, a);     \
+        else hipLaunchKernelGGL((k_tensor<TENSOR_RGB, D, false, C, true>), grid, block, 0, st, a);        \
+        return;                                                                                           \
+    }
+    TENSOR_HWC_CASE(TENSOR_U8, false) TENSOR_HWC_CASE(TENSOR_F16, false) TENSOR_HWC_CASE(TENSOR_BF16, false)
+    TENSOR_HWC_CASE(TENSOR_F32, false) TENSOR_HWC_CASE(TENSOR_U8, true) TENSOR_HWC_CASE(TENSOR_F16, true)
+    TENSOR_HWC_CASE(TENSOR_BF16, true) TENSOR_HWC_CASE(TENSOR_F32, true)
+#undef TENSOR_HWC_CASE
 #define TENSOR_CASE(M, D)                                                                 \
     if (mode == M && dt == D) {                                                           \
         if (v16) hipLaunchKernelGGL((k_tensor<M, D, true>), grid, block, 0, st, a);       \

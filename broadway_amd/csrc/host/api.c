@@ -256,7 +256,8 @@ H264SwDecRet H264SwDecNextPictureCropped(H264SwDecInst decInst, H264SwDecPicture
 
 /* H264SwDecNextPictureTensor (desc: an h264mi_tensor_desc), resized == 1
  * ...TensorResized (an h264mi_tensor_resize_desc) and resized == 2 ...TensorFit
- * (an h264mi_tensor_fit_desc); a window with cw == 0 is the active SPS's crop
+ * (an h264mi_tensor_fit_desc) and resized == 3 ...TensorLayout (an
+ * h264mi_tensor_layout_desc); a window with cw == 0 is the active SPS's crop
  * window.  Everything the export can refuse is checked
  * before a picture is taken from the DPB. */
 static H264SwDecRet next_picture_tensor(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
@@ -264,17 +265,21 @@ static H264SwDecRet next_picture_tensor(H264SwDecInst decInst, H264SwDecPicture 
 {
     if (decInst == NULL || pOutput == NULL || d_dst == NULL || desc == NULL) return H264SWDEC_PARAM_ERR;
     DecContainer *c = (DecContainer *)decInst;
-    if (!(resized == 2 ? c->dec.be.export_tensor_fit : resized ? c->dec.be.export_tensor_resized : c->dec.be.export_tensor))
+    if (!(resized == 3 ? c->dec.be.export_tensor_layout != NULL : resized == 2 ? c->dec.be.export_tensor_fit != NULL
+          : resized ? c->dec.be.export_tensor_resized != NULL : c->dec.be.export_tensor != NULL))
         return H264SWDEC_PARAM_ERR;
-    h264mi_tensor_fit_desc f;
-    memset(&f, 0, sizeof(f));
-    if (resized == 2) f = *(const h264mi_tensor_fit_desc *)desc;
-    else if (resized) f.r = *(const h264mi_tensor_resize_desc *)desc;
-    else f.r.t = *(const h264mi_tensor_desc *)desc;
-    h264mi_tensor_resize_desc *r = &f.r;
+    h264mi_tensor_layout_desc l;
+    memset(&l, 0, sizeof(l));
+    if (resized == 3) l = *(const h264mi_tensor_layout_desc *)desc;
+    else if (resized == 2) l.f = *(const h264mi_tensor_fit_desc *)desc;
+    else if (resized) l.f.r = *(const h264mi_tensor_resize_desc *)desc;
+    else l.f.r.t = *(const h264mi_tensor_desc *)desc;
+    h264mi_tensor_fit_desc *f = &l.f;
+    h264mi_tensor_resize_desc *r = &f->r;
     h264mi_tensor_desc *t = &r->t;
     if (h264mi_tensor_colour_resolve(t->mode, 2, 0, 2, 2) < 0 ||
-        !(resized == 2 ? fit_desc_fixed_ok(&f) : resized ? resize_desc_fixed_ok(r) : tensor_desc_fixed_ok(t)) ||
+        !(resized == 3 ? layout_desc_fixed_ok(&l) : resized == 2 ? fit_desc_fixed_ok(f)
+          : resized ? resize_desc_fixed_ok(r) : tensor_desc_fixed_ok(t)) ||
         !export_aligned(d_dst, 0, export_elem_size(t->dtype)))
         return H264SWDEC_PARAM_ERR;
     if (flushBuffer) h264dec_flush(&c->dec);
@@ -285,13 +290,14 @@ static H264SwDecRet next_picture_tensor(H264SwDecInst decInst, H264SwDecPicture 
         t->x = w.x; t->y = w.y; t->cw = w.cw; t->ch = w.ch;
     }
     const int width = 16 * s->w_mbs, height = 16 * s->h_mbs;
-    if (!(resized == 2 ? fit_window_ok(&f, width, height, NULL)
+    if (!(resized == 3 ? layout_window_ok(&l, width, height) : resized == 2 ? fit_window_ok(f, width, height, NULL)
           : resized    ? resize_window_ok(r, width, height) : tensor_window_ok(t, width, height)))
         return H264SWDEC_PARAM_ERR;
     uint32_t id, idr, em;
     int failed = 0;
-    /* (a fit descriptor starts with its resize descriptor, and that with its h264mi_tensor_desc) */
-    const uint8_t *pic = h264dec_next_output_tensor(&c->dec, &id, &idr, &em, &f, resized, d_dst, hip_stream, &failed);
+    /* (a layout descriptor starts with its fit descriptor, that with its resize descriptor, and that with its
+     * h264mi_tensor_desc) */
+    const uint8_t *pic = h264dec_next_output_tensor(&c->dec, &id, &idr, &em, &l, resized, d_dst, hip_stream, &failed);
     if (failed) return H264SWDEC_PARAM_ERR;         /* (d_dst not on the decoder's GPU) */
     if (!pic) return H264SWDEC_OK;
     pOutput->pOutputPicture = (u32 *)(void *)pic;
@@ -328,6 +334,13 @@ H264SwDecRet H264SwDecNextPictureTensorFit(H264SwDecInst decInst, H264SwDecPictu
                                            const h264mi_tensor_fit_desc *desc, void *d_dst, void *hip_stream)
 {
     return next_picture_tensor(decInst, pOutput, flushBuffer, desc, 2, d_dst, hip_stream);
+}
+
+/* any of the three under a layout descriptor (include/h264mi.h) */
+H264SwDecRet H264SwDecNextPictureTensorLayout(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
+                                              const h264mi_tensor_layout_desc *desc, void *d_dst, void *hip_stream)
+{
+    return next_picture_tensor(decInst, pOutput, flushBuffer, desc, 3, d_dst, hip_stream);
 }
 
 /* the colour id of the last tensor a call above delivered; -1: none yet */
@@ -462,22 +475,28 @@ H264SwDecRet H264SwDecLastPictureAccMotionResized(H264SwDecInst decInst, const h
  * are the delivered window's: the SPS crop offset is added here, and
  * H264MI_TENSOR_COLOUR_STREAM resolves from the delivered picture's VUI and the
  * crop window's size, as the whole-picture tensor's does.  fit != NULL (desc
- * = &fit->r): every box letterboxed into the canvas. */
+ * = &fit->r): every box letterboxed into the canvas; lay != NULL (fit =
+ * &lay->f): under its layout, through the backend's member for that. */
 static H264SwDecRet last_picture_rois(H264SwDecInst decInst, const h264mi_tensor_resize_desc *desc,
-                                      const h264mi_tensor_fit_desc *fit, const h264mi_roi *rois, u32 nrois, void *d_dst,
-                                      void *hip_stream)
+                                      const h264mi_tensor_fit_desc *fit, const h264mi_tensor_layout_desc *lay,
+                                      const h264mi_roi *rois, u32 nrois, void *d_dst, void *hip_stream)
 {
     if (decInst == NULL || desc == NULL || rois == NULL || d_dst == NULL) return H264SWDEC_PARAM_ERR;
     DecContainer *c = (DecContainer *)decInst;
-    if (!(fit ? c->dec.be.export_tensor_rois_fit : c->dec.be.export_tensor_rois)) return H264SWDEC_PARAM_ERR;
+    if (!(lay ? c->dec.be.export_tensor_layout != NULL : fit ? c->dec.be.export_tensor_rois_fit != NULL
+                                                            : c->dec.be.export_tensor_rois != NULL))
+        return H264SWDEC_PARAM_ERR;
     /* (without fit: desc stretched, which has rois_ok's rules) */
-    h264mi_tensor_fit_desc mf;
-    memset(&mf, 0, sizeof(mf));
-    if (fit) mf = *fit;
-    else mf.r = *desc;
-    h264mi_tensor_resize_desc *m = &mf.r;
+    h264mi_tensor_layout_desc ml;
+    memset(&ml, 0, sizeof(ml));
+    if (lay) ml = *lay;
+    else if (fit) ml.f = *fit;
+    else ml.f.r = *desc;
+    h264mi_tensor_fit_desc *mf = &ml.f;
+    h264mi_tensor_resize_desc *m = &mf->r;
     if (nrois < 1 || nrois > 0x7FFFFFFF / sizeof(h264mi_roi) || h264mi_tensor_colour_resolve(m->t.mode, 2, 0, 2, 2) < 0 ||
-        !fit_desc_fixed_ok(&mf) || (m->t.x | m->t.y | m->t.cw | m->t.ch) ||
+        !(lay ? layout_desc_fixed_ok(&ml) && !layout_unresized(&ml) : fit_desc_fixed_ok(mf)) ||
+        (m->t.x | m->t.y | m->t.cw | m->t.ch) ||
         !export_aligned(d_dst, 0, export_elem_size(m->t.dtype)))
         return H264SWDEC_PARAM_ERR;
     for (u32 k = 0; k < nrois; k++)
@@ -494,11 +513,13 @@ static H264SwDecRet last_picture_rois(H264SwDecInst decInst, const h264mi_tensor
              b[k].ch <= w.ch - b[k].y;
         if (ok) { b[k].x += w.x; b[k].y += w.y; }
     }
-    ok = ok && rois_fit_ok(&mf, b, (int)nrois, 1, 16 * s->w_mbs, 16 * s->h_mbs);
+    ok = ok && rois_fit_ok(mf, b, (int)nrois, 1, 16 * s->w_mbs, 16 * s->h_mbs);
     const int colour = h264mi_tensor_colour_resolve(m->t.mode, c->dec.last_out_vui_matrix, c->dec.last_out_vui_full, w.cw, w.ch);
     if (H264MI_TENSOR_LAYOUT(m->t.mode) == H264MI_TENSOR_RGB) m->t.mode = H264MI_TENSOR_MODE(H264MI_TENSOR_RGB, colour, 0);
     /* (a failure of the export itself: d_dst not on the decoder's GPU) */
-    ok = ok && !(fit ? c->dec.be.export_tensor_rois_fit(c->dec.be.ctx, c->dec.last_out_slot1 - 1, &mf, b, (int)nrois, d_dst,
+    ok = ok && !(lay ? c->dec.be.export_tensor_layout(c->dec.be.ctx, c->dec.last_out_slot1 - 1, &ml, b, (int)nrois, d_dst,
+                                                      hip_stream)
+                 : fit ? c->dec.be.export_tensor_rois_fit(c->dec.be.ctx, c->dec.last_out_slot1 - 1, mf, b, (int)nrois, d_dst,
                                                         hip_stream)
                      : c->dec.be.export_tensor_rois(c->dec.be.ctx, c->dec.last_out_slot1 - 1, m, b, (int)nrois, d_dst,
                                                     hip_stream));
@@ -511,14 +532,22 @@ static H264SwDecRet last_picture_rois(H264SwDecInst decInst, const h264mi_tensor
 H264SwDecRet H264SwDecLastPictureTensorRois(H264SwDecInst decInst, const h264mi_tensor_resize_desc *desc,
                                             const h264mi_roi *rois, u32 nrois, void *d_dst, void *hip_stream)
 {
-    return last_picture_rois(decInst, desc, NULL, rois, nrois, d_dst, hip_stream);
+    return last_picture_rois(decInst, desc, NULL, NULL, rois, nrois, d_dst, hip_stream);
 }
 
 /* the same, every box letterboxed into the canvas (include/h264mi.h) */
 H264SwDecRet H264SwDecLastPictureTensorRoisFit(H264SwDecInst decInst, const h264mi_tensor_fit_desc *desc,
                                                const h264mi_roi *rois, u32 nrois, void *d_dst, void *hip_stream)
 {
-    return last_picture_rois(decInst, desc ? &desc->r : NULL, desc, rois, nrois, d_dst, hip_stream);
+    return last_picture_rois(decInst, desc ? &desc->r : NULL, desc, NULL, rois, nrois, d_dst, hip_stream);
+}
+
+/* the same under a layout descriptor (include/h264mi.h) */
+H264SwDecRet H264SwDecLastPictureTensorRoisLayout(H264SwDecInst decInst, const h264mi_tensor_layout_desc *desc,
+                                                  const h264mi_roi *rois, u32 nrois, void *d_dst, void *hip_stream)
+{
+    return last_picture_rois(decInst, desc ? &desc->f.r : NULL, desc ? &desc->f : NULL, desc, rois, nrois, d_dst,
+                             hip_stream);
 }
 
 H264SwDecRet H264SwDecGetTiming(H264SwDecInst decInst, double *parse_s, double *submit_s, double *wait_s,

@@ -658,7 +658,7 @@ const uint8_t *h264dec_next_output_tensor(H264Dec *d, uint32_t *pic_id, uint32_t
                                           const void *desc, int resized, void *d_dst, void *hip_stream, int *failed)
 {
     TensorOut t = {desc, d_dst, hip_stream, 0, resized};
-    /* (a resize or fit descriptor starts with its h264mi_tensor_desc) */
+    /* (a resize, fit or layout descriptor starts with its h264mi_tensor_desc) */
     const int mode_ok = desc && h264mi_tensor_colour_resolve(((const h264mi_tensor_desc *)desc)->mode, 2, 0, 2, 2) >= 0;
     const uint8_t *r = d_dst && mode_ok ? next_output(d, pic_id, is_idr, err_mbs, NULL, NULL, 0, &t) : NULL;
     if (failed) *failed = t.failed;
@@ -672,8 +672,9 @@ static const uint8_t *next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr
                                   uint8_t *crop, int crop_rgba, TensorOut *tensor)
 {
     if (rgba && !d->be.read_rgba) return NULL;
-    if (tensor && !(tensor->resized == 2 ? d->be.export_tensor_fit
-                    : tensor->resized ? d->be.export_tensor_resized : d->be.export_tensor))
+    if (tensor && !(tensor->resized == 3 ? d->be.export_tensor_layout != NULL
+                    : tensor->resized == 2 ? d->be.export_tensor_fit != NULL
+                    : tensor->resized ? d->be.export_tensor_resized != NULL : d->be.export_tensor != NULL))
         return NULL;
     const Sps *sps = crop ? h264dec_active_sps(d) : NULL;
     if (crop && (!d->be.read_crop || !sps)) return NULL;
@@ -695,17 +696,20 @@ static const uint8_t *next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr
     int rr;
     if (tensor) {
         /* the backend gets the colour id of this picture's own SPS in place of STREAM */
-        h264mi_tensor_fit_desc f;
-        memset(&f, 0, sizeof(f));
-        if (tensor->resized == 2) f = *(const h264mi_tensor_fit_desc *)tensor->desc;
-        else if (tensor->resized) f.r = *(const h264mi_tensor_resize_desc *)tensor->desc;
-        else f.r.t = *(const h264mi_tensor_desc *)tensor->desc;
-        h264mi_tensor_desc *t = &f.r.t;
+        h264mi_tensor_layout_desc l;
+        memset(&l, 0, sizeof(l));
+        if (tensor->resized == 3) l = *(const h264mi_tensor_layout_desc *)tensor->desc;
+        else if (tensor->resized == 2) l.f = *(const h264mi_tensor_fit_desc *)tensor->desc;
+        else if (tensor->resized) l.f.r = *(const h264mi_tensor_resize_desc *)tensor->desc;
+        else l.f.r.t = *(const h264mi_tensor_desc *)tensor->desc;
+        h264mi_tensor_fit_desc *f = &l.f;
+        h264mi_tensor_desc *t = &f->r.t;
         /* (by size: the export window's, never a canvas's) */
         const int colour = h264mi_tensor_colour_resolve(t->mode, o->vui_matrix, o->vui_full, t->cw, t->ch);
         if (H264MI_TENSOR_LAYOUT(t->mode) == H264MI_TENSOR_RGB) t->mode = H264MI_TENSOR_MODE(H264MI_TENSOR_RGB, colour, 0);
-        rr = tensor->resized == 2 ? d->be.export_tensor_fit(d->be.ctx, o->slot, &f, tensor->d_dst, tensor->hip_stream)
-             : tensor->resized    ? d->be.export_tensor_resized(d->be.ctx, o->slot, &f.r, tensor->d_dst, tensor->hip_stream)
+        rr = tensor->resized == 3 ? d->be.export_tensor_layout(d->be.ctx, o->slot, &l, NULL, 0, tensor->d_dst, tensor->hip_stream)
+             : tensor->resized == 2 ? d->be.export_tensor_fit(d->be.ctx, o->slot, f, tensor->d_dst, tensor->hip_stream)
+             : tensor->resized    ? d->be.export_tensor_resized(d->be.ctx, o->slot, &f->r, tensor->d_dst, tensor->hip_stream)
                                   : d->be.export_tensor(d->be.ctx, o->slot, t, tensor->d_dst, tensor->hip_stream);
         tensor->failed = rr < 0;
         if (rr >= 0) d->last_tensor_colour1 = colour + 1;

@@ -86,6 +86,12 @@ typedef struct H264Backend {
     int  (*export_tensor_fit)(void *ctx, int slot, const void *desc, void *d_dst, void *hip_stream);
     int  (*export_tensor_rois_fit)(void *ctx, int slot, const void *desc, const void *rois, int nrois, void *d_dst,
                                    void *hip_stream);
+    /* optional: the five exports above under a layout (desc: a checked
+     * h264mi_tensor_layout_desc): rois == NULL, nrois == 0 is desc's window
+     * with export_tensor's returns, else the list form; NULL when the backend
+     * cannot */
+    int  (*export_tensor_layout)(void *ctx, int slot, const void *desc, const void *rois, int nrois, void *d_dst,
+                                 void *hip_stream);
     /* optional: host memory for the output frames (pinned by the HIP
      * backend, so each picture's D2H copy runs at DMA speed); NULL: malloc */
     void *(*host_alloc)(void *ctx, size_t bytes);
@@ -209,7 +215,8 @@ const uint8_t *h264dec_next_output_crop(H264Dec *d, uint32_t *pic_id, uint32_t *
 /* the same, the picture exported by the backend's export_tensor (desc: an
  * h264mi_tensor_desc), with resized == 1 export_tensor_resized (an
  * h264mi_tensor_resize_desc) or with resized == 2 export_tensor_fit (an
- * h264mi_tensor_fit_desc); returns d_dst, a device pointer; *failed = 1
+ * h264mi_tensor_fit_desc) or with resized == 3 export_tensor_layout (an
+ * h264mi_tensor_layout_desc); returns d_dst, a device pointer; *failed = 1
  * when the export of the picture taken from the DPB failed */
 const uint8_t *h264dec_next_output_tensor(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
                                           const void *desc, int resized, void *d_dst, void *hip_stream, int *failed);

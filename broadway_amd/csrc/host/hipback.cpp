@@ -698,6 +698,37 @@ static int hb_export_tensor_rois_fit(void *vctx, int slot, const void *desc, con
     return hb_export(vctx, slot, engine_export_rois_fit, &c, d_dst, hip_stream);
 }
 
+// the pixel exports under a layout descriptor (a member of its own): the
+// single-window form has export_tensor's returns, the list form packs box r's
+// elements behind box r - 1's like export_tensor_rois
+extern "C" int h264mi_engine_export_tensor_layout(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                                  const h264mi_tensor_layout_desc *desc, const h264mi_roi *rois,
+                                                  int nrois, void *d_out, size_t out_stride,
+                                                  void *hip_stream) __attribute__((weak));
+struct LayoutCall {
+    const h264mi_tensor_layout_desc *desc;
+    const h264mi_roi *rois;
+    int nrois;
+};
+
+static int engine_export_layout(h264mi_engine *e, int n, const int *streams, const int *slots, const LayoutCall *c,
+                                void *d_out, size_t, void *hip_stream)
+{
+    const h264mi_tensor_resize_desc &r = c->desc->f.r;
+    const size_t planes = H264MI_TENSOR_LAYOUT(r.t.mode) == H264MI_TENSOR_GRAY ? 1 : 3;
+    return h264mi_engine_export_tensor_layout(e, n, streams, slots, c->desc, c->rois, c->nrois, d_out,
+                                              c->rois ? planes * r.oh * r.ow * export_elem_size(r.t.dtype) : 0,
+                                              hip_stream);
+}
+
+static int hb_export_tensor_layout(void *vctx, int slot, const void *desc, const void *rois, int nrois, void *d_dst,
+                                   void *hip_stream)
+{
+    const LayoutCall c = {(const h264mi_tensor_layout_desc *)desc, (const h264mi_roi *)rois, nrois};
+    if (hb_export(vctx, slot, engine_export_layout, &c, d_dst, hip_stream)) return -1;
+    return rois ? 0 : slot_flagged((HipBackendCtx *)vctx, slot, false);
+}
+
 // Pinned host blocks (decoder output frames) kept after free for the next
 // decoder instance: pinning tens of MB per instance is a large share of a
 // short stream's host time.  Exact-size reuse, at most H264MI_HOST_POOL_MB
@@ -849,6 +880,7 @@ extern "C" H264Backend h264mi_hip_backend_create(int device)
     be.export_tensor_rois = h264mi_engine_export_tensor_rois ? hb_export_tensor_rois : NULL;
     be.export_tensor_fit = h264mi_engine_export_tensor_fit ? hb_export_tensor_fit : NULL;
     be.export_tensor_rois_fit = h264mi_engine_export_tensor_rois_fit ? hb_export_tensor_rois_fit : NULL;
+    be.export_tensor_layout = h264mi_engine_export_tensor_layout ? hb_export_tensor_layout : NULL;
     be.host_alloc = hb_host_alloc;
     be.host_free = hb_host_free;
     be.records_wait = hb_records_wait;

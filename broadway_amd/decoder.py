@@ -172,11 +172,13 @@ class Decoder:
                 raise ValueError("tensor: not combinable with rgb or crop (mode='rgb' and the SPS window are part of it)")
             opts = {} if self._tensor is True else dict(self._tensor)
             unknown = set(opts) - {"dtype", "mode", "mean", "std", "scale", "bias", "size", "colour", "unspecified",
-                                   "fit", "pad"}
+                                   "fit", "pad", "layout"}
             if unknown:
                 raise ValueError(f"tensor: unknown keys {sorted(unknown)}")
-            from .engine import fit_desc, tensor_desc       # (imports torch)
+            from .engine import fit_desc, layout_desc, tensor_desc, tensor_layout       # (imports torch)
             fit, pad = opts.pop("fit", None), opts.pop("pad", None)
+            self._layout = opts.pop("layout", "nchw")
+            tensor_layout(self._layout)
             self._tensor = tensor_desc(None, stream_ok=True, **opts)
             self._resized = opts.get("size") is not None
             self._fitted = fit is not None or pad is not None
@@ -186,6 +188,8 @@ class Decoder:
                 desc, planes, dtype = self._tensor
                 self._tensor = (fit_desc(desc, planes, "letterbox" if fit is None else fit, 114 if pad is None else pad),
                                 planes, dtype)
+            # "nhwc": the same descriptor under a layout, through the one call that takes it
+            self._tensor_layout = layout_desc(self._tensor[0], self._layout) if self._layout != "nchw" else None
             self._device = int(os.environ.get("H264MI_DEVICE") or 0)     # the GPU H264SwDecInit takes (api.c)
         self._fields = {}           # option -> (descriptor, channels or planes, torch dtype) of the fields asked for
         for name, f in _FIELDS.items():
@@ -259,9 +263,12 @@ class Decoder:
                 if self._tensor is not None:
                     desc, planes, dtype = self._tensor
                     w, h = self._out_size()
-                    out, st = self._device_empty((planes, h, w), dtype)
-                    nxt = getattr(L, "H264SwDecNextPictureTensorFit" if self._fitted else
+                    out, st = self._device_empty((planes, h, w), dtype, self._layout)
+                    nxt = getattr(L, "H264SwDecNextPictureTensorLayout" if self._tensor_layout is not None else
+                                  "H264SwDecNextPictureTensorFit" if self._fitted else
                                   "H264SwDecNextPictureTensorResized" if self._resized else "H264SwDecNextPictureTensor", None)
+                    if self._tensor_layout is not None:
+                        desc = self._tensor_layout
                     ret = nxt(self._inst, C.byref(self._pic), 0, C.byref(desc), out.data_ptr(), st) if nxt else \
                         _lib.H264SWDEC_PARAM_ERR
                     if ret == _lib.H264SWDEC_PARAM_ERR:
@@ -309,11 +316,14 @@ class Decoder:
             return i.cropParams.cropOutWidth, i.cropParams.cropOutHeight
         return i.picWidth, i.picHeight
 
-    def _device_empty(self, shape, dtype):
+    def _device_empty(self, shape, dtype, layout="nchw"):
         """(a new tensor on the decoder's GPU, torch's current stream there as a HIP handle)."""
         import torch
         dev = torch.device("cuda", self._device)
         with torch.cuda.device(dev):
+            if layout != "nchw":
+                from .engine import empty_layout
+                return empty_layout(shape, dtype, dev, layout), torch.cuda.current_stream(dev).cuda_stream
             return torch.empty(shape, dtype=dtype, device=dev), torch.cuda.current_stream(dev).cuda_stream
 
     def _crop_window(self):
@@ -356,7 +366,7 @@ class Decoder:
         self.onPictureDecoded(buf, w, h, infos)
 
     def rois(self, boxes, size, mode="rgb", dtype=None, mean=None, std=None, scale=None, bias=None, colour=None,
-             unspecified=None, fit=None, pad=None):
+             unspecified=None, fit=None, pad=None, layout="nchw"):
         """Boxes of the delivered picture as one new ``(K, planes, oh, ow)``
         torch tensor on the decoder's GPU, on torch's current stream
         (``H264SwDecLastPictureTensorRois``): ``boxes`` = [(x, y, cw, ch), ...]
@@ -370,8 +380,12 @@ class Decoder:
         ``tensor_colour`` names it.  With ``fit`` ("letterbox", "topleft" or
         "stretch") and ``pad`` every box is fitted into ``size`` with its
         aspect ratio kept (``H264SwDecLastPictureTensorRoisFit``), as for
-        ``Engine.to_tensor``.  ValueError for a bad argument,
+        ``Engine.to_tensor``.  ``layout="nhwc"``: the same values stored
+        channels-last (``H264SwDecLastPictureTensorRoisLayout``), the result
+        of the usual shape with channels_last strides.  ValueError for a bad argument,
         RuntimeError before a picture was delivered."""
+        from .engine import layout_desc, tensor_layout
+        nhwc = tensor_layout(layout) != 0
         _, _, cw, ch = self._crop_window()
         desc, arr, planes, dtype = rois_args(boxes, size, cw, ch, mode=mode, dtype=dtype, mean=mean, std=std, scale=scale,
                                              bias=bias, colour=colour, unspecified=unspecified, fit=fit, pad=pad)
@@ -379,8 +393,11 @@ class Decoder:
             self._device = int(os.environ.get("H264MI_DEVICE") or 0)
         fitted = fit is not None or pad is not None
         r = desc.r if fitted else desc
-        out, st = self._device_empty((len(arr), planes, r.oh, r.ow), dtype)
-        last = getattr(self._L, "H264SwDecLastPictureTensorRoisFit" if fitted else "H264SwDecLastPictureTensorRois", None)
+        out, st = self._device_empty((len(arr), planes, r.oh, r.ow), dtype, layout)
+        last = getattr(self._L, "H264SwDecLastPictureTensorRoisLayout" if nhwc else
+                       "H264SwDecLastPictureTensorRoisFit" if fitted else "H264SwDecLastPictureTensorRois", None)
+        if nhwc:
+            desc = layout_desc(desc, layout)
         ret = last(self._inst, C.byref(desc), arr, len(arr), out.data_ptr(), st) if last else _lib.H264SWDEC_PARAM_ERR
         if ret == _lib.H264SWDEC_OK:
             raise RuntimeError("rois: no picture has been delivered since the last decode")

@@ -84,16 +84,72 @@ def _field_resized(resized, built, size):
     return d, n, dtype
 
 
+def tensor_layout(layout) -> int:
+    """The ``h264mi_tensor_layout_desc.layout`` of ``layout``: "nchw" (planar,
+    the default everywhere) or "nhwc" (interleaved: torch's channels_last).
+    ValueError for anything else."""
+    if not isinstance(layout, str) or layout not in _lib.TENSOR_LAYOUTS:
+        raise ValueError(f"layout {layout!r}: one of {sorted(_lib.TENSOR_LAYOUTS)}")
+    return _lib.TENSOR_LAYOUTS[layout]
+
+
+def layout_desc(desc, layout):
+    """The ``_lib.TensorLayoutDesc`` of a pixel export's descriptor -- a
+    ``_lib.TensorDesc`` (no size: the unresized export), ``TensorResizeDesc``
+    (a stretch) or ``TensorFitDesc`` -- under ``layout`` (``tensor_layout``)."""
+    d = _lib.TensorLayoutDesc()
+    d.layout = tensor_layout(layout)
+    if isinstance(desc, _lib.TensorFitDesc):
+        d.f = desc
+    elif isinstance(desc, _lib.TensorResizeDesc):
+        d.f.r = desc
+    elif isinstance(desc, _lib.TensorDesc):
+        d.f.r.t = desc
+    else:
+        raise ValueError(f"layout_desc: {type(desc).__name__} is no pixel export's descriptor")
+    return d
+
+
+def empty_layout(shape, dtype, device, layout="nchw"):
+    """A new tensor of the logical ``shape`` = (n, planes, rows, cols), or
+    (planes, rows, cols), in the memory order of ``layout``: "nhwc" is
+    ``torch.empty((n, rows, cols, planes)).permute(0, 3, 1, 2)`` -- the usual
+    shape with channels-last strides."""
+    import torch
+    if not tensor_layout(layout):
+        return torch.empty(shape, dtype=dtype, device=device)
+    if len(shape) == 3:
+        return torch.empty((shape[1], shape[2], shape[0]), dtype=dtype, device=device).permute(2, 0, 1)
+    return torch.empty((shape[0], shape[2], shape[3], shape[1]), dtype=dtype, device=device).permute(0, 3, 1, 2)
+
+
+def check_out(out, shape, dtype, device, layout="nchw"):
+    """``out=`` of an export against the result's logical ``shape`` = (n,
+    planes, rows, cols), dtype, device and ``layout``: "nchw" asks for a
+    contiguous tensor, "nhwc" for one whose ``permute(0, 2, 3, 1)`` is
+    contiguous.  ValueError otherwise, before the library is called."""
+    dense = out.permute(0, 2, 3, 1) if tensor_layout(layout) and out.dim() == 4 else out
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device or not dense.is_contiguous():
+        raise ValueError(f"out: a {dtype} tensor of shape {tuple(shape)} on {device}, {layout!r}-contiguous "
+                         f"(got {out.dtype} {tuple(out.shape)} with strides {tuple(out.stride())} on {out.device})")
+
+
 def tensor_desc(window, mode="rgb", dtype=None, scale=None, bias=None, mean=None, std=None, size=None, colour=None,
-                unspecified=None, stream_ok=False):
+                unspecified=None, stream_ok=False, layout=None):
     """(``_lib.TensorDesc``, planes, torch dtype) of a tensor export
     (Engine.to_tensor, Decoder's ``tensor`` option); window = (x, y, cw, ch),
     or None for the decoder's SPS crop window (cw = 0 in the descriptor).
     With ``size`` = (oh, ow), each 1..16384, the descriptor is a
     ``_lib.TensorResizeDesc`` of the resized export (its ``t`` is the one
     above).  ``colour``: the colour set of the R, G, B samples
-    (``tensor_colour_bits``; None: the reference's BT.601 limited range)."""
+    (``tensor_colour_bits``; None: the reference's BT.601 limited range).
+    ``layout`` "nchw" or "nhwc" (not None): the descriptor is the
+    ``_lib.TensorLayoutDesc`` (``layout_desc``) of the one above."""
     import torch
+    if layout is not None:
+        tensor_layout(layout)
+        d, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std, size, colour, unspecified, stream_ok)
+        return layout_desc(d, layout), planes, dtype
     if size is not None:
         oh, ow = _resize_size(size)
         t, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std, None, colour, unspecified, stream_ok)
@@ -176,12 +232,16 @@ def unletterbox(boxes, window, size, fit: str = "letterbox"):
             for k, x0, y0, x1, y1 in boxes]
 
 
-def fit_desc(desc, planes, fit="letterbox", pad=114):
+def fit_desc(desc, planes, fit="letterbox", pad=114, layout=None):
     """The ``_lib.TensorFitDesc`` of the resize descriptor ``desc`` letterboxed
     (Engine.to_tensor(fit=), the Decoder's ``tensor`` option, Decoder.rois):
     ``fit`` "letterbox", "topleft" or "stretch"; ``pad`` one uint8 sample for
     every plane or one per plane, in the tensor's own domain (R, G, B or
-    luma).  ValueError for anything else."""
+    luma).  With ``layout`` (not None): its ``_lib.TensorLayoutDesc``.
+    ValueError for anything else."""
+    if layout is not None:
+        tensor_layout(layout)
+        return layout_desc(fit_desc(desc, planes, fit, pad), layout)
     if fit not in _lib.TENSOR_FIT:
         raise ValueError(f"fit {fit!r}: one of {sorted(_lib.TENSOR_FIT)}")
     try:
@@ -218,7 +278,7 @@ def snap_rois(boxes, width: int, height: int):
 
 
 def rois_desc(rois, size, npics, width, height, mode="rgb", dtype=None, scale=None, bias=None, mean=None, std=None,
-              colour=None, unspecified=None, stream_ok=False, fit=None, pad=None):
+              colour=None, unspecified=None, stream_ok=False, fit=None, pad=None, layout=None):
     """(``_lib.TensorResizeDesc`` with a zero window, ``_lib.Roi`` array, planes,
     torch dtype) of a region-of-interest export (Engine.to_tensor(rois=),
     Decoder.rois): ``rois`` = [(k, x, y, cw, ch), ...] over ``npics`` pictures
@@ -228,7 +288,13 @@ def rois_desc(rois, size, npics, width, height, mode="rgb", dtype=None, scale=No
     and axis.  With ``fit`` (or ``pad``) the descriptor is the
     ``_lib.TensorFitDesc`` of the letterboxed export (``fit_desc``): every box
     gets its own fit into ``size``, and the 32 samples per output are judged
-    against its content size.  ValueError otherwise."""
+    against its content size.  With ``layout`` (not None) the descriptor is
+    the ``_lib.TensorLayoutDesc`` of that one.  ValueError otherwise."""
+    if layout is not None:
+        tensor_layout(layout)
+        desc, arr, planes, dtype = rois_desc(rois, size, npics, width, height, mode, dtype, scale, bias, mean, std,
+                                             colour, unspecified, stream_ok, fit, pad)
+        return layout_desc(desc, layout), arr, planes, dtype
     if size is None:
         raise ValueError("rois: goes with size=(oh, ow)")
     desc, planes, dtype = tensor_desc((0, 0, 0, 0), mode, dtype, scale, bias, mean, std, size, colour, unspecified,
@@ -577,12 +643,19 @@ class Engine:
             raise ValueError("streams and slots name the same, non-zero number of pictures")
         return n, (C.c_int * n)(*streams), (C.c_int * n)(*slots)
 
-    def _out(self, shape, dtype, out, stream):
+    def _out(self, shape, dtype, out, stream, layout="nchw"):
         """(out, HIP stream handle) of an export: ``out``, checked, or a new
-        ``torch.empty``; ``stream`` or torch's current stream of the device."""
+        ``torch.empty`` (``layout`` "nhwc": ``empty_layout`` / ``check_out``);
+        ``stream`` or torch's current stream of the device."""
         import torch
         dev = torch.device("cuda", self.device)
-        if out is None:
+        if layout != "nchw":
+            if out is None:
+                with torch.cuda.device(self.device):
+                    out = empty_layout(shape, dtype, dev, layout)
+            else:
+                check_out(out, shape, dtype, dev, layout)
+        elif out is None:
             with torch.cuda.device(self.device):
                 out = torch.empty(shape, dtype=dtype, device=dev)
         elif tuple(out.shape) != shape or out.dtype != dtype or out.device != dev or not out.is_contiguous():
@@ -618,7 +691,7 @@ class Engine:
 
     def to_tensor(self, streams: Sequence[int], slots: Sequence[int], window=None, mode: str = "rgb", dtype=None,
                   scale=None, bias=None, mean=None, std=None, out=None, stream=None, size=None, colour=None,
-                  rois=None, fit=None, pad=None):
+                  rois=None, fit=None, pad=None, layout="nchw"):
         """The slots (streams[k], slots[k]) as one ``(n, planes, ch, cw)``
         torch tensor on ``cuda:{self.device}``, built on the GPU and never
         copied to the host: planes R, G, B (``mode="rgb"``, the values of
@@ -657,6 +730,14 @@ class Engine:
         the one launch.  "stretch" gives the bytes of ``size``
         alone.  ``engine.unletterbox`` maps a detector's boxes back.
 
+        ``layout`` = "nhwc" (every form above): the same values
+        stored channels-last by the export's own kernel -- the result has the
+        usual shape ``(n, planes, rows, cols)`` with the strides of
+        ``torch.channels_last`` (``empty_layout``), so model code is unchanged
+        and ``t.permute(0, 2, 3, 1)`` is the contiguous HWC view; ``out`` then
+        is such a tensor (``check_out``).  "nchw", the default, is everything
+        above, untouched.  With ``mode="gray"`` the two are the same bytes.
+
         The export is ordered on ``stream`` (a torch.cuda.Stream; default:
         torch's current stream of the device): it starts after the work queued
         there and after every launch queued on the engine, later work on
@@ -666,6 +747,7 @@ class Engine:
         new ``torch.empty``.  The result is an ordinary torch tensor, so DLPack
         consumers (``torch.utils.dlpack`` / ``__dlpack__``) need nothing further."""
         n, c_streams, c_slots = self._pictures(streams, slots)
+        nhwc = tensor_layout(layout) != 0
         fitted = fit is not None or pad is not None
         if fitted and size is None:
             raise ValueError("fit and pad go with size=(oh, ow), the canvas")
@@ -676,6 +758,9 @@ class Engine:
                                                    bias, mean, std, colour, fit=fit, pad=pad)
             name = "h264mi_engine_export_tensor_rois_fit" if fitted else "h264mi_engine_export_tensor_rois"
             oh, ow = (desc.r.oh, desc.r.ow) if fitted else (desc.oh, desc.ow)
+            if nhwc:
+                return self._export_layout(n, c_streams, c_slots, desc, boxes, (len(boxes), planes, oh, ow), dtype, out,
+                                           stream, layout)
             out, st = self._out((len(boxes), planes, oh, ow), dtype, out, stream)
             if not hasattr(self._L, name) or \
                     getattr(self._L, name)(self._h, n, c_streams, c_slots, C.byref(desc), boxes, len(boxes),
@@ -687,6 +772,9 @@ class Engine:
         desc, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std, size, colour)
         if fitted:
             fd = fit_desc(desc, planes, "letterbox" if fit is None else fit, 114 if pad is None else pad)
+            if nhwc:
+                return self._export_layout(n, c_streams, c_slots, fd, None, (n, planes, desc.oh, desc.ow), dtype, out,
+                                           stream, layout)
             out, st = self._out((n, planes, desc.oh, desc.ow), dtype, out, stream)
             if not hasattr(self._L, "h264mi_engine_export_tensor_fit") or \
                     self._L.h264mi_engine_export_tensor_fit(self._h, n, c_streams, c_slots, C.byref(fd), out.data_ptr(),
@@ -696,11 +784,26 @@ class Engine:
         shape = (n, planes, desc.ch, desc.cw) if size is None else (n, planes, desc.oh, desc.ow)
         if out is None and min(shape) < 1:
             raise ValueError(f"window {tuple(window)}")
+        if nhwc:
+            return self._export_layout(n, c_streams, c_slots, desc, None, shape, dtype, out, stream, layout)
         out, st = self._out(shape, dtype, out, stream)
         export = self._L.h264mi_engine_export_tensor if size is None else self._L.h264mi_engine_export_tensor_resized
         if export(self._h, n, c_streams, c_slots, C.byref(desc), out.data_ptr(),
                   planes * shape[2] * shape[3] * out.element_size(), st) != 0:
             raise RuntimeError(f"{export.__name__} failed (stream, slot, window or size out of range?)")
+        return out
+
+    def _export_layout(self, n, c_streams, c_slots, desc, boxes, shape, dtype, out, stream, layout):
+        """to_tensor's export of ``desc`` (any pixel export's descriptor; with
+        ``boxes``, a ``_lib.Roi`` array, the list form) under ``layout`` through
+        h264mi_engine_export_tensor_layout."""
+        out, st = self._out(shape, dtype, out, stream, layout)
+        ld = layout_desc(desc, layout)
+        if not hasattr(self._L, "h264mi_engine_export_tensor_layout") or \
+                self._L.h264mi_engine_export_tensor_layout(self._h, n, c_streams, c_slots, C.byref(ld), boxes,
+                                                           len(boxes) if boxes is not None else 0, out.data_ptr(),
+                                                           shape[1] * shape[2] * shape[3] * out.element_size(), st) != 0:
+            raise RuntimeError("h264mi_engine_export_tensor_layout failed (stream, slot, window or size out of range?)")
         return out
 
     def keep_records(self, on: bool = True) -> None:

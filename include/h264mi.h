@@ -273,6 +273,30 @@ H264SwDecRet H264SwDecNextPictureTensorFit(H264SwDecInst decInst, H264SwDecPictu
                                            const h264mi_tensor_fit_desc *desc, void *d_dst, void *hip_stream);
 H264SwDecRet H264SwDecLastPictureTensorRoisFit(H264SwDecInst decInst, const h264mi_tensor_fit_desc *desc,
                                                const h264mi_roi *rois, u32 nrois, void *d_dst, void *hip_stream);
+/* The element order of an RGB tensor: one descriptor over all
+ * four pixel exports above, and a layout.  f.r.ow == 0 && f.r.oh == 0 is the
+ * unresized tensor of the window f.r.t (then fit is H264MI_FIT_STRETCH, pad
+ * all zero and filter 0); otherwise `f` is the fit descriptor with its own
+ * rules, H264MI_FIT_STRETCH being the resized tensor.  A picture or box is the
+ * same planes * rows * cols elements at the same place as in the call it
+ * mirrors, with the same values:
+ *   H264MI_LAYOUT_PLANAR        element (p, i, j) at index (p * rows + i) * cols + j:
+ *                               that call's bytes;
+ *   H264MI_LAYOUT_INTERLEAVED   element (p, i, j) at index (i * cols + j) * planes + p
+ *                               (channels-last: HWC per picture, NHWC over a batch).
+ * With GRAY both are the same bytes.  Other layout values are refused. */
+enum { H264MI_LAYOUT_PLANAR = 0, H264MI_LAYOUT_INTERLEAVED = 1 };
+typedef struct { h264mi_tensor_fit_desc f; int layout; } h264mi_tensor_layout_desc;
+/* NextPictureTensor / ...Resized / ...Fit and LastPictureTensorRois / ...RoisFit
+ * under a layout descriptor (not NULL): desc->f.r.t.cw == 0 takes the active
+ * SPS's crop window; with boxes the window is reserved (all zero) and a size
+ * is required.  H264MI_TENSOR_COLOUR_STREAM resolves as for those calls and
+ * H264SwDecLastTensorColour reports it; a bad descriptor is refused before a
+ * picture is taken.  Return codes are those of the calls these mirror. */
+H264SwDecRet H264SwDecNextPictureTensorLayout(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
+                                              const h264mi_tensor_layout_desc *desc, void *d_dst, void *hip_stream);
+H264SwDecRet H264SwDecLastPictureTensorRoisLayout(H264SwDecInst decInst, const h264mi_tensor_layout_desc *desc,
+                                                  const h264mi_roi *rois, u32 nrois, void *d_dst, void *hip_stream);
 /* Motion vectors and MB side information as a device tensor (mbinfo.hip, DESIGN
  * 3.5d; elsewhere: ffmpeg's export_mvs).  The field lives on the luma 4x4-block
  * grid of the MB-aligned picture, BW = 4 * w_mbs columns by BH = 4 * h_mbs
@@ -760,6 +784,22 @@ int  h264mi_engine_export_tensor_fit(h264mi_engine *e, int n, const int *streams
 int  h264mi_engine_export_tensor_rois_fit(h264mi_engine *e, int n, const int *streams, const int *slots,
                                           const h264mi_tensor_fit_desc *desc, const h264mi_roi *rois, int nrois,
                                           void *d_out, size_t out_stride, void *hip_stream);
+/* the eight calls above under a layout descriptor (h264mi_tensor_layout_desc
+ * above): rois == NULL and nrois == 0 is desc's window of every picture, else
+ * the boxes (the window reserved, a size required).  Picture or box k occupies
+ * the planes * rows * cols elements at d_out + k * out_stride the mirrored call
+ * writes, and nothing else is written.  H264MI_LAYOUT_PLANAR runs that call;
+ * H264MI_LAYOUT_INTERLEAVED stores the same values channels-last (GRAY: the
+ * same bytes, the same kernels).  d_out and out_stride are multiples of the
+ * element size; where they and a row's cols * planes * element size bytes are
+ * multiples of 16, the unresized export stores 16 bytes at a time.  -1,
+ * nothing launched, on a bad argument. */
+int  h264mi_tensor_layout_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width, int height,
+                                       int cpitch, const h264mi_tensor_layout_desc *desc, const h264mi_roi *rois,
+                                       int nrois, void *d_out, size_t out_stride, void *hip_stream);
+int  h264mi_engine_export_tensor_layout(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                        const h264mi_tensor_layout_desc *desc, const h264mi_roi *rois, int nrois,
+                                        void *d_out, size_t out_stride, void *hip_stream);
 /* the MB side-information field (h264mi_mbinfo_desc above) of npics record
  * batches of w_mbs * h_mbs MbRec each, batch k starting rec_offsets[k] bytes (a
  * host array of multiples of 96; any order, repeats allowed) after d_recs
