@@ -104,6 +104,17 @@ class TensorLayoutDesc(C.Structure):
     _fields_ = [("f", TensorFitDesc), ("layout", C.c_int)]
 
 
+class Warp(C.Structure):
+    """h264mi_warp (include/h264mi.h)."""
+    _fields_ = [("pic", C.c_int), ("m", C.c_int * 6)]
+
+
+class TensorWarpDesc(C.Structure):
+    """h264mi_tensor_warp_desc (include/h264mi.h)."""
+    _fields_ = [("t", TensorDesc)] + [(n, C.c_int) for n in ("ow", "oh", "filter", "border")] + \
+               [("pad", C.c_ubyte * 4), ("layout", C.c_int)]
+
+
 class MbInfoDesc(C.Structure):
     """h264mi_mbinfo_desc (include/h264mi.h)."""
     _fields_ = [(n, C.c_int) for n in ("bx", "by", "bw", "bh", "nch", "dtype")] + \
@@ -171,6 +182,10 @@ TENSOR_FIT = {"stretch": 0, "letterbox": 1, "topleft": 2}
 TENSOR_U8, TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 0, 1, 2, 3
 # TensorLayoutDesc.layout by the name of the torch memory format it gives
 TENSOR_LAYOUTS = {"nchw": 0, "nhwc": 1}
+# TensorWarpDesc.filter and .border
+WARP_BILINEAR = 0
+WARP_BORDERS = {"constant": 0, "replicate": 1}
+WARPS_MAX_PER_LAUNCH = 32
 
 HEADERS_CB = C.CFUNCTYPE(None, C.c_void_p)
 PICTURE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32)
@@ -335,6 +350,14 @@ def mi() -> C.CDLL:
         L.H264SwDecNextPictureTensorLayout.restype = i32
         L.H264SwDecLastPictureTensorRoisLayout.argtypes = [vp, ld, ro, u32, vp, vp]
         L.H264SwDecLastPictureTensorRoisLayout.restype = i32
+    if hasattr(L, "h264mi_tensor_warps_device_pitch"):      # (optional, as above)
+        wd, wa = C.POINTER(TensorWarpDesc), C.POINTER(Warp)
+        L.h264mi_tensor_warps_device_pitch.argtypes = [vp, C.POINTER(sz), i32, i32, i32, i32, wd, wa, i32, vp, sz, vp]
+        L.h264mi_tensor_warps_device_pitch.restype = i32
+        L.h264mi_engine_export_tensor_warps.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), wd, wa, i32, vp, sz, vp]
+        L.h264mi_engine_export_tensor_warps.restype = i32
+        L.H264SwDecLastPictureTensorWarps.argtypes = [vp, wd, wa, u32, vp, vp]
+        L.H264SwDecLastPictureTensorWarps.restype = i32
     if hasattr(L, "h264mi_mbinfo_device"):                  # (optional, as above)
         md = C.POINTER(MbInfoDesc)
         L.h264mi_mbinfo_device.argtypes = [vp, C.POINTER(sz), i32, i32, i32, md, vp, sz, vp]

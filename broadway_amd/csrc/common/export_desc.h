@@ -185,6 +185,35 @@ static inline int rois_layout_ok(const h264mi_tensor_layout_desc *d, const h264m
     return layout_desc_fixed_ok(d) && !layout_unresized(d) && rois_fit_ok(&d->f, r, nrois, npics, width, height);
 }
 
+/* h264mi_tensor_warp_desc: the tensor descriptor's rules, an output size as for
+ * the resize, a known filter, border and layout, the reserved pad byte zero,
+ * and no pad where the border repeats the edge.  Its window is the one the
+ * taps are confined to (common/warp_geom.h): at most 16384 a side.  The
+ * matrices have no rule: every int32 coefficient is legal. */
+static inline int warp_desc_fixed_ok(const h264mi_tensor_warp_desc *d)
+{
+    return tensor_desc_fixed_ok(&d->t) && d->ow >= 1 && d->oh >= 1 && d->ow <= H264MI_RESIZE_MAX_DIM &&
+           d->oh <= H264MI_RESIZE_MAX_DIM && d->filter == H264MI_WARP_BILINEAR &&
+           (d->border == H264MI_WARP_BORDER_CONSTANT || d->border == H264MI_WARP_BORDER_REPLICATE) && d->pad[3] == 0 &&
+           (d->border != H264MI_WARP_BORDER_REPLICATE || !(d->pad[0] | d->pad[1] | d->pad[2])) &&
+           (d->layout == H264MI_LAYOUT_PLANAR || d->layout == H264MI_LAYOUT_INTERLEAVED);
+}
+
+/* (after warp_desc_fixed_ok) */
+static inline int warp_window_ok(const h264mi_tensor_warp_desc *d, int width, int height)
+{
+    return tensor_window_ok(&d->t, width, height) && d->t.cw <= H264MI_RESIZE_MAX_DIM && d->t.ch <= H264MI_RESIZE_MAX_DIM;
+}
+
+/* a list of h264mi_warp over npics pictures: at least one, every pic in [0, npics).  All or nothing. */
+static inline int warps_ok(const h264mi_warp *w, int nwarps, int npics)
+{
+    if (nwarps < 1) return 0;
+    for (int k = 0; k < nwarps; k++)
+        if (w[k].pic < 0 || w[k].pic >= npics) return 0;
+    return 1;
+}
+
 /* h264mi_mbinfo_desc: the window is in 4x4 blocks of a w_mbs x h_mbs picture */
 static inline int mbinfo_desc_fixed_ok(const h264mi_mbinfo_desc *d)
 {

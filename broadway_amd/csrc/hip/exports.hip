@@ -9,6 +9,7 @@
 #include "crop.hip"
 #include "tensor.hip"
 #include "resize.hip"
+#include "warp.hip"
 #include "field_store.h"
 #include "mbinfo.hip"
 #include "residual.hip"
@@ -22,6 +23,7 @@
 #include <string.h>
 #include "../../../include/h264mi.h"
 #include "../common/export_desc.h"
+#include "../common/warp_geom.h"
 #include "engine_priv.h"
 
 // record retention (h264mi_engine_keep_records): the uploaded batch's records,
@@ -577,6 +579,55 @@ extern "C" int h264mi_tensor_layout_device_pitch(const void *d_in, const size_t 
                        rois ? NULL : &f->r.t, rois, rois ? nrois : npics, d_out, out_stride, stream, hwc);
 }
 
+// The affine-warped export (warp.hip, include/h264mi.h): warp r,
+// the matrix warps[r].m over the window desc->t of the picture that starts
+// in_offsets[warps[r].pic] bytes after d_in: its (planes, oh, ow) elements at
+// d_out + r * out_stride, interleaved with desc->layout (RGB).  Everything is
+// checked first (common/export_desc.h: one bad warp refuses the call; every
+// matrix is legal, the taps stay in the window by common/warp_geom.h); then one
+// launch per EXPORT_MAX_PICS warps, each with its rows' picture offsets and
+// matrices in the kernel arguments.  warps is host memory, read here.  -1
+// (nothing launched) on a bad argument.
+static_assert(H264MI_WARPS_MAX_PER_LAUNCH == TENSOR_MAX_PICS, "include/h264mi.h and tensor.hip name the same bound");
+
+static bool warps_desc_ok(const h264mi_tensor_warp_desc *d, const h264mi_warp *warps, int nwarps, int npics, int width,
+                          int height)
+{
+    return d && warps && tensor_mode_ok(d->t.mode) && warp_desc_fixed_ok(d) && warp_window_ok(d, width, height) &&
+           warps_ok(warps, nwarps, npics);
+}
+
+extern "C" int h264mi_tensor_warps_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width,
+                                                int height, int cpitch, const h264mi_tensor_warp_desc *desc,
+                                                const h264mi_warp *warps, int nwarps, void *d_out, size_t out_stride,
+                                                void *stream)
+{
+    if (!tensor_pics_ok(d_in, in_offsets, npics, width, height, cpitch, d_out) ||
+        !warps_desc_ok(desc, warps, nwarps, npics, width, height))
+        return -1;
+    const h264mi_tensor_desc *t = &desc->t;
+    // (d_out is checked here too, as for the boxes: a host address would fault every launch of the list)
+    if (!export_aligned(d_out, out_stride, export_elem_size(t->dtype)) || h264mi_pointer_device(d_out) < 0) return -1;
+    const int layout = H264MI_TENSOR_LAYOUT(t->mode), colour = H264MI_TENSOR_COLOUR(t->mode);
+    const bool hwc = desc->layout == H264MI_LAYOUT_INTERLEAVED && layout == H264MI_TENSOR_RGB;
+    warp_args wa;
+    tensor_args &a = wa.t;
+    a.in = (const uint8_t *)d_in;
+    a.width = width; a.height = height; a.cpitch = cpitch;
+    a.x = t->x; a.y = t->y; a.cw = t->cw; a.ch = t->ch;
+    a.out_stride = out_stride;
+    for (int p = 0; p < 3; p++) { a.scale[p] = t->scale[p]; a.bias[p] = t->bias[p]; wa.pad[p] = desc->pad[p]; }
+    a.col = tensor_colour_sets[colour];
+    wa.ow = desc->ow; wa.oh = desc->oh; wa.border = desc->border;
+    std::vector<size_t> off((size_t)nwarps);
+    for (int r = 0; r < nwarps; r++) off[r] = in_offsets[warps[r].pic];
+    return export_launches(nwarps, off.data(), a.in_off, &a.out, d_out, out_stride, [&](int r0, int n) {
+        for (int r = 0; r < EXPORT_MAX_PICS; r++)
+            memcpy(wa.m[r], warps[r0 + (r < n ? r : 0)].m, sizeof(wa.m[r]));
+        warp_launch(layout, t->dtype, colour != 0, hwc, n, (hipStream_t)stream, wa);
+    });
+}
+
 // An export of the slots (streams[k], slots[k]), k < n, into the caller's
 // device memory with no host synchronisation: the engine's stream waits for
 // what `stream` (NULL: the null stream; ours is non-blocking, so that too goes
@@ -698,6 +749,23 @@ extern "C" int h264mi_engine_export_tensor_layout(h264mi_engine *e, int n, const
         for (int k = 0; k < n; k++) off[k] = e->frame_bytes * ((size_t)streams[k] * e->nslots + slots[k]);
         return h264mi_tensor_layout_device_pitch(e->d_frames, off.data(), n, width, height, e->cpitch, desc, rois, nrois,
                                                  d_out, out_stride, e->st);
+    });
+}
+
+// warps over the frame slots (h264mi_tensor_warps_device_pitch; warps[r].pic
+// indexes the n slots): one ordering of the two streams for the whole list
+extern "C" int h264mi_engine_export_tensor_warps(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                                 const h264mi_tensor_warp_desc *desc, const h264mi_warp *warps,
+                                                 int nwarps, void *d_out, size_t out_stride, void *stream)
+{
+    if (!e || n < 1 || !streams || !slots || !d_out) return -1;
+    const int width = e->w * 16, height = e->h * 16;
+    if (!warps_desc_ok(desc, warps, nwarps, n, width, height)) return -1;
+    return export_ordered(e, n, streams, slots, d_out, out_stride, export_elem_size(desc->t.dtype), stream, [&] {
+        std::vector<size_t> off((size_t)n);
+        for (int k = 0; k < n; k++) off[k] = e->frame_bytes * ((size_t)streams[k] * e->nslots + slots[k]);
+        return h264mi_tensor_warps_device_pitch(e->d_frames, off.data(), n, width, height, e->cpitch, desc, warps, nwarps,
+                                                d_out, out_stride, e->st);
     });
 }
 

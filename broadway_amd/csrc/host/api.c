@@ -550,6 +550,42 @@ H264SwDecRet H264SwDecLastPictureTensorRoisLayout(H264SwDecInst decInst, const h
                              hip_stream);
 }
 
+/* Affine warps of the delivered picture (include/h264mi.h): a LastPicture call
+ * like the boxes above.  The window the taps are confined to is the SPS crop
+ * window (desc->t.cw == 0) or a window inside it, in its coordinates: the crop
+ * offset goes onto the window and the matrices stay as they are (they map into
+ * the window), so no tap reaches the MB-aligned picture's padding.  STREAM
+ * resolves as for the boxes, by size from the crop window. */
+H264SwDecRet H264SwDecLastPictureTensorWarps(H264SwDecInst decInst, const h264mi_tensor_warp_desc *desc,
+                                             const h264mi_warp *warps, u32 nwarps, void *d_dst, void *hip_stream)
+{
+    if (decInst == NULL || desc == NULL || warps == NULL || d_dst == NULL) return H264SWDEC_PARAM_ERR;
+    DecContainer *c = (DecContainer *)decInst;
+    if (!c->dec.be.export_tensor_warps) return H264SWDEC_PARAM_ERR;
+    h264mi_tensor_warp_desc m = *desc;
+    if (nwarps < 1 || nwarps > 0x7FFFFFFF / sizeof(h264mi_warp) || h264mi_tensor_colour_resolve(m.t.mode, 2, 0, 2, 2) < 0 ||
+        !warp_desc_fixed_ok(&m) || !export_aligned(d_dst, 0, export_elem_size(m.t.dtype)) || !warps_ok(warps, (int)nwarps, 1))
+        return H264SWDEC_PARAM_ERR;
+    const Sps *s = h264dec_active_sps(&c->dec);
+    if (!s || !c->dec.last_out_slot1) return H264SWDEC_OK;      /* no picture delivered */
+    const export_window w = sps_crop_window(s);
+    if (m.t.cw == 0) {
+        m.t.x = w.x; m.t.y = w.y; m.t.cw = w.cw; m.t.ch = w.ch;
+    } else {
+        if (m.t.x < 0 || m.t.y < 0 || m.t.cw < 1 || m.t.ch < 1 || m.t.cw > w.cw - m.t.x || m.t.ch > w.ch - m.t.y)
+            return H264SWDEC_PARAM_ERR;
+        m.t.x += w.x; m.t.y += w.y;
+    }
+    if (!warp_window_ok(&m, 16 * s->w_mbs, 16 * s->h_mbs)) return H264SWDEC_PARAM_ERR;
+    const int colour = h264mi_tensor_colour_resolve(m.t.mode, c->dec.last_out_vui_matrix, c->dec.last_out_vui_full, w.cw, w.ch);
+    if (H264MI_TENSOR_LAYOUT(m.t.mode) == H264MI_TENSOR_RGB) m.t.mode = H264MI_TENSOR_MODE(H264MI_TENSOR_RGB, colour, 0);
+    /* (a failure of the export itself: d_dst not on the decoder's GPU) */
+    if (c->dec.be.export_tensor_warps(c->dec.be.ctx, c->dec.last_out_slot1 - 1, &m, warps, (int)nwarps, d_dst, hip_stream))
+        return H264SWDEC_PARAM_ERR;
+    c->dec.last_tensor_colour1 = colour + 1;
+    return H264SWDEC_PIC_RDY;
+}
+
 H264SwDecRet H264SwDecGetTiming(H264SwDecInst decInst, double *parse_s, double *submit_s, double *wait_s,
                                 double *copy_s, u32 *pictures)
 {

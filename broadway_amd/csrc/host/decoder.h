@@ -92,6 +92,13 @@ typedef struct H264Backend {
      * cannot */
     int  (*export_tensor_layout)(void *ctx, int slot, const void *desc, const void *rois, int nrois, void *d_dst,
                                  void *hip_stream);
+    /* optional: the nwarps warps (h264mi_warp, every pic 0) of slot as the
+     * affine-warped tensors of desc (a checked h264mi_tensor_warp_desc whose
+     * window is in picture coordinates), warp r packed behind warp r - 1 at
+     * d_dst, ordered like export_tensor; no retention; 0 ok, -1 failure; NULL
+     * when the backend cannot */
+    int  (*export_tensor_warps)(void *ctx, int slot, const void *desc, const void *warps, int nwarps, void *d_dst,
+                                void *hip_stream);
     /* optional: host memory for the output frames (pinned by the HIP
      * backend, so each picture's D2H copy runs at DMA speed); NULL: malloc */
     void *(*host_alloc)(void *ctx, size_t bytes);

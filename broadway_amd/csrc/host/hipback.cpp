@@ -729,6 +729,35 @@ static int hb_export_tensor_layout(void *vctx, int slot, const void *desc, const
     return rois ? 0 : slot_flagged((HipBackendCtx *)vctx, slot, false);
 }
 
+// warps of slot as affine-warped tensors (a member of its own, with no
+// retention): the list travels through hb_export as one descriptor, warp r's
+// elements packed behind warp r - 1's
+extern "C" int h264mi_engine_export_tensor_warps(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                                 const h264mi_tensor_warp_desc *desc, const h264mi_warp *warps,
+                                                 int nwarps, void *d_out, size_t out_stride,
+                                                 void *hip_stream) __attribute__((weak));
+struct WarpsCall {
+    const h264mi_tensor_warp_desc *desc;
+    const h264mi_warp *warps;
+    int nwarps;
+};
+
+static int engine_export_warps(h264mi_engine *e, int n, const int *streams, const int *slots, const WarpsCall *c,
+                               void *d_out, size_t, void *hip_stream)
+{
+    const size_t planes = H264MI_TENSOR_LAYOUT(c->desc->t.mode) == H264MI_TENSOR_GRAY ? 1 : 3;
+    return h264mi_engine_export_tensor_warps(e, n, streams, slots, c->desc, c->warps, c->nwarps, d_out,
+                                             planes * c->desc->oh * c->desc->ow * export_elem_size(c->desc->t.dtype),
+                                             hip_stream);
+}
+
+static int hb_export_tensor_warps(void *vctx, int slot, const void *desc, const void *warps, int nwarps, void *d_dst,
+                                  void *hip_stream)
+{
+    const WarpsCall c = {(const h264mi_tensor_warp_desc *)desc, (const h264mi_warp *)warps, nwarps};
+    return hb_export(vctx, slot, engine_export_warps, &c, d_dst, hip_stream);
+}
+
 // Pinned host blocks (decoder output frames) kept after free for the next
 // decoder instance: pinning tens of MB per instance is a large share of a
 // short stream's host time.  Exact-size reuse, at most H264MI_HOST_POOL_MB
@@ -881,6 +910,7 @@ extern "C" H264Backend h264mi_hip_backend_create(int device)
     be.export_tensor_fit = h264mi_engine_export_tensor_fit ? hb_export_tensor_fit : NULL;
     be.export_tensor_rois_fit = h264mi_engine_export_tensor_rois_fit ? hb_export_tensor_rois_fit : NULL;
     be.export_tensor_layout = h264mi_engine_export_tensor_layout ? hb_export_tensor_layout : NULL;
+    be.export_tensor_warps = h264mi_engine_export_tensor_warps ? hb_export_tensor_warps : NULL;
     be.host_alloc = hb_host_alloc;
     be.host_free = hb_host_free;
     be.records_wait = hb_records_wait;

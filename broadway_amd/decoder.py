@@ -158,6 +158,20 @@ def rois_args(boxes, size, width, height, **kw):
     return rois_desc(boxes, size, 1, width or _lib.RESIZE_MAX_DIM, height or _lib.RESIZE_MAX_DIM, stream_ok=True, **kw)
 
 
+def warps_args(mats, size, window, width, height, **kw):
+    """``Decoder.warps``'s arguments as (descriptor, ``_lib.Warp`` array, planes,
+    torch dtype): ``mats`` = [(m0, ..., m5), ...], all of picture 0, over
+    ``window`` of a delivered picture of width x height (0: no headers yet);
+    ``kw``: the ``tensor`` option's keys, ``border``, ``pad`` and ``layout``.
+    ValueError for anything the library would refuse."""
+    from .engine import warps_desc               # (imports torch)
+    try:
+        mats = [(0, tuple(m)) for m in mats]
+    except TypeError:
+        raise ValueError(f"warps: {mats!r}: a list of (m0, m1, m2, m3, m4, m5)") from None
+    return warps_desc(mats, size, 1, window, width, height, stream_ok=True, **kw)
+
+
 class Decoder:
     def __init__(self, options: Optional[dict] = None):
         self.options = dict(options or {})
@@ -403,6 +417,35 @@ class Decoder:
             raise RuntimeError("rois: no picture has been delivered since the last decode")
         if ret != _lib.H264SWDEC_PIC_RDY:
             raise RuntimeError(f"rois: the backend cannot export the boxes ({ret}; there is no host fallback)")
+        return out
+
+    def warps(self, mats, size, window=None, mode="rgb", dtype=None, mean=None, std=None, scale=None, bias=None,
+              colour=None, unspecified=None, border=None, pad=None, layout="nchw"):
+        """Affine warps of the delivered picture as one new ``(K, planes, oh,
+        ow)`` torch tensor on the decoder's GPU, on torch's current stream
+        (``H264SwDecLastPictureTensorWarps``): ``mats`` = [(m0, ..., m5), ...],
+        the Q16 inverse maps of ``Engine.to_tensor(warps=)``
+        (``engine.warp_q16``, ``engine.rotated_box_warp``), in the coordinates
+        of ``window`` = (x, y, cw, ch) -- even, inside the picture
+        ``onPictureDecoded`` receives with ``crop`` or ``tensor``; None: all of
+        it.  No tap reads outside that window, so a crop's padding rows never
+        show: ``border="constant"`` (default) gives ``pad`` there (default 0),
+        "replicate" the window's edge.  Callable when ``rois`` is; the other
+        arguments are those of the ``tensor`` option.  ValueError for a bad
+        argument, RuntimeError before a picture was delivered."""
+        _, _, cw, ch = self._crop_window()
+        desc, arr, planes, dtype = warps_args(mats, size, window, cw, ch, mode=mode, dtype=dtype, mean=mean, std=std,
+                                              scale=scale, bias=bias, colour=colour, unspecified=unspecified, border=border,
+                                              pad=pad, layout=layout)
+        if not hasattr(self, "_device"):
+            self._device = int(os.environ.get("H264MI_DEVICE") or 0)
+        out, st = self._device_empty((len(arr), planes, desc.oh, desc.ow), dtype, layout)
+        last = getattr(self._L, "H264SwDecLastPictureTensorWarps", None)
+        ret = last(self._inst, C.byref(desc), arr, len(arr), out.data_ptr(), st) if last else _lib.H264SWDEC_PARAM_ERR
+        if ret == _lib.H264SWDEC_OK:
+            raise RuntimeError("warps: no picture has been delivered since the last decode")
+        if ret != _lib.H264SWDEC_PIC_RDY:
+            raise RuntimeError(f"warps: the backend cannot export the warps ({ret}; there is no host fallback)")
         return out
 
     @property

@@ -326,6 +326,109 @@ def rois_desc(rois, size, npics, width, height, mode="rgb", dtype=None, scale=No
     return desc, arr, planes, dtype
 
 
+def _q16(v, what):
+    """floor(v * 65536 + 0.5) of a coefficient; ValueError where it leaves int32."""
+    import math
+    v = float(v)
+    q = math.floor(v * 65536.0 + 0.5) if math.isfinite(v) else None
+    if q is None or not -2 ** 31 <= q < 2 ** 31:
+        raise ValueError(f"{what}: coefficient {v!r} does not fit Q16 in int32")
+    return int(q)
+
+
+def warp_q16(M, forward=True):
+    """The six Q16 coefficients ``(m0, ..., m5)`` of ``Engine.to_tensor(warps=)``
+    from a float 2x3 matrix in cv2's convention (integer coordinates are
+    sample centres, of the window and of the output alike).  ``forward``
+    (cv2.warpAffine's default): ``M`` maps a window position to an output
+    position and is inverted here; ``forward=False``: ``M`` maps an output
+    position to a window position already (cv2's WARP_INVERSE_MAP), which is
+    what the export takes.  Each coefficient is ``floor(v * 65536 + 0.5)``;
+    ValueError for a singular forward matrix, a bad shape, or a coefficient
+    outside int32."""
+    try:
+        (a, b, c), (d, e, f) = [[float(v) for v in row] for row in M]
+    except (TypeError, ValueError):
+        raise ValueError(f"warp_q16: {M!r}: a 2x3 matrix") from None
+    if forward:
+        det = a * e - b * d
+        if det == 0.0 or det != det:
+            raise ValueError(f"warp_q16: {M!r} is singular")
+        a, b, c, d, e, f = e / det, -b / det, (b * f - c * e) / det, -d / det, a / det, (c * d - a * f) / det
+    return tuple(_q16(v, "warp_q16") for v in (a, b, c, d, e, f))
+
+
+def rotated_box_warp(cx, cy, bw, bh, angle_deg, size):
+    """The six Q16 coefficients that turn a rotated box upright: the box of
+    bw x bh centred at (cx, cy), rotated counter-clockwise (as seen, y down) by
+    ``angle_deg`` about its centre, in continuous coordinates of the window
+    (sample k covers [k, k + 1)), sampled to ``size`` = (oh, ow).  Output (i,
+    j) samples ``(cx, cy) + R(angle) ((j + 0.5) bw / ow - bw / 2, (i + 0.5) bh
+    / oh - bh / 2) - (0.5, 0.5)`` with R = [[cos, sin], [-sin, cos]].  Angle 0
+    with the box equal to the window and ``size == (ch, cw)`` is the identity,
+    and quarter turns use exact cosines.  ValueError as for ``warp_q16``."""
+    import math
+    oh, ow = _resize_size(size)
+    cx, cy, bw, bh, angle = (float(v) for v in (cx, cy, bw, bh, angle_deg))
+    quarter = {0.0: (1.0, 0.0), 90.0: (0.0, 1.0), 180.0: (-1.0, 0.0), 270.0: (0.0, -1.0)}
+    c, s = quarter.get(angle % 360.0) or (math.cos(math.radians(angle)), math.sin(math.radians(angle)))
+    sx, sy = bw / ow, bh / oh
+    u0, v0 = 0.5 * sx - 0.5 * bw, 0.5 * sy - 0.5 * bh
+    M = ((c * sx, s * sy, cx - 0.5 + c * u0 + s * v0), (-s * sx, c * sy, cy - 0.5 - s * u0 + c * v0))
+    return tuple(_q16(v, "rotated_box_warp") for row in M for v in row)
+
+
+def warps_desc(warps, size, npics, window, width, height, mode="rgb", dtype=None, scale=None, bias=None, mean=None,
+               std=None, colour=None, unspecified=None, stream_ok=False, border=None, pad=None, layout=None):
+    """(``_lib.TensorWarpDesc``, ``_lib.Warp`` array, planes, torch dtype) of an
+    affine-warped export (Engine.to_tensor(warps=), Decoder.warps): ``warps`` =
+    [(k, (m0, ..., m5)), ...] over ``npics`` pictures of width x height (0: not
+    known yet, so the window is not judged against it), every warp to ``size``
+    = (oh, ow) from ``window`` = (x, y, cw, ch), the window the taps are
+    confined to (None: cw = 0, the Decoder's crop window).  The coefficients
+    are Q16 integers (``warp_q16``, ``rotated_box_warp``), any int32.
+    ``border`` "constant" (the default: a tap outside the window is the sample
+    ``pad``, default 0; one value or one per plane) or "replicate" (the
+    window's edge; no ``pad``).  ``layout`` "nchw" (default) or "nhwc".
+    ValueError for anything the library would refuse."""
+    if size is None:
+        raise ValueError("warps: goes with size=(oh, ow)")
+    t, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std, None, colour, unspecified, stream_ok)
+    oh, ow = _resize_size(size)
+    border = "constant" if border is None else border
+    if not isinstance(border, str) or border not in _lib.WARP_BORDERS:
+        raise ValueError(f"border {border!r}: one of {sorted(_lib.WARP_BORDERS)}")
+    if border == "replicate" and pad is not None:
+        raise ValueError("pad: goes with border='constant' (replicate repeats the window's edge)")
+    d = _lib.TensorWarpDesc()
+    d.t, d.ow, d.oh, d.filter, d.border = t, ow, oh, _lib.WARP_BILINEAR, _lib.WARP_BORDERS[border]
+    d.pad[:] = fit_desc(_lib.TensorResizeDesc(), planes, "stretch", 0 if pad is None else pad).pad[:]
+    d.layout = tensor_layout("nchw" if layout is None else layout)
+    if window is not None:
+        x, y, cw, ch = (t.x, t.y, t.cw, t.ch)
+        if (x | y | cw | ch) & 1 or x < 0 or y < 0 or cw < 2 or ch < 2 or cw > _lib.RESIZE_MAX_DIM or \
+                ch > _lib.RESIZE_MAX_DIM or (width and (cw > width - x or ch > height - y)):
+            raise ValueError(f"warps: window {(x, y, cw, ch)}: even, at most {_lib.RESIZE_MAX_DIM} a side and inside "
+                             f"{width} x {height}")
+    try:
+        given = [(k, tuple(m)) for k, m in warps]
+        mats = [(int(k), tuple(int(v) for v in m)) for k, m in given]
+        if any(len(m) != 6 for _, m in mats) or mats != given or \
+                any(isinstance(v, bool) for k, m in given for v in (k,) + m):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"warps {warps!r}: a list of (k, (m0, m1, m2, m3, m4, m5)) integers") from None
+    if not mats:
+        raise ValueError("warps: an empty list")
+    for k, m in mats:
+        if not 0 <= k < npics:
+            raise ValueError(f"warps: {(k, m)}: picture {k} of {npics}")
+        if not all(-2 ** 31 <= v < 2 ** 31 for v in m):
+            raise ValueError(f"warps: {(k, m)}: the coefficients are int32 (Q16)")
+    arr = (_lib.Warp * len(mats))(*[_lib.Warp(k, (C.c_int * 6)(*m)) for k, m in mats])
+    return d, arr, planes, dtype
+
+
 def _field_channels(channels, table, max_ch):
     """The ids of ``channels`` (a name or names of ``table``, 1..max_ch of them)."""
     if isinstance(channels, str):
@@ -691,7 +794,7 @@ class Engine:
 
     def to_tensor(self, streams: Sequence[int], slots: Sequence[int], window=None, mode: str = "rgb", dtype=None,
                   scale=None, bias=None, mean=None, std=None, out=None, stream=None, size=None, colour=None,
-                  rois=None, fit=None, pad=None, layout="nchw"):
+                  rois=None, fit=None, pad=None, layout="nchw", warps=None, border=None):
         """The slots (streams[k], slots[k]) as one ``(n, planes, ch, cw)``
         torch tensor on ``cuda:{self.device}``, built on the GPU and never
         copied to the host: planes R, G, B (``mode="rgb"``, the values of
@@ -738,6 +841,20 @@ class Engine:
         is such a tensor (``check_out``).  "nchw", the default, is everything
         above, untouched.  With ``mode="gray"`` the two are the same bytes.
 
+        ``warps`` = [(k, (m0, ..., m5)), ...] (with ``size``; not with ``rois``
+        or ``fit``): affine warps instead of upright boxes --
+        rotated boxes turned upright, crops aligned to landmarks.  Warp r makes
+        ``size`` outputs from ``window`` of picture k: the six Q16 integers map
+        output (row i, column j) to the window position ``(m0 j + m1 i + m2,
+        m3 j + m4 i + m5) / 65536`` (the inverse map; ``warp_q16`` and
+        ``rotated_box_warp`` make them), sampled bilinearly in integers from
+        the converted samples, reproducible to the byte.  ``border``
+        "constant" (default): a tap outside ``window`` is the sample ``pad``
+        (default 0); "replicate": the window's edge sample.  Nothing outside
+        ``window`` is read.  The result is ``(len(warps), planes, oh, ow)``,
+        from one launch per 32 warps.  Not antialiased: shrink by more than
+        about 2 : 1 with ``size`` / ``rois`` instead.
+
         The export is ordered on ``stream`` (a torch.cuda.Stream; default:
         torch's current stream of the device): it starts after the work queued
         there and after every launch queued on the engine, later work on
@@ -748,6 +865,22 @@ class Engine:
         consumers (``torch.utils.dlpack`` / ``__dlpack__``) need nothing further."""
         n, c_streams, c_slots = self._pictures(streams, slots)
         nhwc = tensor_layout(layout) != 0
+        if warps is None and border is not None:
+            raise ValueError("border: goes with warps")
+        if warps is not None:
+            if rois is not None or fit is not None:
+                raise ValueError("warps: not combinable with rois or fit")
+            if window is None:
+                window = (0, 0, self.w_mbs * 16, self.h_mbs * 16)
+            desc, mats, planes, dtype = warps_desc(warps, size, n, window, self.w_mbs * 16, self.h_mbs * 16, mode, dtype,
+                                                   scale, bias, mean, std, colour, border=border, pad=pad, layout=layout)
+            out, st = self._out((len(mats), planes, desc.oh, desc.ow), dtype, out, stream, layout)
+            if not hasattr(self._L, "h264mi_engine_export_tensor_warps") or \
+                    self._L.h264mi_engine_export_tensor_warps(self._h, n, c_streams, c_slots, C.byref(desc), mats, len(mats),
+                                                              out.data_ptr(), planes * desc.oh * desc.ow * out.element_size(),
+                                                              st) != 0:
+                raise RuntimeError("h264mi_engine_export_tensor_warps failed (stream or slot out of range?)")
+            return out
         fitted = fit is not None or pad is not None
         if fitted and size is None:
             raise ValueError("fit and pad go with size=(oh, ow), the canvas")

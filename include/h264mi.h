@@ -297,6 +297,52 @@ H264SwDecRet H264SwDecNextPictureTensorLayout(H264SwDecInst decInst, H264SwDecPi
                                               const h264mi_tensor_layout_desc *desc, void *d_dst, void *hip_stream);
 H264SwDecRet H264SwDecLastPictureTensorRoisLayout(H264SwDecInst decInst, const h264mi_tensor_layout_desc *desc,
                                                   const h264mi_roi *rois, u32 nrois, void *d_dst, void *hip_stream);
+/* Affine-warped tensors (warp.hip): rotated boxes, aligned crops.
+ * A warp makes (planes, oh, ow) elements from the window t.(x, y, cw, ch) of
+ * one picture (even, as for every pixel export; at most 16384 a side).  Six
+ * int32 coefficients m[0..5] in Q16 map an OUTPUT element to a SOURCE position
+ * (the inverse map, cv2's WARP_INVERSE_MAP); sample (c, r) of the window sits
+ * at (c << 16, r << 16).  For output row i, column j, in exact 64-bit integers:
+ *   X = m0 j + m1 i + m2            Y = m3 j + m4 i + m5
+ *   Xr = (X + 128) >> 8             Yr = (Y + 128) >> 8      (arithmetic shifts: floor)
+ *   x0 = Xr >> 8, fx = Xr & 255     y0 = Yr >> 8, fy = Yr & 255
+ *   v  = ((256 - fx) (256 - fy) s(x0, y0)     + fx (256 - fy) s(x0 + 1, y0)
+ *       + (256 - fx) fy       s(x0, y0 + 1) + fx fy         s(x0 + 1, y0 + 1) + 32768) >> 16
+ * s(c, r) is the 8-bit sample of that plane at window position (c, r): R, G or
+ * B of the descriptor's colour set (4:2:0 chroma replicated, as for the tensor
+ * above) or luma -- the warp filters converted samples, as the resize does.  A
+ * tap outside [0, cw) x [0, ch) is judged on its own: with
+ * H264MI_WARP_BORDER_CONSTANT it is the pad sample pad[p] of plane p, with
+ * H264MI_WARP_BORDER_REPLICATE the sample at the clamped position; nothing
+ * outside the window is ever read.  v <= 255 without a clamp, and becomes an
+ * element under scale[p] and bias[p] as everywhere.  So the identity (65536, 0,
+ * 0, 0, 65536, 0) at (oh, ow) == (ch, cw) gives the bytes of the unresized
+ * tensor of the window, and every map with whole-sample coefficients (shifts,
+ * flips, quarter turns) copies samples.  Every int32 coefficient is legal: a
+ * degenerate matrix samples one point, a huge one lies outside the window
+ * everywhere.  There is no antialiasing: beyond about 2 : 1 a warp aliases
+ * (shrink with the resized tensor or the boxes above).
+ * Rules: the element types of the tensor above; 1 <= ow, oh <= 16384; filter
+ * H264MI_WARP_BILINEAR; a known border; pad[3] == 0, and pad all zero with
+ * REPLICATE; layout as in h264mi_tensor_layout_desc; the window even, inside
+ * the picture, at most 16384 a side; at least one warp, every pic in the
+ * picture list.  One bad warp refuses the whole list. */
+enum { H264MI_WARP_BILINEAR = 0 };
+enum { H264MI_WARP_BORDER_CONSTANT = 0, H264MI_WARP_BORDER_REPLICATE = 1 };
+typedef struct { int pic; int m[6]; } h264mi_warp;
+typedef struct { h264mi_tensor_desc t; int ow, oh, filter, border; unsigned char pad[4]; int layout; } h264mi_tensor_warp_desc;
+#define H264MI_WARPS_MAX_PER_LAUNCH 32
+/* Warps of the picture the last H264SwDecNextPicture* call delivered, as
+ * H264SwDecLastPictureTensorRois takes boxes: every pic is 0; desc->t.cw == 0
+ * takes the SPS crop window, otherwise the window is relative to the crop
+ * window and lies inside it -- the call adds the crop offset to the window,
+ * never to the matrices, so no tap reaches a sample outside the delivered
+ * picture.  Warp r's (planes, oh, ow) elements at d_dst + r * planes * oh * ow
+ * elements.  H264MI_TENSOR_COLOUR_STREAM resolves from the delivered picture's
+ * VUI (by size: from the crop window) and H264SwDecLastTensorColour reports
+ * it.  Return codes are H264SwDecLastPictureTensorRois's. */
+H264SwDecRet H264SwDecLastPictureTensorWarps(H264SwDecInst decInst, const h264mi_tensor_warp_desc *desc,
+                                             const h264mi_warp *warps, u32 nwarps, void *d_dst, void *hip_stream);
 /* Motion vectors and MB side information as a device tensor (mbinfo.hip, DESIGN
  * 3.5d; elsewhere: ffmpeg's export_mvs).  The field lives on the luma 4x4-block
  * grid of the MB-aligned picture, BW = 4 * w_mbs columns by BH = 4 * h_mbs
@@ -800,6 +846,21 @@ int  h264mi_tensor_layout_device_pitch(const void *d_in, const size_t *in_offset
 int  h264mi_engine_export_tensor_layout(h264mi_engine *e, int n, const int *streams, const int *slots,
                                         const h264mi_tensor_layout_desc *desc, const h264mi_roi *rois, int nrois,
                                         void *d_out, size_t out_stride, void *hip_stream);
+/* the affine-warped export (h264mi_tensor_warp_desc above) over a list of
+ * warps: warp r, the matrix warps[r].m over the window desc->t of picture
+ * warps[r].pic of the picture list (in_offsets, or streams / slots): its
+ * (planes, oh, ow) elements, in desc->layout's order, at d_out + r *
+ * out_stride, nothing else written, and nothing outside the window read.
+ * `warps` is a host array, read before the call returns.  One kernel launch
+ * per H264MI_WARPS_MAX_PER_LAUNCH warps, and for the engine call one ordering
+ * of the two streams however many there are.  -1, nothing launched, when
+ * anything is bad, d_out in no device's memory included. */
+int  h264mi_tensor_warps_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width, int height,
+                                      int cpitch, const h264mi_tensor_warp_desc *desc, const h264mi_warp *warps,
+                                      int nwarps, void *d_out, size_t out_stride, void *hip_stream);
+int  h264mi_engine_export_tensor_warps(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                       const h264mi_tensor_warp_desc *desc, const h264mi_warp *warps, int nwarps,
+                                       void *d_out, size_t out_stride, void *hip_stream);
 /* the MB side-information field (h264mi_mbinfo_desc above) of npics record
  * batches of w_mbs * h_mbs MbRec each, batch k starting rec_offsets[k] bytes (a
  * host array of multiples of 96; any order, repeats allowed) after d_recs
