@@ -176,6 +176,10 @@ TENSOR_COLOUR_STREAM = 15
 TENSOR_UNSPECIFIED = {"bt601": 0, "bt709": 1, "size": 2}
 TENSOR_COLOUR_SHIFT, TENSOR_UNSPEC_SHIFT = 8, 12
 RESIZE_TRIANGLE = 0
+RESIZE_BICUBIC = 2            # (1 is reserved)
+# TensorResizeDesc.filter by name, and the source samples per output and axis each takes at most
+RESIZE_FILTERS = {"triangle": RESIZE_TRIANGLE, "bicubic": RESIZE_BICUBIC}
+RESIZE_MAX_RATIO = {RESIZE_TRIANGLE: 32, RESIZE_BICUBIC: 16}
 RESIZE_MAX_DIM = 16384
 ROIS_MAX_PER_LAUNCH = 32
 TENSOR_FIT = {"stretch": 0, "letterbox": 1, "topleft": 2}

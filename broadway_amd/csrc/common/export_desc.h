@@ -69,17 +69,30 @@ static inline int tensor_window_ok(const h264mi_tensor_desc *t, int width, int h
            t->cw <= width - t->x && t->ch <= height - t->y;
 }
 
-/* h264mi_tensor_resize_desc: at most 32 source samples per output and axis */
+/* h264mi_tensor_resize_desc: a known filter (1 is reserved), and at most
+ * resize_max_ratio source samples per output and axis -- 64 taps either way:
+ * the triangle's support is one output wide each side, the bicubic's two */
+static inline int resize_filter_ok(int filter)
+{
+    return filter == H264MI_RESIZE_TRIANGLE || filter == H264MI_RESIZE_BICUBIC;
+}
+
+static inline int resize_max_ratio(int filter)
+{
+    return filter == H264MI_RESIZE_BICUBIC ? 16 : 32;
+}
+
 static inline int resize_desc_fixed_ok(const h264mi_tensor_resize_desc *d)
 {
-    return tensor_desc_fixed_ok(&d->t) && d->filter == H264MI_RESIZE_TRIANGLE && d->ow >= 1 && d->oh >= 1 &&
+    return tensor_desc_fixed_ok(&d->t) && resize_filter_ok(d->filter) && d->ow >= 1 && d->oh >= 1 &&
            d->ow <= H264MI_RESIZE_MAX_DIM && d->oh <= H264MI_RESIZE_MAX_DIM;
 }
 
 static inline int resize_window_ok(const h264mi_tensor_resize_desc *d, int width, int height)
 {
+    const int ratio = resize_max_ratio(d->filter);
     return tensor_window_ok(&d->t, width, height) && d->t.cw <= H264MI_RESIZE_MAX_DIM &&
-           d->t.ch <= H264MI_RESIZE_MAX_DIM && d->t.cw <= 32 * d->ow && d->t.ch <= 32 * d->oh;
+           d->t.ch <= H264MI_RESIZE_MAX_DIM && d->t.cw <= ratio * d->ow && d->t.ch <= ratio * d->oh;
 }
 
 /* a list of h264mi_roi over npics pictures of width x height under d: at least
@@ -134,12 +147,14 @@ static inline int fit_desc_fixed_ok(const h264mi_tensor_fit_desc *d)
 static inline int fit_window_ok(const h264mi_tensor_fit_desc *d, int width, int height, int place[4])
 {
     const h264mi_tensor_desc *t = &d->r.t;
+    const int ratio = resize_max_ratio(d->r.filter);
     int f[4];
     if (!tensor_window_ok(t, width, height) || t->cw > H264MI_RESIZE_MAX_DIM || t->ch > H264MI_RESIZE_MAX_DIM) return 0;
     letterbox_fit(t->cw, t->ch, d->r.ow, d->r.oh, d->fit, f);
     if (place) { place[0] = f[0]; place[1] = f[1]; place[2] = f[2]; place[3] = f[3]; }
-    /* (a content larger than the canvas: only behind a major axis beyond 32 : 1) */
-    return f[0] <= d->r.ow && f[1] <= d->r.oh && t->cw <= 32 * f[0] && t->ch <= 32 * f[1];
+    /* (a content larger than the canvas: only behind a major axis beyond 32 : 1; letterbox_fit is one function
+     * for both filters, so a bicubic content between 16 : 1 and 32 : 1 on an axis is refused here) */
+    return f[0] <= d->r.ow && f[1] <= d->r.oh && t->cw <= ratio * f[0] && t->ch <= ratio * f[1];
 }
 
 /* rois_ok for a fit descriptor: every box is a window fit_window_ok accepts
@@ -273,7 +288,8 @@ static inline int accres_window_ok(const h264mi_accres_desc *d, int w_mbs, int h
 
 /* h264mi_accmv_resize_desc and h264mi_accres_resize_desc: the inner
  * descriptor's rules, resize_desc_*_ok's on the output size, and its bounds on
- * the source grid gw x gh -- the window, or its half-resolution grid for UV */
+ * the source grid gw x gh -- the window, or its half-resolution grid for UV.
+ * The fields are filtered by the triangle only (H264MI_RESIZE_BICUBIC is refused). */
 static inline int field_resize_size_ok(int ow, int oh, int filter)
 {
     return filter == H264MI_RESIZE_TRIANGLE && ow >= 1 && oh >= 1 && ow <= H264MI_RESIZE_MAX_DIM &&

@@ -378,8 +378,9 @@ static int tensor_device(const void *d_in, const size_t *in_offsets, int npics, 
     for (int p = 0; p < 3; p++) { a.scale[p] = t->scale[p]; a.bias[p] = t->bias[p]; }
     a.col = tensor_colour_sets[colour];     // (set 0 runs the kernels with the reference's literals)
     if (r) { ra.ow = r->ow; ra.oh = r->oh; }
+    const bool cubic = r && r->filter == H264MI_RESIZE_BICUBIC;
     return export_launches(npics, in_offsets, a.in_off, &a.out, d_out, out_stride, [&](int, int n) {
-        if (r) resize_launch(layout, t->dtype, colour != 0, n, stream, ra);
+        if (r) resize_launch(layout, t->dtype, colour != 0, cubic, n, stream, ra);
         else tensor_launch(layout, t->dtype, v16, colour != 0, hwc, n, stream, a);
     });
 }
@@ -400,8 +401,10 @@ extern "C" int h264mi_tensor_device_pitch(const void *d_in, const size_t *in_off
 // The same pictures resized (resize.hip): the window filtered to desc->oh x
 // desc->ow samples per plane, picture k's (planes, oh, ow) elements at d_out +
 // k * out_stride.  1 <= ow, oh <= 16384 and, per axis, at most 32 source
-// samples per output (64 taps); filter = H264MI_RESIZE_TRIANGLE.  Stateless:
-// the tap tables are made in the kernel.  -1 (nothing launched) on a bad
+// samples per output under H264MI_RESIZE_TRIANGLE, 16 under
+// H264MI_RESIZE_BICUBIC (64 taps either way); the filter picks the kernel's
+// instantiation, here and in every resized export below.  Stateless: the tap
+// tables are made in the kernel.  -1 (nothing launched) on a bad
 // argument.
 extern "C" int h264mi_tensor_resize_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width,
                                                  int height, int cpitch, const h264mi_tensor_resize_desc *desc,
@@ -452,6 +455,7 @@ static int rois_device(const void *d_in, const size_t *in_offsets, int npics, in
     for (int p = 0; p < 3; p++) { a.scale[p] = t->scale[p]; a.bias[p] = t->bias[p]; }
     a.col = tensor_colour_sets[colour];
     ra.r.ow = desc->ow; ra.r.oh = desc->oh;
+    const bool cubic = desc->filter == H264MI_RESIZE_BICUBIC;
     if (fit)
         for (int p = 0; p < 3; p++) fa.pad[p] = fit->pad[p];
     std::vector<size_t> off((size_t)nrois);
@@ -467,9 +471,9 @@ static int rois_device(const void *d_in, const size_t *in_offsets, int npics, in
                 fa.place[r][0] = f[2]; fa.place[r][1] = f[3]; fa.place[r][2] = f[0]; fa.place[r][3] = f[1];
             }
         }
-        if (hwc) fit_hwc_launch(t->dtype, colour != 0, n, (hipStream_t)stream, fa);
-        else if (fit) fit_launch(layout, t->dtype, colour != 0, n, (hipStream_t)stream, fa);
-        else rois_launch(layout, t->dtype, colour != 0, n, (hipStream_t)stream, ra);
+        if (hwc) fit_hwc_launch(t->dtype, colour != 0, cubic, n, (hipStream_t)stream, fa);
+        else if (fit) fit_launch(layout, t->dtype, colour != 0, cubic, n, (hipStream_t)stream, fa);
+        else rois_launch(layout, t->dtype, colour != 0, cubic, n, (hipStream_t)stream, ra);
     });
 }
 

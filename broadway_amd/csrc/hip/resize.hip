@@ -12,10 +12,20 @@
 //   t   = (sum_k qx_k * s[row][k] + 128) >> 8          (6 fractional bits, 16 bits)
 //   out = (sum_l qy_l * t[l] + (1 << 19)) >> 20        (<= 255, no clamp)
 //
+// The bicubic filter (the kernel's CUBIC flag) is the same kernel
+// with other taps and signed passes: the Keys kernel with a = -0.5 over
+// |2 m k - C| < 2 R (at most 64 taps with n <= 16 m), its weights cut to 16 bits
+// by one shift, q by a floor division and possibly negative (resize_taps_cubic);
+// the tables and t are int16, the multiply-adds signed, t's shift arithmetic,
+// and the output is clamped to 0..255 (any sum |q| < 32768 keeps t in int16 and
+// the vertical sum in int32).  Without the flag the code is the triangle's,
+// instruction for instruction what it was before there was a second filter.
+//
 // A workgroup of 256 threads makes one RESIZE_TW x RESIZE_TH tile of one
 // picture's output:
 //   taps      lanes 0..47 of wave 0 derive first tap, count and the q of one
-//             tile column or row each (32-bit unsigned divisions) into LDS,
+//             tile column or row each (32-bit unsigned divisions; CUBIC: 64-bit
+//             multiply-adds and a shift per weight in front of them) into LDS,
 //             k-major, so that lanes over columns / rows read without conflicts;
 //   per chunk of 2..16 source rows (as many as the tile's source columns leave
 //   room for in the staging buffer):
@@ -27,7 +37,7 @@
 //             of a half-wave read different rows (odd pitch: different banks)
 //             of the same few columns; all planes of a pixel from one dword,
 //             four taps per iteration (the tables are zero-padded to that);
-//             t as uint16, [plane][column][row], columns 9 dwords apart;
+//             t as uint16 (CUBIC: int16), [plane][column][row], columns 9 dwords apart;
 //   vertical  one lane per (plane, output row, output column), 6 (RGB) or 2
 //             (GRAY) per thread, adds the chunk's rows of its taps to a 32-bit
 //             accumulator in a register;
@@ -48,12 +58,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "crop.hip"
 #include "tensor.hip"
 #define RESIZE_TW 32                // output columns of a tile
 #define RESIZE_TH 16                // output rows of a tile
 #define RESIZE_THREADS 256
-#define RESIZE_MAX_TAPS 64          // n <= 32 m
+#define RESIZE_MAX_TAPS 64          // n <= 32 m (triangle), n <= 16 m (bicubic)
 #define RESIZE_ROWS 16              // source rows per chunk, at most
 #define RESIZE_STAGE_DW 6144        // staging buffer; 2 rows of the widest tile (32 : 1) are 2130 dwords
 #define RESIZE_TPITCH (RESIZE_ROWS + 2)     // uint16 per column of t: 9 dwords
@@ -110,6 +121,55 @@ __device__ __forceinline__ void resize_taps(uint32_t n, uint32_t m, uint32_t j, 
     count = (int)k1 - (int)k0 + 1;
     if (count > 0) q[kmax * qpitch] = (uint16_t)((int32_t)q[kmax * qpitch] + rest);
     // (the horizontal pass takes its taps four at a time)
+    for (int k = count > 0 ? count : 0; k < ((count + 3) & ~3); k++) q[k * qpitch] = 0;
+}
+
+// The bicubic taps in the same form, q signed: source sample k is
+// kept where d = |2 m k - C| < 2 R and weighs the Keys kernel with a = -0.5 at
+// d / R, times 2 R^3 -- an integer polynomial, exact in 64 bits (d < 2^16, R <=
+// 2^15) -- shifted down by sh = max(0, bitlen(2 R^3) - 16) bits (floor), so
+// |w'| < 2^16 and everything after it is 32-bit; q_k = floor((w'_k * 16384 + W
+// / 2) / W) by one unsigned division on the numerator's magnitude.
+__device__ __forceinline__ int32_t resize_cubic_weight(uint32_t d, uint32_t R, int sh)
+{
+    const int64_t D = d, Rl = R, R3 = 2 * Rl * Rl * Rl;
+    const int64_t w = d < R ? (3 * D - 5 * Rl) * D * D + R3 : ((5 * Rl - D) * D - 8 * Rl * Rl) * D + 2 * R3;
+    return (int32_t)(w >> sh);
+}
+
+__device__ __forceinline__ void resize_taps_cubic(uint32_t n, uint32_t m, uint32_t j, int16_t *q, int qpitch, int &first,
+                                                  int &count)
+{
+    const uint32_t R = 2u * (m > n ? m : n), m2 = 2u * m;
+    const int32_t C = (int32_t)((2u * j + 1u) * n) - (int32_t)m;
+    int sh = 48 - (int)__builtin_clzll(2ull * R * R * R);
+    sh = sh > 0 ? sh : 0;
+    // kept: C - 2 R < 2 m k < C + 2 R
+    const int32_t lo = C - (int32_t)(2u * R);
+    const uint32_t k0 = lo < 0 ? 0u : (uint32_t)lo / m2 + 1u;
+    uint32_t k1 = ((uint32_t)(C + (int32_t)(2u * R)) - 1u) / m2;
+    k1 = k1 < n - 1u ? k1 : n - 1u;
+    int32_t W = 0, wmax = 0;
+    uint32_t kmax = 0;
+    for (uint32_t k = k0; k <= k1; k++) {
+        const int32_t d = (int32_t)(m2 * k) - C;
+        const int32_t w = resize_cubic_weight((uint32_t)(d < 0 ? -d : d), R, sh);
+        W += w;
+        if (w > wmax) { wmax = w; kmax = k - k0; }
+    }
+    int32_t rest = 16384;
+    for (uint32_t k = k0; k <= k1; k++) {
+        const int32_t d = (int32_t)(m2 * k) - C;
+        const int32_t num = resize_cubic_weight((uint32_t)(d < 0 ? -d : d), R, sh) * 16384 + (W >> 1);
+        // floor(num / W), W > 0: for a negative numerator, minus the magnitude's quotient rounded up
+        const uint32_t mag = ((uint32_t)(num < 0 ? -num : num) + (num < 0 ? (uint32_t)W - 1u : 0u)) / (uint32_t)W;
+        const int32_t qk = num < 0 ? -(int32_t)mag : (int32_t)mag;
+        q[(k - k0) * qpitch] = (int16_t)qk;
+        rest -= qk;
+    }
+    first = (int)k0;
+    count = (int)k1 - (int)k0 + 1;
+    if (count > 0) q[kmax * qpitch] = (int16_t)((int32_t)q[kmax * qpitch] + rest);
     for (int k = count > 0 ? count : 0; k < ((count + 3) & ~3); k++) q[k * qpitch] = 0;
 }
 
@@ -207,17 +267,22 @@ __device__ __forceinline__ const resize_args &resize_part(const rois_args &a) { 
 // of the tile), the rest of it is ka.pad.  HWC (RGB, with FIT -- the table form
 // serves every interleaved resized export, a stretch being a content that
 // fills the canvas): every store's index is the interleaved one, nothing else.
-template <int MODE, int DT, bool COL = false, bool ROIS = false, bool FIT = false, bool HWC = false>
+// CUBIC: resize_taps_cubic's taps, and with them signed tables,
+// a signed t, signed multiply-adds and a clamp at the end; everything else --
+// the stage, the chunks, the forms above, the stores -- does not know the filter.
+template <int MODE, int DT, bool COL = false, bool ROIS = false, bool FIT = false, bool HWC = false, bool CUBIC = false>
 __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename resize_kernel_args<ROIS, FIT>::type ka)
 {
     static_assert(ROIS || !FIT, "the placement is a per-row table, like the window");
     static_assert(!HWC || (FIT && MODE == TENSOR_RGB), "interleaved: RGB, and the table form only");
+    typedef typename std::conditional<CUBIC, int16_t, uint16_t>::type q_t;      // a tap, and t
+    typedef typename std::conditional<CUBIC, int32_t, uint32_t>::type acc_t;    // a sum of their products
     constexpr int NP = MODE == TENSOR_RGB ? 3 : 1;
     constexpr int NE = NP * RESIZE_TW * RESIZE_TH / RESIZE_THREADS;     // outputs per thread
     static_assert(RESIZE_TW == 32 && RESIZE_TH * RESIZE_TW == 2 * RESIZE_THREADS, "item -> (plane, row, column) below");
     __shared__ uint32_t stage[RESIZE_STAGE_DW + 4];         // (+ 4: the zero-weight taps behind the last row's last)
-    __shared__ uint16_t qx[RESIZE_MAX_TAPS * RESIZE_TW], qy[RESIZE_MAX_TAPS * RESIZE_TH];
-    __shared__ uint16_t tb[NP * RESIZE_TW * RESIZE_TPITCH];
+    __shared__ q_t qx[RESIZE_MAX_TAPS * RESIZE_TW], qy[RESIZE_MAX_TAPS * RESIZE_TH];
+    __shared__ q_t tb[NP * RESIZE_TW * RESIZE_TPITCH];
     __shared__ int fx[RESIZE_TW], cx[RESIZE_TW], fy[RESIZE_TH], cy[RESIZE_TH];
     const resize_args &ra = resize_part(ka);
     const int *win = nullptr;
@@ -257,10 +322,16 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
         const bool isx = tid < RESIZE_TW;
         const int l = isx ? tid : tid - RESIZE_TW;
         int f = 0, c = 0;
-        if (l >= (isx ? jx0 : iy0) && l < (isx ? jx1 : iy1))
-            resize_taps((uint32_t)(isx ? cw : ch), (uint32_t)(isx ? rw : rh),
-                        (uint32_t)((isx ? ox0 - px0 : oy0 - py0) + l), (isx ? qx : qy) + l,
-                        isx ? RESIZE_TW : RESIZE_TH, f, c);
+        if (l >= (isx ? jx0 : iy0) && l < (isx ? jx1 : iy1)) {
+            if constexpr (CUBIC)
+                resize_taps_cubic((uint32_t)(isx ? cw : ch), (uint32_t)(isx ? rw : rh),
+                                  (uint32_t)((isx ? ox0 - px0 : oy0 - py0) + l), (isx ? qx : qy) + l,
+                                  isx ? RESIZE_TW : RESIZE_TH, f, c);
+            else
+                resize_taps((uint32_t)(isx ? cw : ch), (uint32_t)(isx ? rw : rh),
+                            (uint32_t)((isx ? ox0 - px0 : oy0 - py0) + l), (isx ? qx : qy) + l,
+                            isx ? RESIZE_TW : RESIZE_TH, f, c);
+        }
         (isx ? fx : fy)[l] = f;
         (isx ? cx : cy)[l] = c;
     }
@@ -273,7 +344,7 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
     const int ys0 = fy[iy0] & ~1, ye = fy[iy1 - 1] + cy[iy1 - 1];
     int lrc = 4;                                    // log2 of the chunk's rows
     while (lrc > 1 && (pitch << lrc) > RESIZE_STAGE_DW) lrc--;
-    if ((pitch << lrc) > RESIZE_STAGE_DW) return;   // (not with n <= 32 m)
+    if ((pitch << lrc) > RESIZE_STAGE_DW) return;   // (not with n <= 32 m, nor with the bicubic's n <= 16 m)
     const int rc = 1 << lrc;
 
     const int x = ROIS ? win[0] : a.x, y = ROIS ? win[1] : a.y;
@@ -282,7 +353,7 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
     const uint8_t *V = U + (size_t)cpitch * (a.height >> 1);
     Y += (size_t)y * width + x;
 
-    uint32_t acc[NE];
+    acc_t acc[NE];
 #pragma unroll
     for (int e = 0; e < NE; e++) acc[e] = 0;
 
@@ -300,13 +371,14 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
             if (r >= nr || j < jx0 || j >= jx1) continue;
             const uint32_t *s = stage + r * pitch + (fx[j] - xs0);
             const int n = cx[j];
-            uint32_t h[NP];
+            acc_t h[NP];
 #pragma unroll
             for (int p = 0; p < NP; p++) h[p] = 0;
             // four taps at a time, their LDS reads in flight together; behind
             // the last tap: weight 0 times whatever the buffer holds
             for (int k = 0; k < n; k += 4) {
-                uint32_t px[4], q[4];
+                uint32_t px[4];
+                acc_t q[4];
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     px[u] = s[k + u];
@@ -315,10 +387,10 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
 #pragma unroll
                 for (int u = 0; u < 4; u++)
 #pragma unroll
-                    for (int p = 0; p < NP; p++) h[p] += q[u] * ((px[u] >> (8 * p)) & 255u);
+                    for (int p = 0; p < NP; p++) h[p] += q[u] * (acc_t)((px[u] >> (8 * p)) & 255u);
             }
 #pragma unroll
-            for (int p = 0; p < NP; p++) tb[(p * RESIZE_TW + j) * RESIZE_TPITCH + r] = (uint16_t)((h[p] + 128u) >> 8);
+            for (int p = 0; p < NP; p++) tb[(p * RESIZE_TW + j) * RESIZE_TPITCH + r] = (q_t)((h[p] + (acc_t)128) >> 8);
         }
         __syncthreads();
         // vertical: item tid + 256 e = (plane e >> 1, row (tid >> 5) + 8 (e & 1), column tid & 31):
@@ -329,8 +401,8 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
             if (i < iy0 || i >= iy1 || j < jx0 || j >= jx1) continue;
             const int f = fy[i];
             const int lo = f > r0 ? f : r0, hi = f + cy[i] < r0 + nr ? f + cy[i] : r0 + nr;
-            const uint16_t *t = tb + (p * RESIZE_TW + j) * RESIZE_TPITCH;
-            for (int row = lo; row < hi; row++) acc[e] += (uint32_t)qy[(row - f) * RESIZE_TH + i] * t[row - r0];
+            const q_t *t = tb + (p * RESIZE_TW + j) * RESIZE_TPITCH;
+            for (int row = lo; row < hi; row++) acc[e] += (acc_t)qy[(row - f) * RESIZE_TH + i] * (acc_t)t[row - r0];
         }
         // (the next chunk's stage writes only `stage`; its barrier orders this
         // chunk's reads of tb before the next horizontal pass)
@@ -341,7 +413,13 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
     for (int e = 0; e < NE; e++) {
         const int p = e >> 1, i = (tid >> 5) + 8 * (e & 1), j = tid & 31;
         if (i >= ny || j >= nx) continue;
-        uint32_t c = (acc[e] + (1u << 19)) >> 20;
+        uint32_t c;
+        if constexpr (CUBIC) {
+            const int32_t r = ((int32_t)acc[e] + (1 << 19)) >> 20;       // (arithmetic; the overshoot is cut here, once)
+            c = (uint32_t)(r < 0 ? 0 : r > 255 ? 255 : r);
+        } else {
+            c = ((uint32_t)acc[e] + (1u << 19)) >> 20;
+        }
         if constexpr (FIT)
             if (i < iy0 || i >= iy1 || j < jx0 || j >= jx1) c = ka.pad[p];
         const uint32_t v = tensor_elem<DT>(c, a.scale[p], a.bias[p]);
@@ -350,8 +428,9 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
     }
 }
 
-// the twelve instantiations by (mode, dt, col) with ROIS and FIT as given, over NROWS
-// grid rows of the tiles of (OH, OW); A: the kernel's arguments
+// the twelve instantiations by (mode, dt, col) with ROIS and FIT as given, each for the
+// triangle and (`cubic`) the bicubic filter, over NROWS grid rows of the tiles of
+// (OH, OW); A: the kernel's arguments
 #define RESIZE_LAUNCH(ROIS, FIT, NROWS, OW, OH, A)                                                                  \
     do {                                                                                                            \
         const unsigned ntx = (unsigned)((OW) + RESIZE_TW - 1) / RESIZE_TW;                                          \
@@ -365,38 +444,44 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
         RESIZE_CASE(ROIS, FIT, TENSOR_GRAY, TENSOR_BF16, A) RESIZE_CASE(ROIS, FIT, TENSOR_GRAY, TENSOR_F32, A)      \
     } while (0)
 #define RESIZE_CASE(ROIS, FIT, M, D, A)                                                                             \
-    if (mode == M && dt == D) hipLaunchKernelGGL((k_tensor_resize<M, D, false, ROIS, FIT>), grid, block, 0, st, A);
+    if (mode == M && dt == D) {                                                                                     \
+        if (cubic) hipLaunchKernelGGL((k_tensor_resize<M, D, false, ROIS, FIT, false, true>), grid, block, 0, st, A); \
+        else hipLaunchKernelGGL((k_tensor_resize<M, D, false, ROIS, FIT>), grid, block, 0, st, A);                  \
+    }
 #define RESIZE_COL_CASE(ROIS, FIT, D, A)                                                                            \
     if (mode == TENSOR_RGB && dt == D && col) {                                                                     \
-        hipLaunchKernelGGL((k_tensor_resize<TENSOR_RGB, D, true, ROIS, FIT>), grid, block, 0, st, A);               \
+        if (cubic) hipLaunchKernelGGL((k_tensor_resize<TENSOR_RGB, D, true, ROIS, FIT, false, true>), grid, block, 0, st, A); \
+        else hipLaunchKernelGGL((k_tensor_resize<TENSOR_RGB, D, true, ROIS, FIT>), grid, block, 0, st, A);          \
         return;                                                                                                     \
     }
 
-static void resize_launch(int mode, int dt, bool col, int npics, hipStream_t st, const resize_args &a)
+static void resize_launch(int mode, int dt, bool col, bool cubic, int npics, hipStream_t st, const resize_args &a)
 {
     RESIZE_LAUNCH(false, false, npics, a.ow, a.oh, a);
 }
 
 // nrois <= TENSOR_MAX_PICS boxes: a.win[r] and a.r.t.in_off[r], r < nrois
-static void rois_launch(int mode, int dt, bool col, int nrois, hipStream_t st, const rois_args &a)
+static void rois_launch(int mode, int dt, bool col, bool cubic, int nrois, hipStream_t st, const rois_args &a)
 {
     RESIZE_LAUNCH(true, false, nrois, a.r.ow, a.r.oh, a);
 }
 
 // the same, row r fitted into the canvas (a.r.oh, a.r.ow) at a.place[r]
-static void fit_launch(int mode, int dt, bool col, int nrois, hipStream_t st, const fit_args &a)
+static void fit_launch(int mode, int dt, bool col, bool cubic, int nrois, hipStream_t st, const fit_args &a)
 {
     RESIZE_LAUNCH(true, true, nrois, a.r.ow, a.r.oh, a);
 }
 
 // the same with the elements interleaved (RGB)
-static void fit_hwc_launch(int dt, bool col, int nrois, hipStream_t st, const fit_args &a)
+static void fit_hwc_launch(int dt, bool col, bool cubic, int nrois, hipStream_t st, const fit_args &a)
 {
     const unsigned ntx = (unsigned)(a.r.ow + RESIZE_TW - 1) / RESIZE_TW, nty = (unsigned)(a.r.oh + RESIZE_TH - 1) / RESIZE_TH;
     const dim3 grid(ntx * nty, nrois), block(RESIZE_THREADS);
 #define RESIZE_HWC_CASE(D, C)                                                                                       \
-    if (dt == D && col == C)                                                                                        \
-        hipLaunchKernelGGL((k_tensor_resize<TENSOR_RGB, D, C, true, true, true>), grid, block, 0, st, a);
+    if (dt == D && col == C) {                                                                                      \
+        if (cubic) hipLaunchKernelGGL((k_tensor_resize<TENSOR_RGB, D, C, true, true, true, true>), grid, block, 0, st, a); \
+        else hipLaunchKernelGGL((k_tensor_resize<TENSOR_RGB, D, C, true, true, true>), grid, block, 0, st, a);      \
+    }
     RESIZE_HWC_CASE(TENSOR_U8, false) RESIZE_HWC_CASE(TENSOR_F16, false) RESIZE_HWC_CASE(TENSOR_BF16, false)
     RESIZE_HWC_CASE(TENSOR_F32, false) RESIZE_HWC_CASE(TENSOR_U8, true) RESIZE_HWC_CASE(TENSOR_F16, true)
     RESIZE_HWC_CASE(TENSOR_BF16, true) RESIZE_HWC_CASE(TENSOR_F32, true)

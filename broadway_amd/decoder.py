@@ -28,7 +28,7 @@ of the wasm glue of Decoder/src/Decoder.c:44-162:
   delivers the whole picture.
 
 * ``tensor: true`` or ``tensor: {"dtype": ..., "mode": ..., "mean": ...,
-  "std": ..., "scale": ..., "bias": ..., "size": (oh, ow)}`` (an extension for
+  "std": ..., "scale": ..., "bias": ..., "size": (oh, ow), "filter": ...}`` (an extension for
   device consumers; needs torch, imported only on this path): nothing is
   copied to the host.
   ``onPictureDecoded(tensor, width, height, infos)`` receives a new
@@ -40,7 +40,9 @@ of the wasm glue of Decoder/src/Decoder.c:44-162:
   "topleft" | "stretch"`` and ``"pad": 114 | (r, g, b)`` it is fitted into
   the canvas ``size`` with its aspect ratio kept and the rest padded,
   ``H264SwDecNextPictureTensorFit``): the tensor is ``(planes, oh, ow)``
-  and the callback's width and height are ``ow`` and ``oh``.  It combines with
+  and the callback's width and height are ``ow`` and ``oh``; ``"filter":
+  "bicubic"`` (with ``size``) resizes with the antialiased bicubic filter
+  instead of the triangle (``Engine.to_tensor``).  It combines with
   neither ``rgb`` nor ``crop`` (ValueError).  ``colour`` picks the colour set
   of the R, G, B samples: "reference" (the default: BT.601 limited range, the
   values of ``rgb: true``), "bt601-full", "bt709", "bt709-full", or "stream"
@@ -186,7 +188,7 @@ class Decoder:
                 raise ValueError("tensor: not combinable with rgb or crop (mode='rgb' and the SPS window are part of it)")
             opts = {} if self._tensor is True else dict(self._tensor)
             unknown = set(opts) - {"dtype", "mode", "mean", "std", "scale", "bias", "size", "colour", "unspecified",
-                                   "fit", "pad", "layout"}
+                                   "fit", "pad", "layout", "filter"}
             if unknown:
                 raise ValueError(f"tensor: unknown keys {sorted(unknown)}")
             from .engine import fit_desc, layout_desc, tensor_desc, tensor_layout       # (imports torch)
@@ -380,7 +382,7 @@ class Decoder:
         self.onPictureDecoded(buf, w, h, infos)
 
     def rois(self, boxes, size, mode="rgb", dtype=None, mean=None, std=None, scale=None, bias=None, colour=None,
-             unspecified=None, fit=None, pad=None, layout="nchw"):
+             unspecified=None, fit=None, pad=None, layout="nchw", filter=None):
         """Boxes of the delivered picture as one new ``(K, planes, oh, ow)``
         torch tensor on the decoder's GPU, on torch's current stream
         (``H264SwDecLastPictureTensorRois``): ``boxes`` = [(x, y, cw, ch), ...]
@@ -396,13 +398,16 @@ class Decoder:
         aspect ratio kept (``H264SwDecLastPictureTensorRoisFit``), as for
         ``Engine.to_tensor``.  ``layout="nhwc"``: the same values stored
         channels-last (``H264SwDecLastPictureTensorRoisLayout``), the result
-        of the usual shape with channels_last strides.  ValueError for a bad argument,
+        of the usual shape with channels_last strides.  ``filter="bicubic"``:
+        every box through the antialiased bicubic filter (``Engine.to_tensor``)
+        instead of the triangle.  ValueError for a bad argument,
         RuntimeError before a picture was delivered."""
         from .engine import layout_desc, tensor_layout
         nhwc = tensor_layout(layout) != 0
         _, _, cw, ch = self._crop_window()
         desc, arr, planes, dtype = rois_args(boxes, size, cw, ch, mode=mode, dtype=dtype, mean=mean, std=std, scale=scale,
-                                             bias=bias, colour=colour, unspecified=unspecified, fit=fit, pad=pad)
+                                             bias=bias, colour=colour, unspecified=unspecified, fit=fit, pad=pad,
+                                             filter=filter)
         if not hasattr(self, "_device"):
             self._device = int(os.environ.get("H264MI_DEVICE") or 0)
         fitted = fit is not None or pad is not None

@@ -71,6 +71,28 @@ def _resize_size(size):
     return oh, ow
 
 
+def resize_filter(filter, size=True, what="filter") -> int:
+    """The ``h264mi_tensor_resize_desc.filter`` of ``filter``: None or
+    "triangle" (the antialiased triangle, torch's ``bilinear, antialias=True``)
+    or "bicubic" (Keys, a = -0.5, antialiased: PIL's BICUBIC, torch's ``bicubic,
+    antialias=True``).  A filter goes with a ``size`` (``size``
+    None or False: ValueError unless ``filter`` is None); ValueError for
+    anything else."""
+    if filter is None:
+        return _lib.RESIZE_TRIANGLE
+    if not isinstance(filter, str) or filter not in _lib.RESIZE_FILTERS:
+        raise ValueError(f"{what} {filter!r}: one of {sorted(_lib.RESIZE_FILTERS)}")
+    if size is None or size is False:
+        raise ValueError(f"{what}: goes with size=(oh, ow)")
+    return _lib.RESIZE_FILTERS[filter]
+
+
+def _no_filter(filter, what):
+    """The exports that have one filter only: ValueError for a ``filter``."""
+    if filter is not None:
+        raise ValueError(f"filter: {what} (only size=, rois= and fit= of to_tensor take one)")
+
+
 def _field_resized(resized, built, size):
     """A field descriptor triple ``built`` with its descriptor wrapped into the
     resize descriptor ``resized`` (``f``, then ow, oh and the filter) of
@@ -135,7 +157,7 @@ def check_out(out, shape, dtype, device, layout="nchw"):
 
 
 def tensor_desc(window, mode="rgb", dtype=None, scale=None, bias=None, mean=None, std=None, size=None, colour=None,
-                unspecified=None, stream_ok=False, layout=None):
+                unspecified=None, stream_ok=False, layout=None, filter=None):
     """(``_lib.TensorDesc``, planes, torch dtype) of a tensor export
     (Engine.to_tensor, Decoder's ``tensor`` option); window = (x, y, cw, ch),
     or None for the decoder's SPS crop window (cw = 0 in the descriptor).
@@ -144,17 +166,21 @@ def tensor_desc(window, mode="rgb", dtype=None, scale=None, bias=None, mean=None
     above).  ``colour``: the colour set of the R, G, B samples
     (``tensor_colour_bits``; None: the reference's BT.601 limited range).
     ``layout`` "nchw" or "nhwc" (not None): the descriptor is the
-    ``_lib.TensorLayoutDesc`` (``layout_desc``) of the one above."""
+    ``_lib.TensorLayoutDesc`` (``layout_desc``) of the one above.  ``filter``
+    (with ``size`` only): "triangle", the default, or "bicubic"
+    (``resize_filter``; a window at most 16 times the output on each axis)."""
     import torch
     if layout is not None:
         tensor_layout(layout)
-        d, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std, size, colour, unspecified, stream_ok)
+        d, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std, size, colour, unspecified, stream_ok,
+                                       filter=filter)
         return layout_desc(d, layout), planes, dtype
+    filt = resize_filter(filter, size)
     if size is not None:
         oh, ow = _resize_size(size)
         t, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std, None, colour, unspecified, stream_ok)
         d = _lib.TensorResizeDesc()
-        d.t, d.ow, d.oh, d.filter = t, ow, oh, _lib.RESIZE_TRIANGLE
+        d.t, d.ow, d.oh, d.filter = t, ow, oh, filt
         return d, planes, dtype
     dtype = torch.float16 if dtype is None else dtype
     dts = {torch.uint8: _lib.TENSOR_U8, torch.float16: _lib.TENSOR_F16, torch.bfloat16: _lib.TENSOR_BF16,
@@ -278,7 +304,7 @@ def snap_rois(boxes, width: int, height: int):
 
 
 def rois_desc(rois, size, npics, width, height, mode="rgb", dtype=None, scale=None, bias=None, mean=None, std=None,
-              colour=None, unspecified=None, stream_ok=False, fit=None, pad=None, layout=None):
+              colour=None, unspecified=None, stream_ok=False, fit=None, pad=None, layout=None, filter=None):
     """(``_lib.TensorResizeDesc`` with a zero window, ``_lib.Roi`` array, planes,
     torch dtype) of a region-of-interest export (Engine.to_tensor(rois=),
     Decoder.rois): ``rois`` = [(k, x, y, cw, ch), ...] over ``npics`` pictures
@@ -289,17 +315,19 @@ def rois_desc(rois, size, npics, width, height, mode="rgb", dtype=None, scale=No
     ``_lib.TensorFitDesc`` of the letterboxed export (``fit_desc``): every box
     gets its own fit into ``size``, and the 32 samples per output are judged
     against its content size.  With ``layout`` (not None) the descriptor is
-    the ``_lib.TensorLayoutDesc`` of that one.  ValueError otherwise."""
+    the ``_lib.TensorLayoutDesc`` of that one.  ``filter`` "triangle" (default)
+    or "bicubic": the 32 samples per output are 16 under "bicubic".  ValueError
+    otherwise."""
     if layout is not None:
         tensor_layout(layout)
         desc, arr, planes, dtype = rois_desc(rois, size, npics, width, height, mode, dtype, scale, bias, mean, std,
-                                             colour, unspecified, stream_ok, fit, pad)
+                                             colour, unspecified, stream_ok, fit, pad, filter=filter)
         return layout_desc(desc, layout), arr, planes, dtype
     if size is None:
         raise ValueError("rois: goes with size=(oh, ow)")
     desc, planes, dtype = tensor_desc((0, 0, 0, 0), mode, dtype, scale, bias, mean, std, size, colour, unspecified,
-                                      stream_ok)
-    oh, ow = desc.oh, desc.ow
+                                      stream_ok, filter=filter)
+    oh, ow, ratio = desc.oh, desc.ow, _lib.RESIZE_MAX_RATIO[desc.filter]
     if fit is not None or pad is not None:
         fit = "letterbox" if fit is None else fit
         desc = fit_desc(desc, planes, fit, 114 if pad is None else pad)
@@ -320,8 +348,8 @@ def rois_desc(rois, size, npics, width, height, mode="rgb", dtype=None, scale=No
         if cw > _lib.RESIZE_MAX_DIM or ch > _lib.RESIZE_MAX_DIM:
             raise ValueError(f"rois: box {(k, x, y, cw, ch)}: at most {_lib.RESIZE_MAX_DIM} a side")
         rw, rh = (ow, oh) if fit is None else letterbox_fit(cw, ch, (oh, ow), fit)[:2]
-        if cw > 32 * rw or ch > 32 * rh or rw > ow or rh > oh:
-            raise ValueError(f"rois: box {(k, x, y, cw, ch)}: at most 32 times the size {(rh, rw)} on each axis")
+        if cw > ratio * rw or ch > ratio * rh or rw > ow or rh > oh:
+            raise ValueError(f"rois: box {(k, x, y, cw, ch)}: at most {ratio} times the size {(rh, rw)} on each axis")
     arr = (_lib.Roi * len(boxes))(*[_lib.Roi(*b) for b in boxes])
     return desc, arr, planes, dtype
 
@@ -794,7 +822,7 @@ class Engine:
 
     def to_tensor(self, streams: Sequence[int], slots: Sequence[int], window=None, mode: str = "rgb", dtype=None,
                   scale=None, bias=None, mean=None, std=None, out=None, stream=None, size=None, colour=None,
-                  rois=None, fit=None, pad=None, layout="nchw", warps=None, border=None):
+                  rois=None, fit=None, pad=None, layout="nchw", warps=None, border=None, filter=None):
         """The slots (streams[k], slots[k]) as one ``(n, planes, ch, cw)``
         torch tensor on ``cuda:{self.device}``, built on the GPU and never
         copied to the host: planes R, G, B (``mode="rgb"``, the values of
@@ -808,6 +836,13 @@ class Engine:
         resized on the GPU before that conversion (antialiased triangle
         filter in integer arithmetic; a window at most 32 times
         the output on each axis) -- the result is ``(n, planes, oh, ow)``.
+        ``filter`` (with ``size``; every form below but ``warps``):
+        "triangle", that default, or "bicubic" -- the antialiased bicubic
+        filter (Keys, a = -0.5) of PIL's BICUBIC and torch's ``bicubic,
+        antialias=True``, what CLIP / SigLIP / DINOv2-style encoders and the
+        timm ViT transforms resize with, in integer arithmetic and
+        reproducible to the byte; a window at most 16 times the
+        output on each axis.
         ``colour`` (``mode="rgb"`` only): the colour set of the R, G, B
         samples -- None / "reference" (BT.601 limited range, the values of
         read_rgba), "bt601-full", "bt709" or "bt709-full" (DESIGN 3.5f); the
@@ -868,6 +903,7 @@ class Engine:
         if warps is None and border is not None:
             raise ValueError("border: goes with warps")
         if warps is not None:
+            _no_filter(filter, "warps are sampled bilinearly")
             if rois is not None or fit is not None:
                 raise ValueError("warps: not combinable with rois or fit")
             if window is None:
@@ -888,7 +924,7 @@ class Engine:
             if window is not None:
                 raise ValueError("rois: not combinable with window (each box is one)")
             desc, boxes, planes, dtype = rois_desc(rois, size, n, self.w_mbs * 16, self.h_mbs * 16, mode, dtype, scale,
-                                                   bias, mean, std, colour, fit=fit, pad=pad)
+                                                   bias, mean, std, colour, fit=fit, pad=pad, filter=filter)
             name = "h264mi_engine_export_tensor_rois_fit" if fitted else "h264mi_engine_export_tensor_rois"
             oh, ow = (desc.r.oh, desc.r.ow) if fitted else (desc.oh, desc.ow)
             if nhwc:
@@ -902,7 +938,7 @@ class Engine:
             return out
         if window is None:
             window = (0, 0, self.w_mbs * 16, self.h_mbs * 16)
-        desc, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std, size, colour)
+        desc, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std, size, colour, filter=filter)
         if fitted:
             fd = fit_desc(desc, planes, "letterbox" if fit is None else fit, 114 if pad is None else pad)
             if nhwc:
@@ -1003,7 +1039,7 @@ class Engine:
             raise RuntimeError("h264mi_engine_keep_accmv failed")
 
     def to_accmv(self, streams: Sequence[int], slots: Sequence[int], channels=("adx", "ady"), window=None,
-                 dtype=None, scale=None, bias=None, out=None, stream=None, size=None):
+                 dtype=None, scale=None, bias=None, out=None, stream=None, size=None, filter=None):
         """The accumulated motion of the pictures last decoded into the slots
         (streams[k], slots[k]) as one ``(n, C, ch, cw)`` torch tensor on
         ``cuda:{self.device}``, one element per luma sample of ``window`` = (x,
@@ -1014,7 +1050,9 @@ class Engine:
         resized on the GPU before the conversion (``accmv_desc``; a window at
         most 32 times the output and 16384 samples on each axis) -- the result
         is ``(n, C, oh, ow)``.  ``out`` and ``stream`` as for ``to_tensor``;
-        the host is never synchronised."""
+        the host is never synchronised.  (``filter``: ValueError; a field has
+        the triangle only.)"""
+        _no_filter(filter, "the accumulated motion is resized by the triangle")
         entry = "h264mi_engine_export_accmv" if size is None else "h264mi_engine_export_accmv_resized"
         return self._export_field(entry, "keep_accmv", streams, slots, window,
                                   lambda w: accmv_desc(channels, w, dtype, scale, bias, size), out, stream)
@@ -1052,7 +1090,8 @@ class Engine:
         return bool(r)
 
     def to_accres(self, streams: Sequence[int], slots: Sequence[int], planes="y", window=None, dtype=None,
-                  scale=None, bias=None, colour=None, unanchored="key", out=None, stream=None, size=None):
+                  scale=None, bias=None, colour=None, unanchored="key", out=None, stream=None, size=None,
+                  filter=None):
         """The accumulated residual of the pictures last decoded into the slots
         (streams[k], slots[k]) -- each sample minus its origin in the key
         picture of its GOP -- as one ``(n, 1 | 2 | 3, rows, columns)`` torch
@@ -1063,7 +1102,9 @@ class Engine:
         reads as zeros).  Needs ``keep_accmv()`` and ``keep_accres()`` before
         the decodes.  ``size`` = (oh, ow): each plane resized on the GPU as for
         ``to_accmv`` -- the result is ``(n, 1 | 2 | 3, oh, ow)``.  ``out`` and
-        ``stream`` as for ``to_tensor``; the host is never synchronised."""
+        ``stream`` as for ``to_tensor``; the host is never synchronised.
+        (``filter``: ValueError, as for ``to_accmv``.)"""
+        _no_filter(filter, "the accumulated residual is resized by the triangle")
         entry = "h264mi_engine_export_accres" if size is None else "h264mi_engine_export_accres_resized"
         return self._export_field(entry, "keep_accres", streams, slots, window,
                                   lambda w: accres_desc(planes, w, dtype, scale, bias, colour, unanchored, size), out,

@@ -204,8 +204,32 @@ H264SwDecRet H264SwDecNextPictureTensor(H264SwDecInst decInst, H264SwDecPicture 
  * widened by the ratio when downscaling, at most 32 source samples per output
  * and axis --, then converted as above: (3 | 1, oh, ow) elements.  With (oh,
  * ow) == (ch, cw) the bytes are those of the unresized tensor.  `filter` is
- * H264MI_RESIZE_TRIANGLE; other values are refused. */
-enum { H264MI_RESIZE_TRIANGLE = 0 };
+ * H264MI_RESIZE_TRIANGLE or H264MI_RESIZE_BICUBIC; other values (1 and -1
+ * among them: reserved) are refused.
+ *
+ * H264MI_RESIZE_BICUBIC is the antialiased bicubic filter of PIL's
+ * BICUBIC and torch's F.interpolate(mode="bicubic", antialias=True): the Keys
+ * kernel with a = -0.5, its support stretched by the ratio when downscaling, at
+ * most 16 source samples per output and axis (64 taps), in integers.  One
+ * axis, n source samples -> m outputs (the mapping is the triangle's):
+ *   R = 2 max(m, n); output j has C = (2 j + 1) n - m; source sample k, 0 <= k
+ *   < n, is at distance d = |2 m k - C| and is kept where d < 2 R (taps outside
+ *   the window are dropped, not clamped; zero weights at d == R are kept);
+ *   w  = 3 d^3 - 5 R d^2 + 2 R^3              (d < R)
+ *      = -d^3 + 5 R d^2 - 8 R^2 d + 4 R^3     (R <= d < 2 R)     exact in 64 bits;
+ *   w' = w >> s, s = max(0, bitlen(2 R^3) - 16) (arithmetic shift: floor);
+ *   W  = sum w' (> 0);  q_k = floor((w'_k 16384 + W / 2) / W), which may be
+ *   negative; 16384 - sum q_k is added to the first tap of largest w'.
+ * Two passes, signed, with one clamp at the end:
+ *   t   = (sum_k qx_k s[row][k] + 128) >> 8                 (arithmetic; an int16)
+ *   out = clamp((sum_l qy_l t[l] + (1 << 19)) >> 20, 0, 255)
+ * It is within 0.5 + 1/32 of that torch operator in float64, clamped to 0 ..
+ * 255, and (oh, ow) == (ch, cw) still gives the unresized tensor's bytes.
+ * Everywhere below, "32 source samples per output and axis" is 16 under this
+ * filter.  The letterbox fit (h264mi_letterbox_fit) is the same function for
+ * both filters -- its minor axis is raised to ceil(n / 32) --, so a window whose
+ * fitted content would exceed 16 : 1 on an axis is refused under BICUBIC. */
+enum { H264MI_RESIZE_TRIANGLE = 0, H264MI_RESIZE_BICUBIC = 2 };
 typedef struct { h264mi_tensor_desc t; int ow, oh, filter; } h264mi_tensor_resize_desc;
 /* NextPictureTensor with the resized tensor of `desc` (not NULL) at d_dst;
  * desc->t.cw == 0 takes the active SPS's crop window.  Otherwise as above. */
@@ -575,7 +599,8 @@ typedef struct {
  * exact), converted as for h264mi_tensor_desc; U8 is refused.  With (oh, ow) ==
  * the grid every output has the single tap 16384, r = 16 s, and the bytes are
  * the unresized export's.
- * Rules: f's own; filter == H264MI_RESIZE_TRIANGLE; 1 <= ow, oh <= 16384; the
+ * Rules: f's own; filter == H264MI_RESIZE_TRIANGLE (the fields have no bicubic
+ * form: H264MI_RESIZE_BICUBIC is refused here); 1 <= ow, oh <= 16384; the
  * source grid at most 16384 a side and at most 32 ow by 32 oh. */
 typedef struct { h264mi_accmv_desc  f; int ow, oh, filter; } h264mi_accmv_resize_desc;
 typedef struct { h264mi_accres_desc f; int ow, oh, filter; } h264mi_accres_resize_desc;
@@ -784,8 +809,9 @@ int  h264mi_engine_export_tensor(h264mi_engine *e, int n, const int *streams, co
  * picture k's (planes, oh, ow) elements at d_out + k * out_stride, nothing
  * else written.  Stateless (the filter taps are derived in the kernel): no
  * device allocation, no copy, no host synchronisation.  -1, nothing launched,
- * also for ow or oh outside 1 .. 16384, a window more than 32 times the output
- * on an axis, or filter != H264MI_RESIZE_TRIANGLE. */
+ * also for ow or oh outside 1 .. 16384, a window more than 32 times
+ * (H264MI_RESIZE_BICUBIC: 16 times) the output on an axis, or a filter that is
+ * neither H264MI_RESIZE_TRIANGLE nor H264MI_RESIZE_BICUBIC. */
 int  h264mi_tensor_resize_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width, int height,
                                        int cpitch, const h264mi_tensor_resize_desc *desc, void *d_out,
                                        size_t out_stride, void *hip_stream);
