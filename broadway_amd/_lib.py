@@ -104,6 +104,12 @@ class TensorLayoutDesc(C.Structure):
     _fields_ = [("f", TensorFitDesc), ("layout", C.c_int)]
 
 
+class TensorDest(C.Structure):
+    """h264mi_tensor_dest (include/h264mi.h): a pixel export's strides, in bytes."""
+    _fields_ = [("row", C.c_int64), ("plane", C.c_int64), ("frame", C.c_int64), ("clip", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class Warp(C.Structure):
     """h264mi_warp (include/h264mi.h)."""
     _fields_ = [("pic", C.c_int), ("m", C.c_int * 6)]
@@ -362,6 +368,21 @@ def mi() -> C.CDLL:
         L.h264mi_engine_export_tensor_warps.restype = i32
         L.H264SwDecLastPictureTensorWarps.argtypes = [vp, wd, wa, u32, vp, vp]
         L.H264SwDecLastPictureTensorWarps.restype = i32
+    if hasattr(L, "h264mi_tensor_dest_device_pitch"):       # (optional, as above)
+        ld, ro, de = C.POINTER(TensorLayoutDesc), C.POINTER(Roi), C.POINTER(TensorDest)
+        wd, wa = C.POINTER(TensorWarpDesc), C.POINTER(Warp)
+        L.h264mi_tensor_dest_device_pitch.argtypes = [vp, C.POINTER(sz), i32, i32, i32, i32, ld, ro, i32, de, vp, sz, vp]
+        L.h264mi_tensor_dest_device_pitch.restype = i32
+        L.h264mi_tensor_warps_dest_device_pitch.argtypes = [vp, C.POINTER(sz), i32, i32, i32, i32, wd, wa, i32, de, vp, sz,
+                                                            vp]
+        L.h264mi_tensor_warps_dest_device_pitch.restype = i32
+        L.h264mi_engine_export_tensor_dest.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), ld, ro, i32, de, vp, sz, vp]
+        L.h264mi_engine_export_tensor_dest.restype = i32
+        L.h264mi_engine_export_tensor_warps_dest.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), wd, wa, i32, de, vp,
+                                                             sz, vp]
+        L.h264mi_engine_export_tensor_warps_dest.restype = i32
+        L.H264SwDecNextPictureTensorDest.argtypes = [vp, C.POINTER(H264SwDecPicture), u32, ld, de, vp, vp]
+        L.H264SwDecNextPictureTensorDest.restype = i32
     if hasattr(L, "h264mi_mbinfo_device"):                  # (optional, as above)
         md = C.POINTER(MbInfoDesc)
         L.h264mi_mbinfo_device.argtypes = [vp, C.POINTER(sz), i32, i32, i32, md, vp, sz, vp]

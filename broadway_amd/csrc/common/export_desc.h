@@ -229,6 +229,65 @@ static inline int warps_ok(const h264mi_warp *w, int nwarps, int npics)
     return 1;
 }
 
+/* h264mi_tensor_dest over items of planes x rows x cols elements
+ * of es bytes: the strides an export runs with, the descriptor's zeros filled
+ * in (NULL: the packed item, one item per clip) */
+typedef struct { int64_t row, plane, frame; int clip; } export_dest;
+
+static inline export_dest dest_resolve(const h264mi_tensor_dest *d, size_t es, int planes, int rows, int cols,
+                                       int interleaved)
+{
+    export_dest o;
+    const int64_t packed = (int64_t)cols * (int64_t)es * (interleaved ? planes : 1);
+    o.row = d && d->row ? d->row : packed;
+    o.plane = interleaved ? 0 : d && d->plane ? d->plane : (int64_t)rows * o.row;
+    o.frame = d ? d->frame : 0;
+    o.clip = d ? d->clip : 1;
+    return o;
+}
+
+/* what the rules of include/h264mi.h say of the descriptor alone, whatever the
+ * items are: no negative stride, a clip, nothing reserved, no frame stride
+ * without a clip, and no plane stride under an interleaved layout.  api.c
+ * refuses on these before it looks for headers. */
+static inline int dest_fixed_ok(const h264mi_tensor_dest *d, int interleaved)
+{
+    return !d || (d->row >= 0 && d->plane >= 0 && d->frame >= 0 && d->clip >= 1 && d->reserved == 0 &&
+                  (d->clip > 1 || d->frame == 0) && (!interleaved || d->plane == 0));
+}
+
+/* the rules of include/h264mi.h for nitems items out_stride apart (dest_fixed_ok
+ * among them).  The levels with more than one element, sorted by stride (at
+ * most four: an insertion sort), must each step over the span of those below;
+ * a span that does not fit 63 bits is refused -- a row whose rows * row does
+ * not, before dest_resolve multiplies them. */
+static inline int dest_ok(const h264mi_tensor_dest *d, size_t es, int planes, int rows, int cols, int interleaved,
+                          int nitems, size_t out_stride)
+{
+    if (es < 1 || planes < 1 || rows < 1 || cols < 1 || nitems < 1 || out_stride > (size_t)INT64_MAX) return 0;
+    if (!dest_fixed_ok(d, interleaved) || (d && d->row > INT64_MAX / rows)) return 0;
+    const export_dest r = dest_resolve(d, es, planes, rows, cols, interleaved);
+    const int64_t e = (int64_t)es, packed = (int64_t)cols * e * (interleaved ? planes : 1);
+    if (r.row % e || r.plane % e || r.frame % e || (int64_t)out_stride % e) return 0;
+    if (r.row < packed || nitems % r.clip) return 0;
+    int64_t stride[4], count[4];
+    int n = 0;
+    const int64_t ls[4] = {r.row, r.plane, r.frame, (int64_t)out_stride};
+    const int64_t lc[4] = {rows, interleaved ? 1 : planes, r.clip, nitems / r.clip};
+    for (int l = 0; l < 4; l++) {
+        if (lc[l] < 2) continue;
+        int k = n++;
+        for (; k > 0 && stride[k - 1] > ls[l]; k--) { stride[k] = stride[k - 1]; count[k] = count[k - 1]; }
+        stride[k] = ls[l]; count[k] = lc[l];
+    }
+    int64_t span = packed;
+    for (int k = 0; k < n; k++) {
+        if (stride[k] < span || stride[k] > (INT64_MAX - span) / (count[k] - 1)) return 0;
+        span += (count[k] - 1) * stride[k];
+    }
+    return 1;
+}
+
 /* h264mi_mbinfo_desc: the window is in 4x4 blocks of a w_mbs x h_mbs picture */
 static inline int mbinfo_desc_fixed_ok(const h264mi_mbinfo_desc *d)
 {

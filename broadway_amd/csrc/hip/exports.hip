@@ -348,13 +348,49 @@ static int export_launches(int npics, const size_t *offsets, unsigned long long 
     return 0;
 }
 
+// The launches of a pixel export (k_tensor, k_tensor_resize, k_tensor_warp)
+// over nitems items under the resolved destination `ds`: as
+// export_launches, but an item is placed by the descriptor -- a.out is d_out
+// for every launch and grid row k's item starts a.out_off[k] bytes behind it,
+// so a launch may begin and end inside a clip.  Fills a.row and a.plane.
+template <class Launch>
+static int dest_launches(int nitems, const size_t *offsets, tensor_args &a, void *d_out, size_t out_stride,
+                         const export_dest &ds, Launch launch)
+{
+    a.out = (uint8_t *)d_out;
+    a.row = (size_t)ds.row;
+    a.plane = (size_t)ds.plane;
+    for (int k0 = 0; k0 < nitems; k0 += EXPORT_MAX_PICS) {
+        const int n = nitems - k0 < EXPORT_MAX_PICS ? nitems - k0 : EXPORT_MAX_PICS;
+        for (int k = 0; k < EXPORT_MAX_PICS; k++) {
+            const size_t item = (size_t)(k0 + k);
+            a.in_off[k] = k < n ? offsets[k0 + k] : 0;
+            a.out_off[k] = k < n ? (item / (size_t)ds.clip) * out_stride + (item % (size_t)ds.clip) * (size_t)ds.frame : 0;
+        }
+        launch(k0, n);
+        HIPCHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+// k_tensor may store 16 bytes at a time under a destination: d_out, the
+// distances between clips, items, planes and rows, and the packed row
+static bool dest_v16(const void *d_out, size_t out_stride, const export_dest &ds, size_t row_bytes)
+{
+    return export_v16(d_out, out_stride, row_bytes) && !(((size_t)ds.frame | (size_t)ds.plane | (size_t)ds.row) & 15);
+}
+
 // Both tensor exports (r != NULL: resized, t = &r->t): one check and one fill
-// of what their kernels share, resize_args::t.  hwc (unresized RGB only, from
-// h264mi_tensor_layout_device_pitch): the elements interleaved, and a row is
-// 3 cw elements
+// of what their kernels share, resize_args::t.  interleaved and dest (unresized
+// only, from h264mi_tensor_dest_device_pitch): the layout -- RGB: the elements
+// interleaved, a row 3 cw elements; GRAY: the same bytes either way -- and the
+// destination (NULL: packed items out_stride apart), judged here, behind the
+// descriptor it depends on and ahead of the launches.  The resized form is the
+// single-window kernel's: planar, packed pictures out_stride apart.
 static int tensor_device(const void *d_in, const size_t *in_offsets, int npics, int width, int height, int cpitch,
                          const h264mi_tensor_desc *t, const h264mi_tensor_resize_desc *r, void *d_out,
-                         size_t out_stride, hipStream_t stream, bool hwc = false)
+                         size_t out_stride, hipStream_t stream, bool interleaved = false,
+                         const h264mi_tensor_dest *dest = NULL)
 {
     static_assert(H264MI_TENSOR_RGB == TENSOR_RGB && H264MI_TENSOR_GRAY == TENSOR_GRAY &&
                       H264MI_TENSOR_U8 == TENSOR_U8 && H264MI_TENSOR_F16 == TENSOR_F16 &&
@@ -366,22 +402,30 @@ static int tensor_device(const void *d_in, const size_t *in_offsets, int npics, 
         return -1;
     const size_t es = export_elem_size(t->dtype);
     if (!export_aligned(d_out, out_stride, es)) return -1;
-    const bool v16 = export_v16(d_out, out_stride, (size_t)t->cw * es * (hwc ? 3 : 1));
     const int layout = H264MI_TENSOR_LAYOUT(t->mode), colour = H264MI_TENSOR_COLOUR(t->mode);
-    if (hwc && (r || layout != H264MI_TENSOR_RGB)) return -1;
+    if (r && (interleaved || dest)) return -1;
+    const bool hwc = interleaved && layout == H264MI_TENSOR_RGB;
     resize_args ra;
     tensor_args &a = ra.t;
     a.in = (const uint8_t *)d_in;
     a.width = width; a.height = height; a.cpitch = cpitch;
     a.x = t->x; a.y = t->y; a.cw = t->cw; a.ch = t->ch;
-    a.out_stride = out_stride;
     for (int p = 0; p < 3; p++) { a.scale[p] = t->scale[p]; a.bias[p] = t->bias[p]; }
     a.col = tensor_colour_sets[colour];     // (set 0 runs the kernels with the reference's literals)
     if (r) { ra.ow = r->ow; ra.oh = r->oh; }
     const bool cubic = r && r->filter == H264MI_RESIZE_BICUBIC;
-    return export_launches(npics, in_offsets, a.in_off, &a.out, d_out, out_stride, [&](int, int n) {
-        if (r) resize_launch(layout, t->dtype, colour != 0, cubic, n, stream, ra);
-        else tensor_launch(layout, t->dtype, v16, colour != 0, hwc, n, stream, a);
+    if (r) {
+        a.out_stride = out_stride;
+        a.row = a.plane = 0;
+        return export_launches(npics, in_offsets, a.in_off, &a.out, d_out, out_stride,
+                               [&](int, int n) { resize_launch(layout, t->dtype, colour != 0, cubic, n, stream, ra); });
+    }
+    if (dest && !dest_ok(dest, es, layout == H264MI_TENSOR_RGB ? 3 : 1, t->ch, t->cw, interleaved, npics, out_stride)) return -1;
+    const export_dest ds = dest_resolve(dest, es, layout == H264MI_TENSOR_RGB ? 3 : 1, t->ch, t->cw, interleaved);
+    const bool v16 = dest_v16(d_out, out_stride, ds, (size_t)t->cw * es * (hwc ? 3 : 1));
+    a.out_stride = 0;
+    return dest_launches(npics, in_offsets, a, d_out, out_stride, ds, [&](int, int n) {
+        tensor_launch(layout, t->dtype, v16, colour != 0, hwc, n, stream, a);
     });
 }
 
@@ -438,20 +482,25 @@ static bool rois_desc_ok(const h264mi_tensor_resize_desc *d, const h264mi_roi *r
 static int rois_device(const void *d_in, const size_t *in_offsets, int npics, int width, int height, int cpitch,
                        const h264mi_tensor_resize_desc *desc, const h264mi_tensor_fit_desc *fit,
                        const h264mi_tensor_desc *whole, const h264mi_roi *rois, int nrois, void *d_out,
-                       size_t out_stride, void *stream, bool hwc = false)
+                       size_t out_stride, void *stream, bool hwc = false, const h264mi_tensor_dest *dest = NULL,
+                       bool interleaved = false)
 {
     const h264mi_tensor_desc *t = &desc->t;
     if (hwc && (!fit || H264MI_TENSOR_LAYOUT(t->mode) != H264MI_TENSOR_RGB)) return -1;
     // (d_out is checked here too: a list is one lookup, and a host address would fault every launch of it)
     if (!export_aligned(d_out, out_stride, export_elem_size(t->dtype)) || h264mi_pointer_device(d_out) < 0) return -1;
     const int layout = H264MI_TENSOR_LAYOUT(t->mode), colour = H264MI_TENSOR_COLOUR(t->mode);
+    const int planes = layout == H264MI_TENSOR_RGB ? 3 : 1;
+    if (dest && !dest_ok(dest, export_elem_size(t->dtype), planes, desc->oh, desc->ow, interleaved || hwc, nrois, out_stride))
+        return -1;
+    const export_dest ds = dest_resolve(dest, export_elem_size(t->dtype), planes, desc->oh, desc->ow, interleaved || hwc);
     fit_args fa;
     rois_args &ra = fa;
     tensor_args &a = ra.r.t;
     a.in = (const uint8_t *)d_in;
     a.width = width; a.height = height; a.cpitch = cpitch;
     a.x = a.y = a.cw = a.ch = 0;
-    a.out_stride = out_stride;
+    a.out_stride = 0;
     for (int p = 0; p < 3; p++) { a.scale[p] = t->scale[p]; a.bias[p] = t->bias[p]; }
     a.col = tensor_colour_sets[colour];
     ra.r.ow = desc->ow; ra.r.oh = desc->oh;
@@ -460,7 +509,7 @@ static int rois_device(const void *d_in, const size_t *in_offsets, int npics, in
         for (int p = 0; p < 3; p++) fa.pad[p] = fit->pad[p];
     std::vector<size_t> off((size_t)nrois);
     for (int r = 0; r < nrois; r++) off[r] = in_offsets[whole ? r : rois[r].pic];
-    return export_launches(nrois, off.data(), a.in_off, &a.out, d_out, out_stride, [&](int r0, int n) {
+    return dest_launches(nrois, off.data(), a, d_out, out_stride, ds, [&](int r0, int n) {
         for (int r = 0; r < EXPORT_MAX_PICS; r++) {
             const h264mi_roi w = {0, t->x, t->y, t->cw, t->ch};
             const h264mi_roi &b = whole ? w : rois[r0 + (r < n ? r : 0)];
@@ -562,25 +611,39 @@ static bool layout_desc_ok(const h264mi_tensor_layout_desc *d, const h264mi_roi 
     return layout_desc_fixed_ok(d) && layout_window_ok(d, width, height);
 }
 
-extern "C" int h264mi_tensor_layout_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width,
-                                                 int height, int cpitch, const h264mi_tensor_layout_desc *desc,
-                                                 const h264mi_roi *rois, int nrois, void *d_out, size_t out_stride,
-                                                 void *stream)
+//  ... into a strided destination: dest (NULL: packed items
+// out_stride apart, the layout call) is judged by dest_ok with the call's items
+// where the launches are made, behind every other check and ahead of the first.
+extern "C" int h264mi_tensor_dest_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width,
+                                               int height, int cpitch, const h264mi_tensor_layout_desc *desc,
+                                               const h264mi_roi *rois, int nrois, const h264mi_tensor_dest *dest,
+                                               void *d_out, size_t out_stride, void *stream)
 {
     if (!tensor_pics_ok(d_in, in_offsets, npics, width, height, cpitch, d_out) ||
         !layout_desc_ok(desc, rois, nrois, npics, width, height))
         return -1;
     const h264mi_tensor_fit_desc *f = &desc->f;
-    const bool hwc = desc->layout == H264MI_LAYOUT_INTERLEAVED && H264MI_TENSOR_LAYOUT(f->r.t.mode) == H264MI_TENSOR_RGB;
+    const bool il = desc->layout == H264MI_LAYOUT_INTERLEAVED;
+    const bool hwc = il && H264MI_TENSOR_LAYOUT(f->r.t.mode) == H264MI_TENSOR_RGB;
     if (layout_unresized(desc))
         return tensor_device(d_in, in_offsets, npics, width, height, cpitch, &f->r.t, NULL, d_out, out_stride,
-                             (hipStream_t)stream, hwc);
+                             (hipStream_t)stream, il, dest);
     const bool stretch = f->fit == H264MI_FIT_STRETCH;
-    if (!rois && stretch && !hwc)
+    // (a stretched single window into a destination runs as a table, one row per picture: the strides are the table forms')
+    if (!rois && stretch && !hwc && !dest)
         return tensor_device(d_in, in_offsets, npics, width, height, cpitch, &f->r.t, &f->r, d_out, out_stride,
                              (hipStream_t)stream);
     return rois_device(d_in, in_offsets, npics, width, height, cpitch, &f->r, stretch && !hwc ? NULL : f,
-                       rois ? NULL : &f->r.t, rois, rois ? nrois : npics, d_out, out_stride, stream, hwc);
+                       rois ? NULL : &f->r.t, rois, rois ? nrois : npics, d_out, out_stride, stream, hwc, dest, il);
+}
+
+extern "C" int h264mi_tensor_layout_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width,
+                                                 int height, int cpitch, const h264mi_tensor_layout_desc *desc,
+                                                 const h264mi_roi *rois, int nrois, void *d_out, size_t out_stride,
+                                                 void *stream)
+{
+    return h264mi_tensor_dest_device_pitch(d_in, in_offsets, npics, width, height, cpitch, desc, rois, nrois, NULL, d_out,
+                                           out_stride, stream);
 }
 
 // The affine-warped export (warp.hip, include/h264mi.h): warp r,
@@ -601,10 +664,10 @@ static bool warps_desc_ok(const h264mi_tensor_warp_desc *d, const h264mi_warp *w
            warps_ok(warps, nwarps, npics);
 }
 
-extern "C" int h264mi_tensor_warps_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width,
-                                                int height, int cpitch, const h264mi_tensor_warp_desc *desc,
-                                                const h264mi_warp *warps, int nwarps, void *d_out, size_t out_stride,
-                                                void *stream)
+extern "C" int h264mi_tensor_warps_dest_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width,
+                                                     int height, int cpitch, const h264mi_tensor_warp_desc *desc,
+                                                     const h264mi_warp *warps, int nwarps, const h264mi_tensor_dest *dest,
+                                                     void *d_out, size_t out_stride, void *stream)
 {
     if (!tensor_pics_ok(d_in, in_offsets, npics, width, height, cpitch, d_out) ||
         !warps_desc_ok(desc, warps, nwarps, npics, width, height))
@@ -613,23 +676,35 @@ extern "C" int h264mi_tensor_warps_device_pitch(const void *d_in, const size_t *
     // (d_out is checked here too, as for the boxes: a host address would fault every launch of the list)
     if (!export_aligned(d_out, out_stride, export_elem_size(t->dtype)) || h264mi_pointer_device(d_out) < 0) return -1;
     const int layout = H264MI_TENSOR_LAYOUT(t->mode), colour = H264MI_TENSOR_COLOUR(t->mode);
-    const bool hwc = desc->layout == H264MI_LAYOUT_INTERLEAVED && layout == H264MI_TENSOR_RGB;
+    const bool il = desc->layout == H264MI_LAYOUT_INTERLEAVED, hwc = il && layout == H264MI_TENSOR_RGB;
+    const int planes = layout == H264MI_TENSOR_RGB ? 3 : 1;
+    if (dest && !dest_ok(dest, export_elem_size(t->dtype), planes, desc->oh, desc->ow, il, nwarps, out_stride)) return -1;
+    const export_dest ds = dest_resolve(dest, export_elem_size(t->dtype), planes, desc->oh, desc->ow, il);
     warp_args wa;
     tensor_args &a = wa.t;
     a.in = (const uint8_t *)d_in;
     a.width = width; a.height = height; a.cpitch = cpitch;
     a.x = t->x; a.y = t->y; a.cw = t->cw; a.ch = t->ch;
-    a.out_stride = out_stride;
+    a.out_stride = 0;
     for (int p = 0; p < 3; p++) { a.scale[p] = t->scale[p]; a.bias[p] = t->bias[p]; wa.pad[p] = desc->pad[p]; }
     a.col = tensor_colour_sets[colour];
     wa.ow = desc->ow; wa.oh = desc->oh; wa.border = desc->border;
     std::vector<size_t> off((size_t)nwarps);
     for (int r = 0; r < nwarps; r++) off[r] = in_offsets[warps[r].pic];
-    return export_launches(nwarps, off.data(), a.in_off, &a.out, d_out, out_stride, [&](int r0, int n) {
+    return dest_launches(nwarps, off.data(), a, d_out, out_stride, ds, [&](int r0, int n) {
         for (int r = 0; r < EXPORT_MAX_PICS; r++)
             memcpy(wa.m[r], warps[r0 + (r < n ? r : 0)].m, sizeof(wa.m[r]));
         warp_launch(layout, t->dtype, colour != 0, hwc, n, (hipStream_t)stream, wa);
     });
+}
+
+extern "C" int h264mi_tensor_warps_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width,
+                                                int height, int cpitch, const h264mi_tensor_warp_desc *desc,
+                                                const h264mi_warp *warps, int nwarps, void *d_out, size_t out_stride,
+                                                void *stream)
+{
+    return h264mi_tensor_warps_dest_device_pitch(d_in, in_offsets, npics, width, height, cpitch, desc, warps, nwarps, NULL,
+                                                 d_out, out_stride, stream);
 }
 
 // An export of the slots (streams[k], slots[k]), k < n, into the caller's
@@ -741,36 +816,63 @@ extern "C" int h264mi_engine_export_tensor_rois_fit(h264mi_engine *e, int n, con
 
 // the frame slots, or boxes over them, under a layout descriptor
 // (h264mi_tensor_layout_device_pitch): one ordering of the two streams per call
-extern "C" int h264mi_engine_export_tensor_layout(h264mi_engine *e, int n, const int *streams, const int *slots,
-                                                  const h264mi_tensor_layout_desc *desc, const h264mi_roi *rois,
-                                                  int nrois, void *d_out, size_t out_stride, void *stream)
+// (dest, DESIGN §3.5p: judged before the streams are ordered, with the call's items)
+extern "C" int h264mi_engine_export_tensor_dest(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                                const h264mi_tensor_layout_desc *desc, const h264mi_roi *rois,
+                                                int nrois, const h264mi_tensor_dest *dest, void *d_out,
+                                                size_t out_stride, void *stream)
 {
     if (!e || n < 1 || !streams || !slots || !d_out) return -1;
     const int width = e->w * 16, height = e->h * 16;
     if (!layout_desc_ok(desc, rois, nrois, n, width, height)) return -1;
-    return export_ordered(e, n, streams, slots, d_out, out_stride, export_elem_size(desc->f.r.t.dtype), stream, [&] {
+    const h264mi_tensor_resize_desc &r = desc->f.r;
+    const size_t es = export_elem_size(r.t.dtype);
+    if (dest && !dest_ok(dest, es, H264MI_TENSOR_LAYOUT(r.t.mode) == H264MI_TENSOR_RGB ? 3 : 1,
+                         layout_unresized(desc) ? r.t.ch : r.oh, layout_unresized(desc) ? r.t.cw : r.ow,
+                         desc->layout == H264MI_LAYOUT_INTERLEAVED, rois ? nrois : n, out_stride))
+        return -1;
+    return export_ordered(e, n, streams, slots, d_out, out_stride, es, stream, [&] {
         std::vector<size_t> off((size_t)n);
         for (int k = 0; k < n; k++) off[k] = e->frame_bytes * ((size_t)streams[k] * e->nslots + slots[k]);
-        return h264mi_tensor_layout_device_pitch(e->d_frames, off.data(), n, width, height, e->cpitch, desc, rois, nrois,
-                                                 d_out, out_stride, e->st);
+        return h264mi_tensor_dest_device_pitch(e->d_frames, off.data(), n, width, height, e->cpitch, desc, rois, nrois,
+                                               dest, d_out, out_stride, e->st);
     });
 }
 
-// warps over the frame slots (h264mi_tensor_warps_device_pitch; warps[r].pic
+extern "C" int h264mi_engine_export_tensor_layout(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                                  const h264mi_tensor_layout_desc *desc, const h264mi_roi *rois,
+                                                  int nrois, void *d_out, size_t out_stride, void *stream)
+{
+    return h264mi_engine_export_tensor_dest(e, n, streams, slots, desc, rois, nrois, NULL, d_out, out_stride, stream);
+}
+
+// warps over the frame slots (h264mi_tensor_warps_dest_device_pitch; warps[r].pic
 // indexes the n slots): one ordering of the two streams for the whole list
-extern "C" int h264mi_engine_export_tensor_warps(h264mi_engine *e, int n, const int *streams, const int *slots,
-                                                 const h264mi_tensor_warp_desc *desc, const h264mi_warp *warps,
-                                                 int nwarps, void *d_out, size_t out_stride, void *stream)
+extern "C" int h264mi_engine_export_tensor_warps_dest(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                                      const h264mi_tensor_warp_desc *desc, const h264mi_warp *warps,
+                                                      int nwarps, const h264mi_tensor_dest *dest, void *d_out,
+                                                      size_t out_stride, void *stream)
 {
     if (!e || n < 1 || !streams || !slots || !d_out) return -1;
     const int width = e->w * 16, height = e->h * 16;
     if (!warps_desc_ok(desc, warps, nwarps, n, width, height)) return -1;
-    return export_ordered(e, n, streams, slots, d_out, out_stride, export_elem_size(desc->t.dtype), stream, [&] {
+    const size_t es = export_elem_size(desc->t.dtype);
+    if (dest && !dest_ok(dest, es, H264MI_TENSOR_LAYOUT(desc->t.mode) == H264MI_TENSOR_RGB ? 3 : 1, desc->oh, desc->ow,
+                         desc->layout == H264MI_LAYOUT_INTERLEAVED, nwarps, out_stride))
+        return -1;
+    return export_ordered(e, n, streams, slots, d_out, out_stride, es, stream, [&] {
         std::vector<size_t> off((size_t)n);
         for (int k = 0; k < n; k++) off[k] = e->frame_bytes * ((size_t)streams[k] * e->nslots + slots[k]);
-        return h264mi_tensor_warps_device_pitch(e->d_frames, off.data(), n, width, height, e->cpitch, desc, warps, nwarps,
-                                                d_out, out_stride, e->st);
+        return h264mi_tensor_warps_dest_device_pitch(e->d_frames, off.data(), n, width, height, e->cpitch, desc, warps,
+                                                     nwarps, dest, d_out, out_stride, e->st);
     });
+}
+
+extern "C" int h264mi_engine_export_tensor_warps(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                                 const h264mi_tensor_warp_desc *desc, const h264mi_warp *warps,
+                                                 int nwarps, void *d_out, size_t out_stride, void *stream)
+{
+    return h264mi_engine_export_tensor_warps_dest(e, n, streams, slots, desc, warps, nwarps, NULL, d_out, out_stride, stream);
 }
 
 // Motion vectors and MB side information as planar fields (mbinfo.hip): the

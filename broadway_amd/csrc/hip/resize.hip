@@ -229,23 +229,26 @@ __device__ __forceinline__ void resize_stage(const tensor_args &a, const int *wi
     }
 }
 
-// the bits v of an element as element o of the output at O: one non-temporal store
+// the bits v of an element as the element o bytes (a multiple of the element
+// size) into the output at O: one non-temporal store
 template <int DT>
 __device__ __forceinline__ void resize_store(uint8_t *O, size_t o, uint32_t v)
 {
     constexpr int ES = tensor_elem_size(DT);
     if (ES == 1) __builtin_nontemporal_store((uint8_t)v, O + o);
-    else if (ES == 2) __builtin_nontemporal_store((uint16_t)v, (uint16_t *)O + o);
-    else __builtin_nontemporal_store(v, (uint32_t *)O + o);
+    else if (ES == 2) __builtin_nontemporal_store((uint16_t)v, (uint16_t *)(O + o));
+    else __builtin_nontemporal_store(v, (uint32_t *)(O + o));
 }
 
-// element (p, i, j) of a picture of (NP, oh, ow) elements: planar, or (HWC,
-// DESIGN §3.5m) interleaved, (oh, ow, NP)
-template <bool HWC, int NP>
-__device__ __forceinline__ size_t resize_out_index(int p, int i, int j, int oh, int ow)
+// where element (p, i, j) of an item lies, in bytes from its start, by the
+// destination's strides a.row and a.plane: planar, or (HWC,
+// DESIGN §3.5m) interleaved, NP elements per column
+template <bool HWC, int NP, int DT>
+__device__ __forceinline__ size_t resize_out_index(const tensor_args &a, int p, int i, int j)
 {
-    if constexpr (HWC) return ((size_t)i * ow + (size_t)j) * NP + p;
-    return ((size_t)p * oh + (size_t)i) * ow + (size_t)j;
+    constexpr int ES = tensor_elem_size(DT);
+    if constexpr (HWC) return (size_t)i * a.row + ((size_t)j * NP + p) * ES;
+    return (size_t)p * a.plane + (size_t)i * a.row + (size_t)j * ES;
 }
 
 // the arguments of k_tensor_resize<.., ROIS, FIT>, and their resize_args
@@ -305,13 +308,13 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
         iy0 = py0 > oy0 ? py0 - oy0 : 0;
         iy1 = py0 + rh - oy0 < ny ? py0 + rh - oy0 : ny;
         if (jx0 >= jx1 || iy0 >= iy1) {             // all bar (uniform over the workgroup)
-            uint8_t *O = a.out + blockIdx.y * a.out_stride;
+            uint8_t *O = a.out + a.out_off[blockIdx.y];
 #pragma unroll
             for (int e = 0; e < NE; e++) {
                 const int p = e >> 1, i = (tid >> 5) + 8 * (e & 1), j = tid & 31;
                 if (i >= ny || j >= nx) continue;
                 const uint32_t v = tensor_elem<DT>(ka.pad[p], a.scale[p], a.bias[p]);
-                const size_t o = resize_out_index<HWC, NP>(p, oy0 + i, ox0 + j, oh, ow);
+                const size_t o = resize_out_index<HWC, NP, DT>(a, p, oy0 + i, ox0 + j);
                 resize_store<DT>(O, o, v);
             }
             return;
@@ -408,7 +411,12 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
         // chunk's reads of tb before the next horizontal pass)
     }
 
-    uint8_t *O = a.out + blockIdx.y * a.out_stride;
+    // The destination's strides are the table forms' (ROIS): the single-window form writes packed
+    // pictures out_stride apart, with the index arithmetic it always had -- with the strides as arguments its
+    // legs measured 3 to 13 % slower, the table forms' did not -- and a strided single window runs as a table.
+    uint8_t *O;
+    if constexpr (ROIS) O = a.out + a.out_off[blockIdx.y];
+    else O = a.out + blockIdx.y * a.out_stride;
 #pragma unroll
     for (int e = 0; e < NE; e++) {
         const int p = e >> 1, i = (tid >> 5) + 8 * (e & 1), j = tid & 31;
@@ -423,7 +431,9 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_tensor_resize(const typename
         if constexpr (FIT)
             if (i < iy0 || i >= iy1 || j < jx0 || j >= jx1) c = ka.pad[p];
         const uint32_t v = tensor_elem<DT>(c, a.scale[p], a.bias[p]);
-        const size_t o = resize_out_index<HWC, NP>(p, oy0 + i, ox0 + j, oh, ow);
+        size_t o;
+        if constexpr (ROIS) o = resize_out_index<HWC, NP, DT>(a, p, oy0 + i, ox0 + j);
+        else o = (((size_t)p * oh + (size_t)(oy0 + i)) * ow + (size_t)(ox0 + j)) * tensor_elem_size(DT);
         resize_store<DT>(O, o, v);
     }
 }

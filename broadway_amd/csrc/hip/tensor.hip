@@ -8,13 +8,15 @@
 // conversion (v_cvt_f16_f32 / v_cvt_pk_bf16_f32).  Input as in crop.hip: luma
 // rows `width` apart, chroma rows `cpitch` apart (an engine slot, or packed
 // I420 with cpitch = width / 2); picture k starts in_off[k] bytes after `in`
-// and goes to out + k * out_stride.
+// and goes to out + out_off[k], its rows `row` bytes and (planar) its planes
+// `plane` bytes apart (the host resolves an h264mi_tensor_dest,
+// or the packed item of a call without one, into these).
 //
 // HBM-bound elementwise kernels, 64 threads per block, work items in raster
 // order (no lane idles at row ends), non-temporal stores.  A work item is two
 // rows of 4 * NG columns, NG the 4-column groups of color.hip it holds:
-//   V16   row starts are 16-byte aligned (out, out_stride and cw * element
-//         size are multiples of 16): NG = 4 / element size, so a lane stores
+//   V16   row starts are 16-byte aligned (out, every out_off, row, plane and
+//         cw * element size are multiples of 16): NG = 4 / element size, so a lane stores
 //         16 bytes per plane row, 6 stores (RGB) or 2 (GRAY) per item;
 //   else  NG = 1 and every element is stored on its own (a row can start on
 //         any element, and a row pair's last group is 2 columns wide when
@@ -39,10 +41,12 @@ struct tensor_args {
     const uint8_t *in;
     uint8_t *out;
     int width, height, cpitch, x, y, cw, ch;
-    size_t out_stride;
+    size_t out_stride;              // k_tensor_resize without a table only: picture k goes to out + k * out_stride
+    size_t row, plane;              // bytes between two rows and (planar) two planes of an item
     float scale[3], bias[3];
     colour_set col;                 // COL kernels only (tensor_colour_sets[id], id != 0)
     unsigned long long in_off[TENSOR_MAX_PICS];
+    unsigned long long out_off[TENSOR_MAX_PICS];    // grid row k's item starts out_off[k] bytes after `out`
 };
 
 // the colour sets of the RGB exports by id (include/h264mi.h):
@@ -219,8 +223,8 @@ __global__ __launch_bounds__(64) void k_tensor(const tensor_args a)
     const uint8_t *U = Y + (size_t)width * a.height + (size_t)(a.y >> 1) * cpitch + (a.x >> 1);
     const uint8_t *V = U + (size_t)cpitch * (a.height >> 1);
     Y += (size_t)a.y * width + a.x;
-    uint8_t *O = a.out + blockIdx.y * a.out_stride;
-    const size_t plane = (size_t)cw * a.ch * ES;
+    uint8_t *O = a.out + a.out_off[blockIdx.y];
+    const size_t plane = a.plane, row = a.row;
 #pragma unroll
     for (int h = 0; h < 2; h++) {
         const int f = blockIdx.x * 128 + h * 64 + (int)threadIdx.x;
@@ -276,16 +280,16 @@ __global__ __launch_bounds__(64) void k_tensor(const tensor_args a)
         }
         const int n = full ? NC : 2;
         if constexpr (HWC) {
-            uint8_t *d = O + ((size_t)(2 * y2) * cw + NC * g) * (3 * ES);
+            uint8_t *d = O + (size_t)(2 * y2) * row + (size_t)(NC * g) * (3 * ES);
             tensor_store_hwc<DT, NC, V16>(c[0], n, a.scale, a.bias, d);
-            tensor_store_hwc<DT, NC, V16>(c[1], n, a.scale, a.bias, d + (size_t)cw * (3 * ES));
+            tensor_store_hwc<DT, NC, V16>(c[1], n, a.scale, a.bias, d + row);
             continue;
         }
-        uint8_t *d = O + ((size_t)(2 * y2) * cw + NC * g) * ES;
+        uint8_t *d = O + (size_t)(2 * y2) * row + (size_t)(NC * g) * ES;
 #pragma unroll
         for (int p = 0; p < NP; p++) {
             tensor_store<DT, NC, V16>(c[0][p], n, a.scale[p], a.bias[p], d + p * plane);
-            tensor_store<DT, NC, V16>(c[1][p], n, a.scale[p], a.bias[p], d + p * plane + (size_t)cw * ES);
+            tensor_store<DT, NC, V16>(c[1][p], n, a.scale[p], a.bias[p], d + p * plane + row);
         }
     }
 }

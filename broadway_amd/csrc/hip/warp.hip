@@ -57,7 +57,7 @@ __global__ __launch_bounds__(WARP_THREADS) void k_tensor_warp(const warp_args ka
     const int ty = (int)blockIdx.x / ntx, tx = (int)blockIdx.x - ty * ntx;
     const int i = ty * WARP_TH + (tid >> 5), j = tx * WARP_TW + (tid & 31);
     const int *m = ka.m[blockIdx.y];
-    uint8_t *O = a.out + blockIdx.y * a.out_stride;
+    uint8_t *O = a.out + a.out_off[blockIdx.y];
     const bool mine = i < oh && j < ow;
 
     if (ka.border == H264MI_WARP_BORDER_CONSTANT &&
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(WARP_THREADS) void k_tensor_warp(const warp_args ka
         if (mine) {
 #pragma unroll
             for (int p = 0; p < NP; p++)
-                resize_store<DT>(O, resize_out_index<HWC, NP>(p, i, j, oh, ow), tensor_elem<DT>(ka.pad[p], a.scale[p], a.bias[p]));
+                resize_store<DT>(O, resize_out_index<HWC, NP, DT>(a, p, i, j), tensor_elem<DT>(ka.pad[p], a.scale[p], a.bias[p]));
         }
         return;
     }
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(WARP_THREADS) void k_tensor_warp(const warp_args ka
         uint32_t acc = 32768u;                      // (the weights add up to 65536: acc < 2^24 + 2^15)
 #pragma unroll
         for (int k = 0; k < 4; k++) acc += w[k] * ((px[k] >> (8 * p)) & 255u);
-        resize_store<DT>(O, resize_out_index<HWC, NP>(p, i, j, oh, ow), tensor_elem<DT>(acc >> 16, a.scale[p], a.bias[p]));
+        resize_store<DT>(O, resize_out_index<HWC, NP, DT>(a, p, i, j), tensor_elem<DT>(acc >> 16, a.scale[p], a.bias[p]));
     }
 }
 

@@ -257,20 +257,24 @@ H264SwDecRet H264SwDecNextPictureCropped(H264SwDecInst decInst, H264SwDecPicture
 /* H264SwDecNextPictureTensor (desc: an h264mi_tensor_desc), resized == 1
  * ...TensorResized (an h264mi_tensor_resize_desc) and resized == 2 ...TensorFit
  * (an h264mi_tensor_fit_desc) and resized == 3 ...TensorLayout (an
- * h264mi_tensor_layout_desc); a window with cw == 0 is the active SPS's crop
+ * h264mi_tensor_layout_desc) and resized == 4 ...TensorDest (the same, into the
+ * strided destination dest, which may be NULL); a window with cw == 0 is the active SPS's crop
  * window.  Everything the export can refuse is checked
  * before a picture is taken from the DPB. */
 static H264SwDecRet next_picture_tensor(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
-                                        const void *desc, int resized, void *d_dst, void *hip_stream)
+                                        const void *desc, int resized, const h264mi_tensor_dest *dest, void *d_dst,
+                                        void *hip_stream)
 {
     if (decInst == NULL || pOutput == NULL || d_dst == NULL || desc == NULL) return H264SWDEC_PARAM_ERR;
     DecContainer *c = (DecContainer *)decInst;
-    if (!(resized == 3 ? c->dec.be.export_tensor_layout != NULL : resized == 2 ? c->dec.be.export_tensor_fit != NULL
-          : resized ? c->dec.be.export_tensor_resized != NULL : c->dec.be.export_tensor != NULL))
-        return H264SWDEC_PARAM_ERR;
+    /* the backend member each form runs over, by `resized` */
+    const int have[5] = {c->dec.be.export_tensor != NULL, c->dec.be.export_tensor_resized != NULL,
+                         c->dec.be.export_tensor_fit != NULL, c->dec.be.export_tensor_layout != NULL,
+                         c->dec.be.export_tensor_dest != NULL};
+    if (resized < 0 || resized > 4 || !have[resized]) return H264SWDEC_PARAM_ERR;
     h264mi_tensor_layout_desc l;
     memset(&l, 0, sizeof(l));
-    if (resized == 3) l = *(const h264mi_tensor_layout_desc *)desc;
+    if (resized >= 3) l = *(const h264mi_tensor_layout_desc *)desc;
     else if (resized == 2) l.f = *(const h264mi_tensor_fit_desc *)desc;
     else if (resized) l.f.r = *(const h264mi_tensor_resize_desc *)desc;
     else l.f.r.t = *(const h264mi_tensor_desc *)desc;
@@ -278,9 +282,12 @@ static H264SwDecRet next_picture_tensor(H264SwDecInst decInst, H264SwDecPicture 
     h264mi_tensor_resize_desc *r = &f->r;
     h264mi_tensor_desc *t = &r->t;
     if (h264mi_tensor_colour_resolve(t->mode, 2, 0, 2, 2) < 0 ||
-        !(resized == 3 ? layout_desc_fixed_ok(&l) : resized == 2 ? fit_desc_fixed_ok(f)
+        !(resized >= 3 ? layout_desc_fixed_ok(&l) : resized == 2 ? fit_desc_fixed_ok(f)
           : resized ? resize_desc_fixed_ok(r) : tensor_desc_fixed_ok(t)) ||
         !export_aligned(d_dst, 0, export_elem_size(t->dtype)))
+        return H264SWDEC_PARAM_ERR;
+    /* (what dest_ok refuses whatever the window turns out to be; one picture is one item, so its clip is 1) */
+    if (resized == 4 && dest && (!dest_fixed_ok(dest, l.layout == H264MI_LAYOUT_INTERLEAVED) || dest->clip != 1))
         return H264SWDEC_PARAM_ERR;
     if (flushBuffer) h264dec_flush(&c->dec);
     const Sps *s = h264dec_active_sps(&c->dec);
@@ -290,14 +297,22 @@ static H264SwDecRet next_picture_tensor(H264SwDecInst decInst, H264SwDecPicture 
         t->x = w.x; t->y = w.y; t->cw = w.cw; t->ch = w.ch;
     }
     const int width = 16 * s->w_mbs, height = 16 * s->h_mbs;
-    if (!(resized == 3 ? layout_window_ok(&l, width, height) : resized == 2 ? fit_window_ok(f, width, height, NULL)
+    if (!(resized >= 3 ? layout_window_ok(&l, width, height) : resized == 2 ? fit_window_ok(f, width, height, NULL)
           : resized    ? resize_window_ok(r, width, height) : tensor_window_ok(t, width, height)))
+        return H264SWDEC_PARAM_ERR;
+    /* (one picture is one item: dest_ok then asks for clip == 1) */
+    if (resized == 4 && dest &&
+        !dest_ok(dest, export_elem_size(t->dtype), H264MI_TENSOR_LAYOUT(t->mode) == H264MI_TENSOR_RGB ? 3 : 1,
+                 layout_unresized(&l) ? t->ch : r->oh, layout_unresized(&l) ? t->cw : r->ow,
+                 l.layout == H264MI_LAYOUT_INTERLEAVED, 1, 0))
         return H264SWDEC_PARAM_ERR;
     uint32_t id, idr, em;
     int failed = 0;
     /* (a layout descriptor starts with its fit descriptor, that with its resize descriptor, and that with its
      * h264mi_tensor_desc) */
-    const uint8_t *pic = h264dec_next_output_tensor(&c->dec, &id, &idr, &em, &l, resized, d_dst, hip_stream, &failed);
+    const uint8_t *pic = resized == 4
+        ? h264dec_next_output_tensor_dest(&c->dec, &id, &idr, &em, &l, dest, d_dst, hip_stream, &failed)
+        : h264dec_next_output_tensor(&c->dec, &id, &idr, &em, &l, resized, d_dst, hip_stream, &failed);
     if (failed) return H264SWDEC_PARAM_ERR;         /* (d_dst not on the decoder's GPU) */
     if (!pic) return H264SWDEC_OK;
     pOutput->pOutputPicture = (u32 *)(void *)pic;
@@ -319,28 +334,36 @@ H264SwDecRet H264SwDecNextPictureTensor(H264SwDecInst decInst, H264SwDecPicture 
     t.mode = H264MI_TENSOR_RGB;
     t.dtype = H264MI_TENSOR_F16;
     for (int p = 0; p < 3; p++) t.scale[p] = 1.0f / 255.0f;
-    return next_picture_tensor(decInst, pOutput, flushBuffer, desc ? desc : &t, 0, d_dst, hip_stream);
+    return next_picture_tensor(decInst, pOutput, flushBuffer, desc ? desc : &t, 0, NULL, d_dst, hip_stream);
 }
 
 /* NextPictureTensor with the tensor resized on the GPU (include/h264mi.h) */
 H264SwDecRet H264SwDecNextPictureTensorResized(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
                                                const h264mi_tensor_resize_desc *desc, void *d_dst, void *hip_stream)
 {
-    return next_picture_tensor(decInst, pOutput, flushBuffer, desc, 1, d_dst, hip_stream);
+    return next_picture_tensor(decInst, pOutput, flushBuffer, desc, 1, NULL, d_dst, hip_stream);
 }
 
 /* NextPictureTensorResized letterboxed (include/h264mi.h) */
 H264SwDecRet H264SwDecNextPictureTensorFit(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
                                            const h264mi_tensor_fit_desc *desc, void *d_dst, void *hip_stream)
 {
-    return next_picture_tensor(decInst, pOutput, flushBuffer, desc, 2, d_dst, hip_stream);
+    return next_picture_tensor(decInst, pOutput, flushBuffer, desc, 2, NULL, d_dst, hip_stream);
 }
 
 /* any of the three under a layout descriptor (include/h264mi.h) */
 H264SwDecRet H264SwDecNextPictureTensorLayout(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
                                               const h264mi_tensor_layout_desc *desc, void *d_dst, void *hip_stream)
 {
-    return next_picture_tensor(decInst, pOutput, flushBuffer, desc, 3, d_dst, hip_stream);
+    return next_picture_tensor(decInst, pOutput, flushBuffer, desc, 3, NULL, d_dst, hip_stream);
+}
+
+/* NextPictureTensorLayout into a strided destination (include/h264mi.h) */
+H264SwDecRet H264SwDecNextPictureTensorDest(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
+                                            const h264mi_tensor_layout_desc *desc, const h264mi_tensor_dest *dest,
+                                            void *d_dst, void *hip_stream)
+{
+    return next_picture_tensor(decInst, pOutput, flushBuffer, desc, 4, dest, d_dst, hip_stream);
 }
 
 /* the colour id of the last tensor a call above delivered; -1: none yet */

@@ -634,6 +634,7 @@ typedef struct TensorOut {
     const void *desc;
     void *d_dst, *hip_stream;
     int failed, resized;
+    const void *dest;               /* resized == 4: the h264mi_tensor_dest, or NULL */
 } TensorOut;
 
 /* rgba != NULL: the picture as RGBA (w*h*4 bytes) into rgba, converted by
@@ -657,8 +658,19 @@ const uint8_t *h264dec_next_output_crop(H264Dec *d, uint32_t *pic_id, uint32_t *
 const uint8_t *h264dec_next_output_tensor(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
                                           const void *desc, int resized, void *d_dst, void *hip_stream, int *failed)
 {
-    TensorOut t = {desc, d_dst, hip_stream, 0, resized};
+    TensorOut t = {desc, d_dst, hip_stream, 0, resized, NULL};
     /* (a resize, fit or layout descriptor starts with its h264mi_tensor_desc) */
+    const int mode_ok = desc && h264mi_tensor_colour_resolve(((const h264mi_tensor_desc *)desc)->mode, 2, 0, 2, 2) >= 0;
+    const uint8_t *r = d_dst && mode_ok ? next_output(d, pic_id, is_idr, err_mbs, NULL, NULL, 0, &t) : NULL;
+    if (failed) *failed = t.failed;
+    return r;
+}
+
+const uint8_t *h264dec_next_output_tensor_dest(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
+                                               const void *desc, const void *dest, void *d_dst, void *hip_stream,
+                                               int *failed)
+{
+    TensorOut t = {desc, d_dst, hip_stream, 0, 4, dest};
     const int mode_ok = desc && h264mi_tensor_colour_resolve(((const h264mi_tensor_desc *)desc)->mode, 2, 0, 2, 2) >= 0;
     const uint8_t *r = d_dst && mode_ok ? next_output(d, pic_id, is_idr, err_mbs, NULL, NULL, 0, &t) : NULL;
     if (failed) *failed = t.failed;
@@ -672,7 +684,8 @@ static const uint8_t *next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr
                                   uint8_t *crop, int crop_rgba, TensorOut *tensor)
 {
     if (rgba && !d->be.read_rgba) return NULL;
-    if (tensor && !(tensor->resized == 3 ? d->be.export_tensor_layout != NULL
+    if (tensor && !(tensor->resized == 4 ? d->be.export_tensor_dest != NULL
+                    : tensor->resized == 3 ? d->be.export_tensor_layout != NULL
                     : tensor->resized == 2 ? d->be.export_tensor_fit != NULL
                     : tensor->resized ? d->be.export_tensor_resized != NULL : d->be.export_tensor != NULL))
         return NULL;
@@ -698,7 +711,7 @@ static const uint8_t *next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr
         /* the backend gets the colour id of this picture's own SPS in place of STREAM */
         h264mi_tensor_layout_desc l;
         memset(&l, 0, sizeof(l));
-        if (tensor->resized == 3) l = *(const h264mi_tensor_layout_desc *)tensor->desc;
+        if (tensor->resized >= 3) l = *(const h264mi_tensor_layout_desc *)tensor->desc;
         else if (tensor->resized == 2) l.f = *(const h264mi_tensor_fit_desc *)tensor->desc;
         else if (tensor->resized) l.f.r = *(const h264mi_tensor_resize_desc *)tensor->desc;
         else l.f.r.t = *(const h264mi_tensor_desc *)tensor->desc;
@@ -707,7 +720,8 @@ static const uint8_t *next_output(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr
         /* (by size: the export window's, never a canvas's) */
         const int colour = h264mi_tensor_colour_resolve(t->mode, o->vui_matrix, o->vui_full, t->cw, t->ch);
         if (H264MI_TENSOR_LAYOUT(t->mode) == H264MI_TENSOR_RGB) t->mode = H264MI_TENSOR_MODE(H264MI_TENSOR_RGB, colour, 0);
-        rr = tensor->resized == 3 ? d->be.export_tensor_layout(d->be.ctx, o->slot, &l, NULL, 0, tensor->d_dst, tensor->hip_stream)
+        rr = tensor->resized == 4 ? d->be.export_tensor_dest(d->be.ctx, o->slot, &l, tensor->dest, tensor->d_dst, tensor->hip_stream)
+             : tensor->resized == 3 ? d->be.export_tensor_layout(d->be.ctx, o->slot, &l, NULL, 0, tensor->d_dst, tensor->hip_stream)
              : tensor->resized == 2 ? d->be.export_tensor_fit(d->be.ctx, o->slot, f, tensor->d_dst, tensor->hip_stream)
              : tensor->resized    ? d->be.export_tensor_resized(d->be.ctx, o->slot, &f->r, tensor->d_dst, tensor->hip_stream)
                                   : d->be.export_tensor(d->be.ctx, o->slot, t, tensor->d_dst, tensor->hip_stream);

@@ -92,6 +92,10 @@ typedef struct H264Backend {
      * cannot */
     int  (*export_tensor_layout)(void *ctx, int slot, const void *desc, const void *rois, int nrois, void *d_dst,
                                  void *hip_stream);
+    /* optional: export_tensor_layout's single-window form into a strided
+     * destination (dest: a checked h264mi_tensor_dest with clip 1, or NULL),
+     * with export_tensor's returns; NULL when the backend cannot */
+    int  (*export_tensor_dest)(void *ctx, int slot, const void *desc, const void *dest, void *d_dst, void *hip_stream);
     /* optional: the nwarps warps (h264mi_warp, every pic 0) of slot as the
      * affine-warped tensors of desc (a checked h264mi_tensor_warp_desc whose
      * window is in picture coordinates), warp r packed behind warp r - 1 at
@@ -227,6 +231,12 @@ const uint8_t *h264dec_next_output_crop(H264Dec *d, uint32_t *pic_id, uint32_t *
  * when the export of the picture taken from the DPB failed */
 const uint8_t *h264dec_next_output_tensor(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
                                           const void *desc, int resized, void *d_dst, void *hip_stream, int *failed);
+/* the same with resized == 4: export_tensor_dest (desc: an
+ * h264mi_tensor_layout_desc) into the strided destination dest (an
+ * h264mi_tensor_dest, or NULL) */
+const uint8_t *h264dec_next_output_tensor_dest(H264Dec *d, uint32_t *pic_id, uint32_t *is_idr, uint32_t *err_mbs,
+                                               const void *desc, const void *dest, void *d_dst, void *hip_stream,
+                                               int *failed);
 int  h264dec_valid_param_sets(const H264Dec *d);
 /* conceal the current picture's missing MBs (conceal.c); returns their
  * number or -1 */

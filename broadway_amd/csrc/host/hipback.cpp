@@ -729,6 +729,29 @@ static int hb_export_tensor_layout(void *vctx, int slot, const void *desc, const
     return rois ? 0 : slot_flagged((HipBackendCtx *)vctx, slot, false);
 }
 
+// the single-window form of the same into a strided destination (a member of its own)
+extern "C" int h264mi_engine_export_tensor_dest(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                                const h264mi_tensor_layout_desc *desc, const h264mi_roi *rois,
+                                                int nrois, const h264mi_tensor_dest *dest, void *d_out,
+                                                size_t out_stride, void *hip_stream) __attribute__((weak));
+struct DestCall {
+    const h264mi_tensor_layout_desc *desc;
+    const h264mi_tensor_dest *dest;
+};
+
+static int engine_export_dest(h264mi_engine *e, int n, const int *streams, const int *slots, const DestCall *c,
+                              void *d_out, size_t, void *hip_stream)
+{
+    return h264mi_engine_export_tensor_dest(e, n, streams, slots, c->desc, NULL, 0, c->dest, d_out, 0, hip_stream);
+}
+
+static int hb_export_tensor_dest(void *vctx, int slot, const void *desc, const void *dest, void *d_dst, void *hip_stream)
+{
+    const DestCall c = {(const h264mi_tensor_layout_desc *)desc, (const h264mi_tensor_dest *)dest};
+    if (hb_export(vctx, slot, engine_export_dest, &c, d_dst, hip_stream)) return -1;
+    return slot_flagged((HipBackendCtx *)vctx, slot, false);
+}
+
 // warps of slot as affine-warped tensors (a member of its own, with no
 // retention): the list travels through hb_export as one descriptor, warp r's
 // elements packed behind warp r - 1's
@@ -910,6 +933,7 @@ extern "C" H264Backend h264mi_hip_backend_create(int device)
     be.export_tensor_fit = h264mi_engine_export_tensor_fit ? hb_export_tensor_fit : NULL;
     be.export_tensor_rois_fit = h264mi_engine_export_tensor_rois_fit ? hb_export_tensor_rois_fit : NULL;
     be.export_tensor_layout = h264mi_engine_export_tensor_layout ? hb_export_tensor_layout : NULL;
+    be.export_tensor_dest = h264mi_engine_export_tensor_dest ? hb_export_tensor_dest : NULL;
     be.export_tensor_warps = h264mi_engine_export_tensor_warps ? hb_export_tensor_warps : NULL;
     be.host_alloc = hb_host_alloc;
     be.host_free = hb_host_free;

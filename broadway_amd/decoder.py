@@ -51,6 +51,16 @@ of the wasm glue of Decoder/src/Decoder.c:44-162:
   where it names none the family of ``unspecified``: "bt601" (default),
   "bt709" or "size" (BT.709 from 1280 columns or 577 rows of the exported
   window).  ``decoder.tensor_colour`` names the set of the last tensor.
+  ``"clip": T`` (with ``"step": s``, default 1; combines with every key
+  above): the pictures as video clips.  Every s-th delivered picture is
+  written in place into the current ``(planes, T, h, w)`` clip
+  (``H264SwDecNextPictureTensorDest``) -- ``onPictureDecoded``
+  still fires for it, with the strided view ``clip[:, t]`` -- and after the
+  T-th ``onClipDecoded(clip, width, height)`` fires and a new clip is
+  allocated; the pictures in between are taken and dropped.  A clip is
+  contiguous (``layout: "nhwc"``: channels-last per frame), so a batch of them
+  is NCTHW.  An incomplete last clip is not emitted: ``decoder.clip_fill`` is
+  the number of pictures it holds.
 
 * ``mbinfo: true`` or ``mbinfo: {"channels": ..., "dtype": ..., "scale": ...,
   "bias": ...}`` (an extension for device consumers; needs torch; combines
@@ -188,11 +198,18 @@ class Decoder:
                 raise ValueError("tensor: not combinable with rgb or crop (mode='rgb' and the SPS window are part of it)")
             opts = {} if self._tensor is True else dict(self._tensor)
             unknown = set(opts) - {"dtype", "mode", "mean", "std", "scale", "bias", "size", "colour", "unspecified",
-                                   "fit", "pad", "layout", "filter"}
+                                   "fit", "pad", "layout", "filter", "clip", "step"}
             if unknown:
                 raise ValueError(f"tensor: unknown keys {sorted(unknown)}")
             from .engine import fit_desc, layout_desc, tensor_desc, tensor_layout       # (imports torch)
             fit, pad = opts.pop("fit", None), opts.pop("pad", None)
+            self._clip_t, self._clip_step = opts.pop("clip", None), opts.pop("step", None)
+            if self._clip_step is not None and self._clip_t is None:
+                raise ValueError("tensor: step goes with clip")
+            for what, v in (("clip", self._clip_t), ("step", self._clip_step)):
+                if v is not None and (not isinstance(v, int) or isinstance(v, bool) or v < 1):
+                    raise ValueError(f"tensor: {what} {v!r}: a positive integer")
+            self._clip_step = self._clip_step or 1
             self._layout = opts.pop("layout", "nchw")
             tensor_layout(self._layout)
             self._tensor = tensor_desc(None, stream_ok=True, **opts)
@@ -207,6 +224,8 @@ class Decoder:
             # "nhwc": the same descriptor under a layout, through the one call that takes it
             self._tensor_layout = layout_desc(self._tensor[0], self._layout) if self._layout != "nchw" else None
             self._device = int(os.environ.get("H264MI_DEVICE") or 0)     # the GPU H264SwDecInit takes (api.c)
+            if self._clip_t is not None:
+                self._clip_desc = self._tensor_layout or layout_desc(self._tensor[0], "nchw")
         self._fields = {}           # option -> (descriptor, channels or planes, torch dtype) of the fields asked for
         for name, f in _FIELDS.items():
             setattr(self, name, None)
@@ -238,6 +257,11 @@ class Decoder:
         self.pic_display_number = 1
         self.onPictureDecoded: Callable = lambda buffer, width, height, infos: None
         self.onHeadersDecoded: Callable = lambda: None
+        # the `clip` key of the tensor option: the clip being filled, the pictures it holds, the pictures delivered
+        self.onClipDecoded: Callable = lambda clip, width, height: None
+        self._clip = None
+        self.clip_fill = 0
+        self._clip_seen = 0
 
     # DecoderPost.js:275-285 + Decoder.c:44-53
     def decode(self, typed_ar, par_info: Optional[dict] = None) -> None:
@@ -276,7 +300,10 @@ class Decoder:
             inp.dataLen = 0
             self.pic_decode_number += 1
             while True:
-                if self._tensor is not None:
+                if self._tensor is not None and self._clip_t is not None:
+                    if not self._next_into_clip():
+                        break
+                elif self._tensor is not None:
                     desc, planes, dtype = self._tensor
                     w, h = self._out_size()
                     out, st = self._device_empty((planes, h, w), dtype, self._layout)
@@ -321,6 +348,49 @@ class Decoder:
         elif ret in (_lib.H264SWDEC_STRM_PROCESSED, _lib.H264SWDEC_STRM_ERR):
             inp.dataLen = 0
         return ret
+
+    def _next_into_clip(self) -> bool:
+        """The next delivered picture under ``tensor: {"clip": T, "step": s}``:
+        every s-th one is written in place into frame ``clip_fill`` of the
+        current ``(planes, T, h, w)`` clip (H264SwDecNextPictureTensorDest:
+        the frame's strides are the destination) and handed to
+        onPictureDecoded as that view; the T-th completes the clip, which goes
+        to onClipDecoded, and the next picture starts a new one.  The pictures
+        in between are taken with H264SwDecNextPicture and dropped.  False:
+        no picture was ready."""
+        L = self._L
+        if self._clip_seen % self._clip_step:
+            if L.H264SwDecNextPicture(self._inst, C.byref(self._pic), 0) != _lib.H264SWDEC_PIC_RDY:
+                return False
+            self._clip_seen += 1
+            self.pic_display_number += 1
+            return True
+        import torch
+        from .engine import dest_of_view, empty_clip
+        _, planes, dtype = self._tensor
+        w, h = self._out_size()
+        dev = torch.device("cuda", self._device)
+        if self._clip is None or tuple(self._clip.shape) != (planes, self._clip_t, h, w):
+            with torch.cuda.device(dev):
+                self._clip = empty_clip((1, planes, self._clip_t, h, w), dtype, dev, self._layout)[0]
+            self.clip_fill = 0
+        view = self._clip[:, self.clip_fill]
+        dest, _ = dest_of_view(view[None], (1, planes, h, w), dtype, dev, self._layout)
+        nxt = getattr(L, "H264SwDecNextPictureTensorDest", None)
+        ret = nxt(self._inst, C.byref(self._pic), 0, C.byref(self._clip_desc), C.byref(dest), view.data_ptr(),
+                  torch.cuda.current_stream(dev).cuda_stream) if nxt else _lib.H264SWDEC_PARAM_ERR
+        if ret == _lib.H264SWDEC_PARAM_ERR:
+            raise RuntimeError("tensor: the backend cannot export into a clip (there is no host fallback)")
+        if ret != _lib.H264SWDEC_PIC_RDY:
+            return False
+        self._clip_seen += 1
+        self.pic_display_number += 1
+        self.clip_fill += 1
+        self._emit(self._pic, view)
+        if self.clip_fill == self._clip_t:
+            clip, self._clip, self.clip_fill = self._clip, None, 0
+            self.onClipDecoded(clip, w, h)
+        return True
 
     def _out_size(self):
         """(width, height) of the pictures handed to onPictureDecoded."""

@@ -156,6 +156,61 @@ def check_out(out, shape, dtype, device, layout="nchw"):
                          f"(got {out.dtype} {tuple(out.shape)} with strides {tuple(out.stride())} on {out.device})")
 
 
+def empty_clip(shape, dtype, device, layout="nchw"):
+    """A new tensor of the logical ``shape`` = (b, planes, t, rows, cols) for
+    ``to_tensor(clip=t)``: contiguous NCTHW, or with "nhwc"
+    ``torch.empty((b, t, rows, cols, planes)).permute(0, 4, 1, 2, 3)`` -- the
+    strides of ``torch.channels_last_3d``."""
+    import torch
+    if not tensor_layout(layout):
+        return torch.empty(shape, dtype=dtype, device=device)
+    b, p, t, rows, cols = shape
+    return torch.empty((b, t, rows, cols, p), dtype=dtype, device=device).permute(0, 4, 1, 2, 3)
+
+
+def dest_of_view(out, shape, dtype, device, layout="nchw"):
+    """(``_lib.TensorDest``, out_stride in bytes) of ``out=``, any view of the
+    result's logical ``shape`` -- (n, planes, rows, cols), or (b, planes, t,
+    rows, cols) of ``clip=t`` -- whose strides the exports can write through
+    (h264mi_tensor_dest): the column stride is 1 ("nhwc": the
+    plane stride 1 and the column stride ``planes``), every other stride is
+    free as long as no two elements share an address -- a slice of a wider
+    tensor, a tile of a canvas, a permuted clip.  ValueError, naming the
+    stride, for anything else, before the library is called.  A dimension of
+    one element has no stride to speak of."""
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device:
+        raise ValueError(f"out: a {dtype} view of shape {tuple(shape)} on {device} "
+                         f"(got {out.dtype} {tuple(out.shape)} on {out.device})")
+    es = out.element_size()
+    st = tuple(out.stride())
+    if len(shape) == 5:
+        (n, planes, clip, rows, cols), (s_n, s_p, s_t, s_r, s_c) = shape, st
+    else:
+        (n, planes, rows, cols), (s_n, s_p, s_r, s_c), clip, s_t = shape, st, 1, 0
+    nhwc = tensor_layout(layout) != 0 and planes > 1
+    names = {"column": s_c, "row": s_r, "plane": s_p, "frame": s_t, "item": s_n}
+    if nhwc and (s_p != 1 or (cols > 1 and s_c != planes)):
+        raise ValueError(f"out: layout 'nhwc' writes the planes of a column side by side: plane stride 1 and column "
+                         f"stride {planes} (got plane stride {s_p}, column stride {s_c})")
+    if not nhwc and cols > 1 and s_c != 1:
+        raise ValueError(f"out: column stride {s_c}: the elements of a row are written side by side (stride 1)")
+    packed = cols * (planes if nhwc else 1)
+    # the levels above a row's elements that hold more than one element, by stride
+    levels = [(s_r, rows, "row")] + ([] if nhwc else [(s_p, planes, "plane")]) + [(s_t, clip, "frame"), (s_n, n, "item")]
+    span = packed
+    for stride, count, name in sorted((l for l in levels if l[1] > 1), key=lambda l: l[0]):
+        if stride < span:
+            raise ValueError(f"out: {name} stride {stride} (dimension of {count}): below the {span} elements it has to "
+                             f"step over -- elements would share an address (strides {names})")
+        span += (count - 1) * stride
+    d = _lib.TensorDest()
+    d.row = s_r * es if rows > 1 else 0
+    d.plane = s_p * es if planes > 1 and not nhwc else 0
+    d.frame = s_t * es if clip > 1 else 0
+    d.clip = clip
+    return d, (s_n * es if n > 1 else 0)
+
+
 def tensor_desc(window, mode="rgb", dtype=None, scale=None, bias=None, mean=None, std=None, size=None, colour=None,
                 unspecified=None, stream_ok=False, layout=None, filter=None):
     """(``_lib.TensorDesc``, planes, torch dtype) of a tensor export
@@ -798,6 +853,48 @@ class Engine:
             out.record_stream(st)       # (the caching allocator: the block is in use on `stream` too)
         return out, st.cuda_stream
 
+    def _out_dest(self, shape, dtype, out, stream, layout="nchw", clip=None):
+        """``_out`` for the pixel exports: (out, HIP stream handle, None) where
+        the existing calls serve -- no ``out``, or one that is dense in
+        ``layout`` -- and otherwise (out, handle, (``_lib.TensorDest``,
+        out_stride)) of ``dest_of_view``.  ``clip`` = T: the ``shape[0]`` items
+        as ``(shape[0] // T, planes, T, rows, cols)``, a new ``empty_clip`` or
+        ``out``, always through a destination."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if clip is None:
+            dense = out is None or (tuple(out.shape) == tuple(shape) and out.dtype == dtype and out.device == dev and
+                                    (out.permute(0, 2, 3, 1) if layout != "nchw" else out).is_contiguous())
+            if dense:
+                return self._out(shape, dtype, out, stream, layout) + (None,)
+        else:
+            n, planes, rows, cols = shape
+            if not isinstance(clip, int) or isinstance(clip, bool) or clip < 1 or n % clip:
+                raise ValueError(f"clip {clip!r}: a positive integer that divides the {n} items")
+            shape = (n // clip, planes, clip, rows, cols)
+            if out is None:
+                with torch.cuda.device(self.device):
+                    out = empty_clip(shape, dtype, dev, layout)
+        dest = dest_of_view(out, shape, dtype, dev, layout)
+        cur = torch.cuda.current_stream(dev)
+        st = stream if stream is not None else cur
+        if st != cur:
+            out.record_stream(st)
+        return out, st.cuda_stream, dest
+
+    def _export_dest(self, n, c_streams, c_slots, desc, boxes, layout, out, st, dest):
+        """``out`` filled through h264mi_engine_export_tensor_dest: ``desc`` any
+        pixel export's descriptor, ``boxes`` a ``_lib.Roi`` array or None,
+        ``dest`` from ``_out_dest``."""
+        ld = desc if isinstance(desc, _lib.TensorLayoutDesc) else layout_desc(desc, layout)
+        d, out_stride = dest
+        if not hasattr(self._L, "h264mi_engine_export_tensor_dest") or \
+                self._L.h264mi_engine_export_tensor_dest(self._h, n, c_streams, c_slots, C.byref(ld), boxes,
+                                                         len(boxes) if boxes is not None else 0, C.byref(d),
+                                                         out.data_ptr(), out_stride, st) != 0:
+            raise RuntimeError("h264mi_engine_export_tensor_dest failed (stream, slot, window or size out of range?)")
+        return out
+
     def _export_field(self, entry, needs, streams, slots, window, build, out, stream, blocks=False, uv=False):
         """A field export (to_mbinfo, to_residual, to_accmv, to_accres) through
         the library's ``entry``, which needs the retention ``needs``:
@@ -822,7 +919,7 @@ class Engine:
 
     def to_tensor(self, streams: Sequence[int], slots: Sequence[int], window=None, mode: str = "rgb", dtype=None,
                   scale=None, bias=None, mean=None, std=None, out=None, stream=None, size=None, colour=None,
-                  rois=None, fit=None, pad=None, layout="nchw", warps=None, border=None, filter=None):
+                  rois=None, fit=None, pad=None, layout="nchw", warps=None, border=None, filter=None, clip=None):
         """The slots (streams[k], slots[k]) as one ``(n, planes, ch, cw)``
         torch tensor on ``cuda:{self.device}``, built on the GPU and never
         copied to the host: planes R, G, B (``mode="rgb"``, the values of
@@ -894,9 +991,26 @@ class Engine:
         torch's current stream of the device): it starts after the work queued
         there and after every launch queued on the engine, later work on
         ``stream`` sees the tensor, and a later launch that overwrites a slot
-        waits for it.  The host is never synchronised.  ``out``: a contiguous
-        tensor of the result's shape, dtype and device to fill instead of a
-        new ``torch.empty``.  The result is an ordinary torch tensor, so DLPack
+        waits for it.  The host is never synchronised.  ``out``: a tensor of
+        the result's shape, dtype and device to fill instead of a new
+        ``torch.empty`` -- contiguous, or any view whose strides the exports
+        can write through (``dest_of_view``; every form above): a
+        channel slice ``x[:, 1:4]`` of a wider tensor, a tile of a canvas, a
+        permuted clip, rows with a pitch.  Only the view's elements are
+        written.  A view with a column stride other than 1 ("nhwc": a plane
+        stride other than 1), an expanded dimension or overlapping elements is
+        a ValueError that names the stride.
+
+        ``clip`` = T (every form above; the number of items a multiple of T):
+        the items as video clips, ``(n // T, planes, T, rows, cols)`` --
+        contiguous NCTHW, what video models take, written in place by the same
+        kernels instead of ``permute(...).contiguous()`` over the result; with
+        ``layout="nhwc"`` the same shape with the strides of
+        ``torch.channels_last_3d``.  Item k is frame ``k % T`` of clip ``k //
+        T``; with ``rois`` or ``warps`` a clip is a tube, one tracked box over T
+        pictures.  ``out`` then is a 5-D view under the same rules.
+
+        The result is an ordinary torch tensor, so DLPack
         consumers (``torch.utils.dlpack`` / ``__dlpack__``) need nothing further."""
         n, c_streams, c_slots = self._pictures(streams, slots)
         nhwc = tensor_layout(layout) != 0
@@ -910,7 +1024,14 @@ class Engine:
                 window = (0, 0, self.w_mbs * 16, self.h_mbs * 16)
             desc, mats, planes, dtype = warps_desc(warps, size, n, window, self.w_mbs * 16, self.h_mbs * 16, mode, dtype,
                                                    scale, bias, mean, std, colour, border=border, pad=pad, layout=layout)
-            out, st = self._out((len(mats), planes, desc.oh, desc.ow), dtype, out, stream, layout)
+            out, st, dest = self._out_dest((len(mats), planes, desc.oh, desc.ow), dtype, out, stream, layout, clip)
+            if dest is not None:
+                if not hasattr(self._L, "h264mi_engine_export_tensor_warps_dest") or \
+                        self._L.h264mi_engine_export_tensor_warps_dest(self._h, n, c_streams, c_slots, C.byref(desc), mats,
+                                                                       len(mats), C.byref(dest[0]), out.data_ptr(), dest[1],
+                                                                       st) != 0:
+                    raise RuntimeError("h264mi_engine_export_tensor_warps_dest failed (stream or slot out of range?)")
+                return out
             if not hasattr(self._L, "h264mi_engine_export_tensor_warps") or \
                     self._L.h264mi_engine_export_tensor_warps(self._h, n, c_streams, c_slots, C.byref(desc), mats, len(mats),
                                                               out.data_ptr(), planes * desc.oh * desc.ow * out.element_size(),
@@ -927,10 +1048,12 @@ class Engine:
                                                    bias, mean, std, colour, fit=fit, pad=pad, filter=filter)
             name = "h264mi_engine_export_tensor_rois_fit" if fitted else "h264mi_engine_export_tensor_rois"
             oh, ow = (desc.r.oh, desc.r.ow) if fitted else (desc.oh, desc.ow)
+            out, st, dest = self._out_dest((len(boxes), planes, oh, ow), dtype, out, stream, layout, clip)
+            if dest is not None:
+                return self._export_dest(n, c_streams, c_slots, desc, boxes, layout, out, st, dest)
             if nhwc:
                 return self._export_layout(n, c_streams, c_slots, desc, boxes, (len(boxes), planes, oh, ow), dtype, out,
                                            stream, layout)
-            out, st = self._out((len(boxes), planes, oh, ow), dtype, out, stream)
             if not hasattr(self._L, name) or \
                     getattr(self._L, name)(self._h, n, c_streams, c_slots, C.byref(desc), boxes, len(boxes),
                                            out.data_ptr(), planes * oh * ow * out.element_size(), st) != 0:
@@ -941,10 +1064,12 @@ class Engine:
         desc, planes, dtype = tensor_desc(window, mode, dtype, scale, bias, mean, std, size, colour, filter=filter)
         if fitted:
             fd = fit_desc(desc, planes, "letterbox" if fit is None else fit, 114 if pad is None else pad)
+            out, st, dest = self._out_dest((n, planes, desc.oh, desc.ow), dtype, out, stream, layout, clip)
+            if dest is not None:
+                return self._export_dest(n, c_streams, c_slots, fd, None, layout, out, st, dest)
             if nhwc:
                 return self._export_layout(n, c_streams, c_slots, fd, None, (n, planes, desc.oh, desc.ow), dtype, out,
                                            stream, layout)
-            out, st = self._out((n, planes, desc.oh, desc.ow), dtype, out, stream)
             if not hasattr(self._L, "h264mi_engine_export_tensor_fit") or \
                     self._L.h264mi_engine_export_tensor_fit(self._h, n, c_streams, c_slots, C.byref(fd), out.data_ptr(),
                                                             planes * desc.oh * desc.ow * out.element_size(), st) != 0:
@@ -953,9 +1078,11 @@ class Engine:
         shape = (n, planes, desc.ch, desc.cw) if size is None else (n, planes, desc.oh, desc.ow)
         if out is None and min(shape) < 1:
             raise ValueError(f"window {tuple(window)}")
+        out, st, dest = self._out_dest(shape, dtype, out, stream, layout, clip)
+        if dest is not None:
+            return self._export_dest(n, c_streams, c_slots, desc, None, layout, out, st, dest)
         if nhwc:
             return self._export_layout(n, c_streams, c_slots, desc, None, shape, dtype, out, stream, layout)
-        out, st = self._out(shape, dtype, out, stream)
         export = self._L.h264mi_engine_export_tensor if size is None else self._L.h264mi_engine_export_tensor_resized
         if export(self._h, n, c_streams, c_slots, C.byref(desc), out.data_ptr(),
                   planes * shape[2] * shape[3] * out.element_size(), st) != 0:

@@ -321,6 +321,44 @@ H264SwDecRet H264SwDecNextPictureTensorLayout(H264SwDecInst decInst, H264SwDecPi
                                               const h264mi_tensor_layout_desc *desc, void *d_dst, void *hip_stream);
 H264SwDecRet H264SwDecLastPictureTensorRoisLayout(H264SwDecInst decInst, const h264mi_tensor_layout_desc *desc,
                                                   const h264mi_roi *rois, u32 nrois, void *d_dst, void *hip_stream);
+/* Where a pixel export writes: the strides of the destination,
+ * in bytes, so that an export fills a clip (N, C, T, H, W), a slice of a wider
+ * tensor or a tile of a canvas in place.  An item k -- a picture, a box or a
+ * warp -- of planes * rows * cols elements of es bytes starts at
+ *   d_out + (k / clip) * out_stride + (k % clip) * frame
+ * and its element (p, i, j) lies at
+ *   planar:       + p * plane + i * row + j * es
+ *   interleaved:  + i * row + (j * planes + p) * es
+ * NULL, or all zero with clip = 1, is the packed item of the call without a
+ * descriptor, byte for byte.  Contiguous NCTHW: row = 0, frame = rows * cols *
+ * es, plane = T * frame, out_stride = C * plane.
+ * Rules (common/export_desc.h dest_ok; one broken rule refuses the call, nothing
+ * launched): every stride, out_stride included, is a non-negative multiple of
+ * es; row is at least the packed row; plane is 0 when interleaved; clip >= 1
+ * divides the number of items; frame is 0 with clip = 1; reserved is 0; and no
+ * two elements share an address: of the levels (row, rows), (plane, planes) if
+ * planar, (frame, clip) and (out_stride, items / clip), those with a count
+ * above 1, sorted by stride, each have a stride of at least the span of
+ * everything below them (the packed row at the bottom, then (count - 1) *
+ * stride + span).  The levels' order is free: an item stride below the plane
+ * stride (clip.permute(1, 0, 2, 3)) and a frame below the row (a tile grid) are
+ * legal.  The destination's total extent is the caller's business, as
+ * out_stride's always was. */
+typedef struct {
+    int64_t row;     /* bytes between two rows; 0: packed (cols * es, interleaved: cols * planes * es) */
+    int64_t plane;   /* bytes between two planes (planar only; interleaved: must be 0); 0: rows * row */
+    int64_t frame;   /* bytes between two consecutive items of a clip (clip == 1: must be 0) */
+    int32_t clip;    /* T >= 1: items per clip */
+    int32_t reserved;/* 0 */
+} h264mi_tensor_dest;
+/* NextPictureTensorLayout into a strided destination (dest NULL: that call).
+ * One picture is one item, so dest->clip is 1: a caller that fills a clip
+ * moves d_dst itself (d_dst = clip + t * frame).  A bad descriptor is refused
+ * before a picture is taken.  A backend without export_tensor_dest:
+ * H264SWDEC_PARAM_ERR. */
+H264SwDecRet H264SwDecNextPictureTensorDest(H264SwDecInst decInst, H264SwDecPicture *pOutput, u32 flushBuffer,
+                                            const h264mi_tensor_layout_desc *desc, const h264mi_tensor_dest *dest,
+                                            void *d_dst, void *hip_stream);
 /* Affine-warped tensors (warp.hip): rotated boxes, aligned crops.
  * A warp makes (planes, oh, ow) elements from the window t.(x, y, cw, ch) of
  * one picture (even, as for every pixel export; at most 16384 a side).  Six
@@ -887,6 +925,29 @@ int  h264mi_tensor_warps_device_pitch(const void *d_in, const size_t *in_offsets
 int  h264mi_engine_export_tensor_warps(h264mi_engine *e, int n, const int *streams, const int *slots,
                                        const h264mi_tensor_warp_desc *desc, const h264mi_warp *warps, int nwarps,
                                        void *d_out, size_t out_stride, void *hip_stream);
+/* the layout and warp calls above into a strided destination
+ * (h264mi_tensor_dest above): every form they cover, the same
+ * values, item k's element (p, i, j) where the descriptor puts it, and not a
+ * byte written that the descriptor does not address.  dest == NULL is the call
+ * above.  Everything is checked before anything is launched (dest_ok with the
+ * call's items: pictures, boxes or warps); a launch's 32 items may begin and
+ * end inside a clip.  Where d_out, out_stride, frame, plane, row and the packed
+ * row are all multiples of 16, the unresized export stores 16 bytes at a time. */
+int  h264mi_tensor_dest_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width, int height,
+                                     int cpitch, const h264mi_tensor_layout_desc *desc, const h264mi_roi *rois,
+                                     int nrois, const h264mi_tensor_dest *dest, void *d_out, size_t out_stride,
+                                     void *hip_stream);
+int  h264mi_tensor_warps_dest_device_pitch(const void *d_in, const size_t *in_offsets, int npics, int width, int height,
+                                           int cpitch, const h264mi_tensor_warp_desc *desc, const h264mi_warp *warps,
+                                           int nwarps, const h264mi_tensor_dest *dest, void *d_out, size_t out_stride,
+                                           void *hip_stream);
+int  h264mi_engine_export_tensor_dest(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                      const h264mi_tensor_layout_desc *desc, const h264mi_roi *rois, int nrois,
+                                      const h264mi_tensor_dest *dest, void *d_out, size_t out_stride, void *hip_stream);
+int  h264mi_engine_export_tensor_warps_dest(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                            const h264mi_tensor_warp_desc *desc, const h264mi_warp *warps, int nwarps,
+                                            const h264mi_tensor_dest *dest, void *d_out, size_t out_stride,
+                                            void *hip_stream);
 /* the MB side-information field (h264mi_mbinfo_desc above) of npics record
  * batches of w_mbs * h_mbs MbRec each, batch k starting rec_offsets[k] bytes (a
  * host array of multiples of 96; any order, repeats allowed) after d_recs
