@@ -121,6 +121,11 @@ class TensorWarpDesc(C.Structure):
                [("pad", C.c_ubyte * 4), ("layout", C.c_int)]
 
 
+class StatsDesc(C.Structure):
+    """h264mi_stats_desc (include/h264mi.h)."""
+    _fields_ = [(n, C.c_int) for n in ("x", "y", "cw", "ch", "planes", "colour", "flags", "reserved")]
+
+
 class MbInfoDesc(C.Structure):
     """h264mi_mbinfo_desc (include/h264mi.h)."""
     _fields_ = [(n, C.c_int) for n in ("bx", "by", "bw", "bh", "nch", "dtype")] + \
@@ -196,6 +201,11 @@ TENSOR_LAYOUTS = {"nchw": 0, "nhwc": 1}
 WARP_BILINEAR = 0
 WARP_BORDERS = {"constant": 0, "replicate": 1}
 WARPS_MAX_PER_LAUNCH = 32
+# StatsDesc.planes by name, its flag, and the int64 words of a plane record by name
+STATS_PLANES = {"y": 0, "yuv": 1, "rgb": 2}
+STATS_HIST = 1
+STATS_WORDS, STATS_BINS = 8, 256
+STATS_FIELDS = ("count", "sum", "sumsq", "min", "max", "sad", "ssd")
 
 HEADERS_CB = C.CFUNCTYPE(None, C.c_void_p)
 PICTURE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32)
@@ -368,6 +378,18 @@ def mi() -> C.CDLL:
         L.h264mi_engine_export_tensor_warps.restype = i32
         L.H264SwDecLastPictureTensorWarps.argtypes = [vp, wd, wa, u32, vp, vp]
         L.H264SwDecLastPictureTensorWarps.restype = i32
+    if hasattr(L, "h264mi_stats_device_pitch"):             # (optional, as above)
+        sd, ro = C.POINTER(StatsDesc), C.POINTER(Roi)
+        L.h264mi_stats_item_words.argtypes = [sd]
+        L.h264mi_stats_item_words.restype = sz
+        L.h264mi_stats_device_pitch.argtypes = [vp, C.POINTER(sz), vp, C.POINTER(sz), i32, i32, i32, i32, sd, ro, i32, vp,
+                                                sz, vp]
+        L.h264mi_stats_device_pitch.restype = i32
+        L.h264mi_engine_export_stats.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
+                                                 sd, ro, i32, vp, sz, vp]
+        L.h264mi_engine_export_stats.restype = i32
+        L.H264SwDecLastPictureStats.argtypes = [vp, sd, ro, u32, vp, vp]
+        L.H264SwDecLastPictureStats.restype = i32
     if hasattr(L, "h264mi_tensor_dest_device_pitch"):       # (optional, as above)
         ld, ro, de = C.POINTER(TensorLayoutDesc), C.POINTER(Roi), C.POINTER(TensorDest)
         wd, wa = C.POINTER(TensorWarpDesc), C.POINTER(Warp)

@@ -229,6 +229,47 @@ static inline int warps_ok(const h264mi_warp *w, int nwarps, int npics)
     return 1;
 }
 
+/* h264mi_stats_desc: a known plane set, no unknown flag, nothing
+ * reserved, and a colour id 0..3 that only RGB reads (0 otherwise; never
+ * H264MI_TENSOR_COLOUR_STREAM: api.c resolves it first).  Its window has the
+ * pixel exports' rules and no size cap. */
+static inline int stats_desc_fixed_ok(const h264mi_stats_desc *d)
+{
+    return d->planes >= H264MI_STATS_Y && d->planes <= H264MI_STATS_RGB && !(d->flags & ~H264MI_STATS_HIST) &&
+           d->reserved == 0 && d->colour >= 0 &&
+           d->colour <= (d->planes == H264MI_STATS_RGB ? H264MI_TENSOR_COLOUR_BT709_FULL : 0);
+}
+
+static inline int stats_box_ok(int x, int y, int cw, int ch, int width, int height)
+{
+    return x >= 0 && y >= 0 && cw > 0 && ch > 0 && !((x | y | cw | ch) & 1) && cw <= width - x && ch <= height - y;
+}
+
+/* (after stats_desc_fixed_ok) */
+static inline int stats_window_ok(const h264mi_stats_desc *d, int width, int height)
+{
+    return stats_box_ok(d->x, d->y, d->cw, d->ch, width, height);
+}
+
+/* a list of h264mi_roi over npics pictures under d: at least one box, every pic
+ * in [0, npics), every box a window stats_window_ok accepts, and d's own
+ * window reserved (all zero).  All or nothing. */
+static inline int stats_rois_ok(const h264mi_stats_desc *d, const h264mi_roi *r, int nrois, int npics, int width, int height)
+{
+    if (nrois < 1 || !stats_desc_fixed_ok(d) || (d->x | d->y | d->cw | d->ch)) return 0;
+    for (int k = 0; k < nrois; k++)
+        if (r[k].pic < 0 || r[k].pic >= npics || !stats_box_ok(r[k].x, r[k].y, r[k].cw, r[k].ch, width, height)) return 0;
+    return 1;
+}
+
+/* the int64 words of an item, P * L; 0 for a bad plane set or flag */
+static inline size_t stats_item_words(const h264mi_stats_desc *d)
+{
+    if (d->planes < H264MI_STATS_Y || d->planes > H264MI_STATS_RGB || (d->flags & ~H264MI_STATS_HIST)) return 0;
+    return (size_t)(d->planes == H264MI_STATS_Y ? 1 : 3) *
+           (H264MI_STATS_WORDS + (d->flags & H264MI_STATS_HIST ? H264MI_STATS_BINS : 0));
+}
+
 /* h264mi_tensor_dest over items of planes x rows x cols elements
  * of es bytes: the strides an export runs with, the descriptor's zeros filled
  * in (NULL: the packed item, one item per clip) */

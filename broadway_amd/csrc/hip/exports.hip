@@ -1,5 +1,5 @@
 // h264mi engine, export side: the entry points of every export kernel (RGBA,
-// crop, tensors, MB fields, residual, accumulated motion and residual), the
+// crop, tensors, statistics, MB fields, residual, accumulated motion and residual), the
 // engine-level exports over them, and what an engine retains for them
 // (engine_priv.h engine_exports).  Its own translation unit and code object:
 // it never includes recon_kernels.hip, so no change here reaches k_prep,
@@ -10,6 +10,7 @@
 #include "tensor.hip"
 #include "resize.hip"
 #include "warp.hip"
+#include "stats.hip"
 #include "field_store.h"
 #include "mbinfo.hip"
 #include "residual.hip"
@@ -873,6 +874,100 @@ extern "C" int h264mi_engine_export_tensor_warps(h264mi_engine *e, int n, const 
                                                  int nwarps, void *d_out, size_t out_stride, void *stream)
 {
     return h264mi_engine_export_tensor_warps_dest(e, n, streams, slots, desc, warps, nwarps, NULL, d_out, out_stride, stream);
+}
+
+// Picture statistics (stats.hip, include/h264mi.h): item k -- desc's
+// window of picture k, or box k of picture rois[k].pic -- as stats_item_words
+// int64 words at d_out + k * out_stride, against the same window of reference
+// picture k (rois: rois[k].pic) where d_ref names one.  Everything is checked
+// first (common/export_desc.h: one bad box refuses the call); then, per
+// EXPORT_MAX_PICS items, k_stats_init writes every word of their records and
+// k_stats, behind it on the stream, adds the strips' partials -- the item
+// offsets and windows travel in the kernel arguments.  rois is host memory, read
+// here.  -1 (nothing launched) on a bad argument.
+static_assert(H264MI_STATS_Y == STATS_Y && H264MI_STATS_YUV == STATS_YUV && H264MI_STATS_RGB == STATS_RGB &&
+                  H264MI_STATS_WORDS == STATS_WORDS && H264MI_STATS_BINS == STATS_BINS &&
+                  STATS_MAX_ITEMS == EXPORT_MAX_PICS,
+              "include/h264mi.h and stats.hip name the same plane sets, record and items per launch");
+
+extern "C" size_t h264mi_stats_item_words(const h264mi_stats_desc *desc) { return desc ? stats_item_words(desc) : 0; }
+
+// a statistics descriptor, with its boxes (rois == NULL, then nrois == 0: its own window), an export accepts
+static bool stats_desc_ok(const h264mi_stats_desc *d, const h264mi_roi *rois, int nrois, int npics, int width, int height)
+{
+    if (!d || (rois ? nrois < 1 : nrois != 0)) return false;
+    if (rois) return stats_rois_ok(d, rois, nrois, npics, width, height);
+    return stats_desc_fixed_ok(d) && stats_window_ok(d, width, height);
+}
+
+// d_out, out_stride: int64 words, and items that do not overlap
+static bool stats_out_ok(const h264mi_stats_desc *d, int nitems, const void *d_out, size_t out_stride)
+{
+    return export_aligned(d_out, out_stride, 8) && (nitems < 2 || out_stride >= stats_item_words(d) * 8);
+}
+
+extern "C" int h264mi_stats_device_pitch(const void *d_in, const size_t *in_offsets, const void *d_ref,
+                                         const size_t *ref_offsets, int npics, int width, int height, int cpitch,
+                                         const h264mi_stats_desc *desc, const h264mi_roi *rois, int nrois, void *d_out,
+                                         size_t out_stride, void *stream)
+{
+    if (!tensor_pics_ok(d_in, in_offsets, npics, width, height, cpitch, d_out) || !d_ref != !ref_offsets ||
+        !stats_desc_ok(desc, rois, nrois, npics, width, height))
+        return -1;
+    const int nitems = rois ? nrois : npics;
+    // (d_out is looked up too, as for the boxes of the pixel exports: a host address would fault every launch)
+    if (!stats_out_ok(desc, nitems, d_out, out_stride) || h264mi_pointer_device(d_out) < 0) return -1;
+    const bool hist = desc->flags & H264MI_STATS_HIST;
+    stats_args a;
+    a.in = (const uint8_t *)d_in;
+    a.ref = (const uint8_t *)d_ref;
+    a.out = (uint8_t *)d_out;
+    a.width = width; a.height = height; a.cpitch = cpitch;
+    a.col = tensor_colour_sets[desc->colour];       // (set 0 runs the kernel with the reference's literals)
+    for (int k0 = 0; k0 < nitems; k0 += EXPORT_MAX_PICS) {
+        const int n = nitems - k0 < EXPORT_MAX_PICS ? nitems - k0 : EXPORT_MAX_PICS;
+        int strips = 1;
+        for (int k = 0; k < EXPORT_MAX_PICS; k++) {
+            const h264mi_roi w = {k0 + k, desc->x, desc->y, desc->cw, desc->ch};
+            const h264mi_roi &b = rois ? rois[k0 + (k < n ? k : 0)] : w;
+            const int pic = k < n ? b.pic : 0;
+            a.in_off[k] = k < n ? in_offsets[pic] : 0;
+            a.ref_off[k] = k < n && ref_offsets ? ref_offsets[pic] : 0;
+            a.out_off[k] = k < n ? (size_t)(k0 + k) * out_stride : 0;
+            a.win[k][0] = b.x; a.win[k][1] = b.y; a.win[k][2] = b.cw; a.win[k][3] = b.ch;
+            const long long units = (long long)((b.cw + STATS_UNIT_COLS - 1) / STATS_UNIT_COLS) * (b.ch >> 1);
+            const int s = (int)((units + STATS_STRIP_UNITS - 1) / STATS_STRIP_UNITS);
+            if (k < n && s > strips) strips = s;
+        }
+        stats_launch(desc->planes, hist, d_ref != NULL, desc->colour != 0, strips, n, (hipStream_t)stream, a);
+        HIPCHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+// statistics of the frame slots, or of boxes over them (rois[k].pic indexes the
+// n slots), against the reference slots where named: one ordering of the two
+// streams per call
+extern "C" int h264mi_engine_export_stats(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                          const int *ref_streams, const int *ref_slots, const h264mi_stats_desc *desc,
+                                          const h264mi_roi *rois, int nrois, void *d_out, size_t out_stride, void *stream)
+{
+    if (!e || n < 1 || !streams || !slots || !d_out || !ref_streams != !ref_slots) return -1;
+    const int width = e->w * 16, height = e->h * 16;
+    if (!stats_desc_ok(desc, rois, nrois, n, width, height) || !stats_out_ok(desc, rois ? nrois : n, d_out, out_stride))
+        return -1;
+    for (int k = 0; ref_streams && k < n; k++)
+        if (ref_streams[k] < 0 || ref_streams[k] >= e->nstreams || ref_slots[k] < 0 || ref_slots[k] >= e->nslots) return -1;
+    return export_ordered(e, n, streams, slots, d_out, out_stride, 8, stream, [&] {
+        std::vector<size_t> off((size_t)n), roff((size_t)n);
+        for (int k = 0; k < n; k++) {
+            off[k] = e->frame_bytes * ((size_t)streams[k] * e->nslots + slots[k]);
+            if (ref_streams) roff[k] = e->frame_bytes * ((size_t)ref_streams[k] * e->nslots + ref_slots[k]);
+        }
+        return h264mi_stats_device_pitch(e->d_frames, off.data(), ref_streams ? e->d_frames : NULL,
+                                         ref_streams ? roff.data() : NULL, n, width, height, e->cpitch, desc, rois, nrois,
+                                         d_out, out_stride, e->st);
+    });
 }
 
 // Motion vectors and MB side information as planar fields (mbinfo.hip): the

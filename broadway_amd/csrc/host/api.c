@@ -609,6 +609,64 @@ H264SwDecRet H264SwDecLastPictureTensorWarps(H264SwDecInst decInst, const h264mi
     return H264SWDEC_PIC_RDY;
 }
 
+/* Statistics of the delivered picture (include/h264mi.h): a
+ * LastPicture call like the boxes above, over the backend's export_stats.
+ * Without boxes the window is the SPS crop window (desc->cw == 0) or a window
+ * inside it, in its coordinates; boxes are in its coordinates too: the crop
+ * offset is added here.  H264MI_TENSOR_COLOUR_STREAM (RGB) is taken out of the
+ * descriptor ahead of the rules, which know ids only, and resolves from the
+ * delivered picture's VUI (BT.601 where it names no matrix).  No reference
+ * picture: the decoder does not hold the previously delivered slot. */
+H264SwDecRet H264SwDecLastPictureStats(H264SwDecInst decInst, const h264mi_stats_desc *desc, const h264mi_roi *rois,
+                                       u32 nrois, void *d_dst, void *hip_stream)
+{
+    if (decInst == NULL || desc == NULL || d_dst == NULL) return H264SWDEC_PARAM_ERR;
+    DecContainer *c = (DecContainer *)decInst;
+    if (!c->dec.be.export_stats) return H264SWDEC_PARAM_ERR;
+    h264mi_stats_desc m = *desc;
+    const int from_stream = m.planes == H264MI_STATS_RGB && m.colour == H264MI_TENSOR_COLOUR_STREAM;
+    if (from_stream) m.colour = 0;
+    if ((rois ? nrois < 1 || nrois > 0x7FFFFFFF / sizeof(h264mi_roi) || (m.x | m.y | m.cw | m.ch) : nrois != 0) ||
+        !stats_desc_fixed_ok(&m) || !export_aligned(d_dst, 0, 8))
+        return H264SWDEC_PARAM_ERR;
+    for (u32 k = 0; rois && k < nrois; k++)
+        if (rois[k].pic != 0) return H264SWDEC_PARAM_ERR;
+    const Sps *s = h264dec_active_sps(&c->dec);
+    if (!s || !c->dec.last_out_slot1) return H264SWDEC_OK;      /* no picture delivered */
+    const export_window w = sps_crop_window(s);
+    h264mi_roi *b = NULL;
+    int ok = 1;
+    if (rois) {
+        b = (h264mi_roi *)malloc(nrois * sizeof(*b));
+        if (!b) return H264SWDEC_MEMFAIL;
+        for (u32 k = 0; k < nrois && ok; k++) {
+            b[k] = rois[k];
+            ok = stats_box_ok(b[k].x, b[k].y, b[k].cw, b[k].ch, w.cw, w.ch);
+            if (ok) { b[k].x += w.x; b[k].y += w.y; }
+        }
+        ok = ok && stats_rois_ok(&m, b, (int)nrois, 1, 16 * s->w_mbs, 16 * s->h_mbs);
+    } else {
+        if (m.cw == 0) {
+            ok = !(m.x | m.y | m.ch);
+            m.cw = w.cw; m.ch = w.ch;
+        }
+        ok = ok && stats_window_ok(&m, w.cw, w.ch);
+        if (ok) { m.x += w.x; m.y += w.y; }
+        ok = ok && stats_window_ok(&m, 16 * s->w_mbs, 16 * s->h_mbs);
+    }
+    const int colour = from_stream ? h264mi_tensor_colour_resolve(H264MI_TENSOR_MODE(H264MI_TENSOR_RGB, H264MI_TENSOR_COLOUR_STREAM,
+                                                                                     H264MI_TENSOR_UNSPEC_BT601),
+                                                                  c->dec.last_out_vui_matrix, c->dec.last_out_vui_full, w.cw, w.ch)
+                                   : m.colour;
+    m.colour = colour;
+    /* (a failure of the export itself: d_dst not on the decoder's GPU) */
+    ok = ok && !c->dec.be.export_stats(c->dec.be.ctx, c->dec.last_out_slot1 - 1, &m, b, rois ? (int)nrois : 0, d_dst, hip_stream);
+    free(b);
+    if (!ok) return H264SWDEC_PARAM_ERR;
+    c->dec.last_tensor_colour1 = colour + 1;
+    return H264SWDEC_PIC_RDY;
+}
+
 H264SwDecRet H264SwDecGetTiming(H264SwDecInst decInst, double *parse_s, double *submit_s, double *wait_s,
                                 double *copy_s, u32 *pictures)
 {

@@ -103,6 +103,13 @@ typedef struct H264Backend {
      * when the backend cannot */
     int  (*export_tensor_warps)(void *ctx, int slot, const void *desc, const void *warps, int nwarps, void *d_dst,
                                 void *hip_stream);
+    /* optional: the statistics of desc (a checked h264mi_stats_desc in picture
+     * coordinates) of slot -- of its window (rois NULL, nrois 0) or of the
+     * nrois boxes rois (h264mi_roi, every pic 0; desc's window zero) --, item r
+     * packed behind item r - 1 at d_dst, ordered like export_tensor; no
+     * retention; 0 ok, -1 failure; NULL when the backend cannot */
+    int  (*export_stats)(void *ctx, int slot, const void *desc, const void *rois, int nrois, void *d_dst,
+                         void *hip_stream);
     /* optional: host memory for the output frames (pinned by the HIP
      * backend, so each picture's D2H copy runs at DMA speed); NULL: malloc */
     void *(*host_alloc)(void *ctx, size_t bytes);

@@ -781,6 +781,33 @@ static int hb_export_tensor_warps(void *vctx, int slot, const void *desc, const 
     return hb_export(vctx, slot, engine_export_warps, &c, d_dst, hip_stream);
 }
 
+// statistics of slot, of its window or of boxes over it (a member of its own,
+// with no retention and no reference picture): the list travels through
+// hb_export as one descriptor, item r's words packed behind item r - 1's
+extern "C" int h264mi_engine_export_stats(h264mi_engine *e, int n, const int *streams, const int *slots,
+                                          const int *ref_streams, const int *ref_slots, const h264mi_stats_desc *desc,
+                                          const h264mi_roi *rois, int nrois, void *d_out, size_t out_stride,
+                                          void *hip_stream) __attribute__((weak));
+struct StatsCall {
+    const h264mi_stats_desc *desc;
+    const h264mi_roi *rois;
+    int nrois;
+};
+
+static int engine_export_stats(h264mi_engine *e, int n, const int *streams, const int *slots, const StatsCall *c,
+                               void *d_out, size_t, void *hip_stream)
+{
+    return h264mi_engine_export_stats(e, n, streams, slots, NULL, NULL, c->desc, c->rois, c->nrois, d_out,
+                                      stats_item_words(c->desc) * 8, hip_stream);
+}
+
+static int hb_export_stats(void *vctx, int slot, const void *desc, const void *rois, int nrois, void *d_dst,
+                           void *hip_stream)
+{
+    const StatsCall c = {(const h264mi_stats_desc *)desc, (const h264mi_roi *)rois, nrois};
+    return hb_export(vctx, slot, engine_export_stats, &c, d_dst, hip_stream);
+}
+
 // Pinned host blocks (decoder output frames) kept after free for the next
 // decoder instance: pinning tens of MB per instance is a large share of a
 // short stream's host time.  Exact-size reuse, at most H264MI_HOST_POOL_MB
@@ -935,6 +962,7 @@ extern "C" H264Backend h264mi_hip_backend_create(int device)
     be.export_tensor_layout = h264mi_engine_export_tensor_layout ? hb_export_tensor_layout : NULL;
     be.export_tensor_dest = h264mi_engine_export_tensor_dest ? hb_export_tensor_dest : NULL;
     be.export_tensor_warps = h264mi_engine_export_tensor_warps ? hb_export_tensor_warps : NULL;
+    be.export_stats = h264mi_engine_export_stats ? hb_export_stats : NULL;
     be.host_alloc = hb_host_alloc;
     be.host_free = hb_host_free;
     be.records_wait = hb_records_wait;

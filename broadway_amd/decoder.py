@@ -523,6 +523,40 @@ class Decoder:
             raise RuntimeError(f"warps: the backend cannot export the warps ({ret}; there is no host fallback)")
         return out
 
+    def stats(self, boxes=None, planes="y", hist=False, colour=None, window=None):
+        """Statistics of the delivered picture as one new ``int64`` torch
+        tensor of shape ``(K or 1, P, L)`` on the decoder's GPU, on torch's
+        current stream (``H264SwDecLastPictureStats``; the picture is not
+        exported): per box of ``boxes`` = [(x, y, cw, ch), ...], or for
+        ``window`` (None: everything), both in the coordinates of the picture
+        ``onPictureDecoded`` receives with ``crop`` or ``tensor``, even and
+        inside it; ``planes``, ``hist`` and ``colour`` as for
+        ``Engine.to_stats`` (``engine.stats_fields`` names the words), and
+        ``colour="stream"`` takes the set the picture's VUI names, which
+        ``tensor_colour`` then reports.  There is no reference picture here
+        (sad and ssd are 0): compare consecutive histograms to detect a cut.
+        Callable when ``rois`` is.  ValueError for a bad argument, RuntimeError
+        before a picture was delivered."""
+        import torch
+        from .engine import stats_desc
+        _, _, cw, ch = self._crop_window()
+        try:
+            rois = None if boxes is None else [(0,) + tuple(b) for b in boxes]
+        except TypeError:
+            raise ValueError(f"stats: boxes {boxes!r}: a list of (x, y, cw, ch)") from None
+        desc, arr, P, L = stats_desc(planes, window, rois, hist, colour, 1, cw or None, ch or None, stream_ok=True)
+        if not hasattr(self, "_device"):
+            self._device = int(os.environ.get("H264MI_DEVICE") or 0)
+        out, st = self._device_empty((len(arr) if arr is not None else 1, P, L), torch.int64)
+        last = getattr(self._L, "H264SwDecLastPictureStats", None)
+        ret = last(self._inst, C.byref(desc), arr, len(arr) if arr is not None else 0, out.data_ptr(), st) \
+            if last else _lib.H264SWDEC_PARAM_ERR
+        if ret == _lib.H264SWDEC_OK:
+            raise RuntimeError("stats: no picture has been delivered since the last decode")
+        if ret != _lib.H264SWDEC_PIC_RDY:
+            raise RuntimeError(f"stats: the backend cannot take the statistics ({ret}; there is no host fallback)")
+        return out
+
     @property
     def tensor_colour(self) -> Optional[str]:
         """The colour set of the last tensor delivered ("reference",

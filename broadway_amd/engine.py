@@ -512,6 +512,82 @@ def warps_desc(warps, size, npics, window, width, height, mode="rgb", dtype=None
     return d, arr, planes, dtype
 
 
+def stats_desc(planes="y", window=None, rois=None, hist=False, colour=None, npics=1, width=None, height=None,
+               stream_ok=False):
+    """(``_lib.StatsDesc``, ``_lib.Roi`` array or None, P, L) of a statistics
+    export (Engine.to_stats, Decoder.stats): ``planes`` "y", "yuv" or "rgb";
+    ``window`` = (x, y, cw, ch) or ``rois`` = [(k, x, y, cw, ch), ...] over
+    ``npics`` pictures of width x height (None: sizes are not judged here) --
+    never both; ``window`` None without boxes leaves the descriptor's window
+    zero (the Decoder: the whole delivered picture).  ``hist``: the 256 bins
+    behind the 8 words.  ``colour``: a key of ``_lib.TENSOR_COLOURS``, with
+    "rgb" only; "stream" belongs to the Decoder (``stream_ok``).  P plane
+    records of L int64 words per item.  The rules of include/h264mi.h: every
+    window even and inside the picture, a non-empty box list, k in [0, npics).
+    ValueError otherwise."""
+    if not isinstance(planes, str) or planes not in _lib.STATS_PLANES:
+        raise ValueError(f"planes {planes!r}: one of {sorted(_lib.STATS_PLANES)}")
+    d = _lib.StatsDesc()
+    d.planes = _lib.STATS_PLANES[planes]
+    d.flags = _lib.STATS_HIST if hist else 0
+    if colour is not None:
+        if planes != "rgb":
+            raise ValueError(f"colour: planes {planes!r} has no colour set (only 'rgb')")
+        if not isinstance(colour, str) or colour not in _lib.TENSOR_COLOURS:
+            raise ValueError(f"colour {colour!r}: one of {sorted(_lib.TENSOR_COLOURS)}")
+        if colour == "stream" and not stream_ok:
+            raise ValueError("colour 'stream': Decoder.stats only (an engine knows no stream)")
+        d.colour = _lib.TENSOR_COLOURS[colour]
+
+    def box(b, what):
+        x, y, cw, ch = b
+        if (x | y | cw | ch) & 1 or x < 0 or y < 0 or cw < 2 or ch < 2 or \
+                (width is not None and cw > width - x) or (height is not None and ch > height - y):
+            raise ValueError(f"{what} {tuple(b)}: even and inside {width} x {height}")
+
+    arr = None
+    if rois is not None:
+        if window is not None:
+            raise ValueError("rois: goes without a window (every box is its own)")
+        try:
+            given = [tuple(b) for b in rois]
+            boxes = [tuple(int(v) for v in b) for b in given]
+            if any(len(b) != 5 for b in boxes) or boxes != given:
+                raise ValueError
+        except (TypeError, ValueError):
+            raise ValueError(f"rois {rois!r}: a list of (k, x, y, cw, ch) integers") from None
+        if not boxes:
+            raise ValueError("rois: an empty list")
+        for b in boxes:
+            if not 0 <= b[0] < npics:
+                raise ValueError(f"rois: box {b}: picture {b[0]} of {npics}")
+            box(b[1:], "rois: box")
+        arr = (_lib.Roi * len(boxes))(*[_lib.Roi(*b) for b in boxes])
+    elif window is not None:
+        try:
+            given = tuple(window)
+            win = tuple(int(v) for v in given)
+            if len(win) != 4 or win != given:
+                raise ValueError
+        except (TypeError, ValueError):
+            raise ValueError(f"window {window!r}: (x, y, cw, ch) integers") from None
+        box(win, "window")
+        d.x, d.y, d.cw, d.ch = win
+    return d, arr, 1 if planes == "y" else 3, _lib.STATS_WORDS + (_lib.STATS_BINS if hist else 0)
+
+
+def stats_fields(t):
+    """Named views of a statistics tensor ``t`` of shape (..., L), L = 8 or 264,
+    without a copy: ``count, sum, sumsq, min, max, sad, ssd`` of shape (...),
+    and ``hist`` of shape (..., 256) where L holds it."""
+    if t.shape[-1] not in (_lib.STATS_WORDS, _lib.STATS_WORDS + _lib.STATS_BINS):
+        raise ValueError(f"stats_fields: a last dimension of {_lib.STATS_WORDS} or {_lib.STATS_WORDS + _lib.STATS_BINS} words")
+    out = {name: t[..., i] for i, name in enumerate(_lib.STATS_FIELDS)}
+    if t.shape[-1] > _lib.STATS_WORDS:
+        out["hist"] = t[..., _lib.STATS_WORDS:]
+    return out
+
+
 def _field_channels(channels, table, max_ch):
     """The ids of ``channels`` (a name or names of ``table``, 1..max_ch of them)."""
     if isinstance(channels, str):
@@ -1100,6 +1176,45 @@ class Engine:
                                                            len(boxes) if boxes is not None else 0, out.data_ptr(),
                                                            shape[1] * shape[2] * shape[3] * out.element_size(), st) != 0:
             raise RuntimeError("h264mi_engine_export_tensor_layout failed (stream, slot, window or size out of range?)")
+        return out
+
+    def to_stats(self, streams: Sequence[int], slots: Sequence[int], planes="y", window=None, rois=None, hist=False,
+                 ref=None, colour=None, out=None, stream=None):
+        """Statistics of the pictures in the slots (streams[k], slots[k]) as one
+        ``int64`` torch tensor of shape ``(N or K, P, L)`` on
+        ``cuda:{self.device}`` (stats.hip, ``stats_desc``; nothing is exported
+        and nothing reaches the host): per item -- ``window`` = (x, y, cw, ch)
+        of each of the N pictures (None: all of it), or the K boxes ``rois`` =
+        [(k, x, y, cw, ch), ...] -- and per plane of ``planes`` ("y": P = 1;
+        "yuv", chroma at its own resolution, and "rgb", the uint8 samples of
+        ``to_tensor`` under ``colour``: P = 3) the L = 8 words ``count, sum,
+        sumsq, min, max, sad, ssd, 0`` and, with ``hist``, 256 bins behind
+        them (``stats_fields`` names them).  ``ref`` = (ref_streams,
+        ref_slots), as many slots: sad and ssd of picture k against reference k
+        over the same window (0 without).  Exact integers; ``out`` and
+        ``stream`` as for ``to_tensor``: no host synchronisation, and a later
+        decode into a named slot waits."""
+        import torch
+        n, c_streams, c_slots = self._pictures(streams, slots)
+        if window is None and rois is None:
+            window = (0, 0, self.w_mbs * 16, self.h_mbs * 16)
+        desc, boxes, P, L = stats_desc(planes, window, rois, hist, colour, n, self.w_mbs * 16, self.h_mbs * 16)
+        c_rs = c_rl = None
+        if ref is not None:
+            try:
+                rs, rl = ref
+                if len(rs) != n or len(rl) != n:
+                    raise ValueError
+            except (TypeError, ValueError):
+                raise ValueError(f"ref: (ref_streams, ref_slots) naming {n} pictures, one per picture") from None
+            c_rs, c_rl = (C.c_int * n)(*rs), (C.c_int * n)(*rl)
+        items = len(boxes) if boxes is not None else n
+        out, st = self._out((items, P, L), torch.int64, out, stream)
+        if not hasattr(self._L, "h264mi_engine_export_stats") or \
+                self._L.h264mi_engine_export_stats(self._h, n, c_streams, c_slots, c_rs, c_rl, C.byref(desc), boxes,
+                                                   len(boxes) if boxes is not None else 0, out.data_ptr(), P * L * 8,
+                                                   st) != 0:
+            raise RuntimeError("h264mi_engine_export_stats failed (stream, slot or window out of range?)")
         return out
 
     def keep_records(self, on: bool = True) -> None:

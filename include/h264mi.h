@@ -405,6 +405,57 @@ typedef struct { h264mi_tensor_desc t; int ow, oh, filter, border; unsigned char
  * it.  Return codes are H264SwDecLastPictureTensorRois's. */
 H264SwDecRet H264SwDecLastPictureTensorWarps(H264SwDecInst decInst, const h264mi_tensor_warp_desc *desc,
                                              const h264mi_warp *warps, u32 nwarps, void *d_dst, void *hip_stream);
+/* Picture statistics (stats.hip): answers about a picture without
+ * exporting it -- a scene cut, a black or frozen frame, a clip's mean and
+ * standard deviation, a box's colour histogram, the PSNR of two decodes -- from
+ * one pass over the frame slot, as exact integers.  An item is one window (x,
+ * y, cw, ch: the pixel exports' rules -- even, inside the picture -- with no
+ * size cap) of one picture, or one box of a box list (h264mi_roi above; the
+ * descriptor's own window is then reserved: all zero).  Its result is P plane
+ * records of L little-endian int64 words, contiguous; P = 1 for
+ * H264MI_STATS_Y, 3 for H264MI_STATS_YUV and H264MI_STATS_RGB; L =
+ * H264MI_STATS_WORDS, plus H264MI_STATS_BINS with the flag H264MI_STATS_HIST:
+ *   0  count   samples of the plane in the item (U and V: (cw / 2) (ch / 2))
+ *   1  sum     sum of s                    2  sumsq   sum of s^2
+ *   3  min                                 4  max
+ *   5  sad     sum of |s - r| against the reference picture; 0 without one
+ *   6  ssd     sum of (s - r)^2; 0 without one
+ *   7  reserved: 0
+ *   8 .. 263   hist[v]: samples equal to v (H264MI_STATS_HIST only)
+ * The samples s: Y and YUV take the stored samples of the window, chroma at
+ * its own 4:2:0 resolution (not replicated); RGB takes exactly the uint8 values
+ * of the unresized tensor above for `colour` = 0..3, so its statistics are
+ * those of that tensor.  A reference is a second picture list of the same
+ * length: item k -- box k of picture pic -- is compared with the same window
+ * of reference picture k -- pic.  Every word of every record is written
+ * whatever the destination held; there is no floating point, and the result
+ * does not depend on the order of summation.
+ * Rules: planes one of the three; flags 0 or H264MI_STATS_HIST; reserved 0;
+ * colour 0..3 with RGB and 0 otherwise (the H264SwDec call also takes
+ * H264MI_TENSOR_COLOUR_STREAM with RGB); the window, or every box, even and
+ * inside the picture; one bad box refuses the list. */
+enum { H264MI_STATS_Y = 0, H264MI_STATS_YUV = 1, H264MI_STATS_RGB = 2 };
+#define H264MI_STATS_HIST  1        /* flags */
+#define H264MI_STATS_WORDS 8
+#define H264MI_STATS_BINS  256
+typedef struct { int x, y, cw, ch, planes, colour, flags, reserved; } h264mi_stats_desc;
+/* the int64 words of one item, P * L; 0 for a bad planes / flags.  A pure function. */
+size_t h264mi_stats_item_words(const h264mi_stats_desc *desc);
+/* Statistics of the picture the last H264SwDecNextPicture* call delivered, as
+ * H264SwDecLastPictureTensorRois takes boxes: valid until the next
+ * H264SwDecDecode, the DPB is not touched.  rois == NULL (nrois 0): the
+ * descriptor's window, relative to the delivered (SPS crop) window and inside
+ * it, cw == 0 taking all of it; else every pic is 0 and every box is in the
+ * crop window's coordinates -- the call adds the crop offset.  Item r's words
+ * at d_dst + r * h264mi_stats_item_words(desc) * 8 bytes (d_dst a multiple of
+ * 8), ordered on `hip_stream`.  colour == H264MI_TENSOR_COLOUR_STREAM (RGB)
+ * resolves from the delivered picture's VUI -- BT.601 where it names no
+ * matrix -- and H264SwDecLastTensorColour reports it.  There is no reference
+ * picture here: the decoder does not hold the previously delivered picture's
+ * slot, so a decoder user detects cuts from consecutive histograms.
+ * Return codes are H264SwDecLastPictureTensorRois's. */
+H264SwDecRet H264SwDecLastPictureStats(H264SwDecInst decInst, const h264mi_stats_desc *desc, const h264mi_roi *rois,
+                                       u32 nrois, void *d_dst, void *hip_stream);
 /* Motion vectors and MB side information as a device tensor (mbinfo.hip, DESIGN
  * 3.5d; elsewhere: ffmpeg's export_mvs).  The field lives on the luma 4x4-block
  * grid of the MB-aligned picture, BW = 4 * w_mbs columns by BH = 4 * h_mbs
@@ -948,6 +999,26 @@ int  h264mi_engine_export_tensor_warps_dest(h264mi_engine *e, int n, const int *
                                             const h264mi_tensor_warp_desc *desc, const h264mi_warp *warps, int nwarps,
                                             const h264mi_tensor_dest *dest, void *d_out, size_t out_stride,
                                             void *hip_stream);
+/* picture statistics (h264mi_stats_desc above): item k -- desc's window of
+ * picture k of the picture list, or with rois (a host array, read before the
+ * call returns; NULL with nrois 0: none) box k of picture rois[k].pic -- as
+ * h264mi_stats_item_words(desc) int64 words at d_out + k * out_stride.  d_ref /
+ * ref_offsets (ref_streams / ref_slots), both NULL for none, name as many
+ * reference pictures of the same size and pitch: picture k's reference is
+ * reference k.  d_out and out_stride are multiples of 8, and with more than
+ * one item out_stride is at least the item's bytes; nothing outside the items'
+ * words is written, and every word of them is.  One small launch that fills
+ * the records, then the kernel, per H264MI_ROIS_MAX_PER_LAUNCH items; any
+ * number of items.  The engine call is ordered like every engine export (no
+ * host synchronisation; a later decode into a named slot, reference slots
+ * included, waits) and refuses H264MI_TENSOR_COLOUR_STREAM.  -1 on a bad
+ * argument, nothing launched. */
+int  h264mi_stats_device_pitch(const void *d_in, const size_t *in_offsets, const void *d_ref, const size_t *ref_offsets,
+                               int npics, int width, int height, int cpitch, const h264mi_stats_desc *desc,
+                               const h264mi_roi *rois, int nrois, void *d_out, size_t out_stride, void *hip_stream);
+int  h264mi_engine_export_stats(h264mi_engine *e, int n, const int *streams, const int *slots, const int *ref_streams,
+                                const int *ref_slots, const h264mi_stats_desc *desc, const h264mi_roi *rois, int nrois,
+                                void *d_out, size_t out_stride, void *hip_stream);
 /* the MB side-information field (h264mi_mbinfo_desc above) of npics record
  * batches of w_mbs * h_mbs MbRec each, batch k starting rec_offsets[k] bytes (a
  * host array of multiples of 96; any order, repeats allowed) after d_recs
